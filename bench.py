@@ -7,13 +7,17 @@ Workload at N=1: BASELINE configs[2] "batch of 128 independent synthetic sequenc
 latency case and a parity test); N>1 shards 128 sequences per GPU with no data-path collective (weak scaling).
 Frames are rendered on the device outside the timed region; steady state only (after solver_flag == NON_LINEAR).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no torchrun environment re-executes itself under `python -m torch.distributed.run` with N ranks (one per
 GPU) and fails loudly if fewer than N devices are visible; under torchrun (WORLD_SIZE set) N must equal WORLD_SIZE.
-The timed region is K steps bracketed by barrier + synchronize; it is repeated `--repeats` times on fresh frames and `value` is the
-MEDIAN repeat (all repeats are listed).  Prints ONE JSON line on rank 0 with `roofline` (dominant kernel), `roofline_kernels`
-(the next heaviest kernels) and `cpu_baseline` objects.
+A plain run sets up, warms up, times exactly K steps (bracketed by barrier + synchronize) and prints ONE JSON line on rank 0;
+`ms_per_step` is the time of one timed step.  Frames are rendered on the device at most FRAME_BUDGET bytes ahead, outside the timed
+region: a long run is timed in chunks whose times are summed.  `--dump-outputs DIR` writes what the last timed step left behind for a
+caller (windows, odometry, status of every sequence) as DIR/<name>.npy.
+`--full` also measures everything beyond the headline: the timed region repeated `--repeats` (10) times on fresh frames with `value`
+the MEDIAN repeat, per-kernel times with `roofline` (dominant kernel) / `roofline_kernels`, the `cpu_baseline` and `parity` legs, the
+PCIe-inclusive and IMU-streaming legs and the auxiliary batch sizes / configurations; the detail object goes to a side file and stderr.
 """
 import argparse
 import json
@@ -35,6 +39,38 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 FP64_PEAK_TFLOPS = 78.6   # MI355X FP64 vector == FP64 matrix peak (MI355X_MICROARCH.md has no f64 row)
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: 8.0 TB/s spec
+FRAME_BUDGET = 32 << 30   # bytes of rendered frames held in HBM at a time (S = 128: 291 frames; any --steps fits)
+DUMP_BUDGET = 64 << 20    # --dump-outputs: at most this many bytes in all (a fixed sample of the sequences beyond it)
+
+
+def frame_slots(S, cfg, F):
+    """frames of S sequences that fit FRAME_BUDGET (all F when they do)"""
+    return max(1, min(F, FRAME_BUDGET // (S * cfg.height * cfg.width * 3)))
+
+
+def feed_rendered(b, syn, torch, gray, depth, seq0, times, f0, n, barrier=None):
+    """vio_feed of frames f0 .. f0 + n - 1 of sequences seq0 .. seq0 + S - 1 from HBM.  The frames are rendered into the len(gray) slots of
+    gray / depth one chunk at a time, outside the timed region; returns the seconds from the first feed of each chunk to the device
+    synchronisation after its last, summed over the chunks.  barrier (N > 1 ranks) runs before and after every timed chunk."""
+    S = gray.shape[1]
+    el = 0.0
+    for c in range(f0, f0 + n, len(gray)):
+        m = min(len(gray), f0 + n - c)
+        for i in range(m):        # (the slots are free: the previous chunk ended in b.sync + synchronize)
+            syn.render_device(S, seq0, float(times[c + i]), gray[i], depth[i])
+        torch.cuda.synchronize()
+        if barrier:
+            barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(m):
+            b.feed(gray[i], depth[i], np.full(S, times[c + i]), on_device=True)
+        b.sync()
+        torch.cuda.synchronize()
+        el += time.perf_counter() - t0
+        if barrier:
+            barrier()
+    return el
 
 
 def backend_flops(I, O, F, k_obs, W, S_imu):
@@ -68,28 +104,18 @@ def aux_rate(P, vio_ct, torch, cfg, sc, dev, S, n_pre, Wm, K, lag=0, seq0=0):
     H, Wd = cfg.height, cfg.width
     F = n_pre + Wm + K
     syn = P.Synth(sc)
-    gray = torch.empty((F, S, H, Wd), dtype=torch.uint8, device=dev)
-    depth = torch.empty((F, S, H, Wd), dtype=torch.uint16, device=dev)
+    slots = frame_slots(S, cfg, F)
+    gray = torch.empty((slots, S, H, Wd), dtype=torch.uint8, device=dev)
+    depth = torch.empty((slots, S, H, Wd), dtype=torch.uint16, device=dev)
     times = vio_ct.frame_times(sc, F)
-    for f in range(F):
-        syn.render_device(S, seq0, float(times[f]), gray[f], depth[f])
     nimu = int(F / sc.cam_rate * sc.imu_rate) + 64
     b = P.VioBatch(cfg, S, imu_capacity=nimu + 64)
     b.set_tracker_lag(lag)
     imu = [syn.imu(seq0 + s, nimu) for s in range(S)]
     b.push_imu_batch(np.stack([x[0] for x in imu]), np.stack([x[1] for x in imu]), np.stack([x[2] for x in imu]))
-    for f in range(n_pre + Wm):
-        b.feed(gray[f], depth[f], np.full(S, times[f]), on_device=True)
-    b.sync()
-    torch.cuda.synchronize()
+    feed_rendered(b, syn, torch, gray, depth, seq0, times, 0, n_pre + Wm)
     b.profile_begin(K)
-    t0 = time.perf_counter()
-    for k in range(K):
-        f = n_pre + Wm + k
-        b.feed(gray[f], depth[f], np.full(S, times[f]), on_device=True)
-    b.sync()
-    torch.cuda.synchronize()
-    el = time.perf_counter() - t0
+    el = feed_rendered(b, syn, torch, gray, depth, seq0, times, n_pre + Wm, K)
     _, kms = b.profile_end()
     stats = b.status_all()
     ok = all(st.solver_flag == 1 for st in stats) and float(np.mean([st.iterations for st in stats])) >= 3.0   # (healthy solves of this workload take 4 - 8 iterations)
@@ -191,6 +217,16 @@ def device_identity(torch, index):
     return ident
 
 
+def write_outputs(out_dir, outputs):
+    """out_dir/<name>.npy in float64, at most DUMP_BUDGET bytes: beyond it a fixed (seeded) sample of the sequences, the same in every run"""
+    n = len(outputs["window"])
+    keep = min(n, (DUMP_BUDGET - (1 << 16)) // sum(a[0].nbytes for a in outputs.values()))
+    rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False)) if keep < n else slice(None)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[rows], np.float64))
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -204,21 +240,29 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=10, help="the K-step timed region is run this many times (fresh frames); value = median. "
-                    "The default gives 10 x 20 = 200 timed frames per sequence under the driver's --steps 20 (SURVEY.md 8d asks for >= 200)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure (the defaults marked --full below, "
+                    "per-kernel times and rooflines, the detail object)")
+    ap.add_argument("--repeats", type=int, default=None, help="the K-step timed region is run this many times (fresh frames); value = median. "
+                    "Default 1; --full: 10, i.e. 10 x 20 = 200 timed frames per sequence at --steps 20 (SURVEY.md 8d asks for >= 200)")
     ap.add_argument("--seqs", type=int, default=128, help="sequences per GPU")
-    ap.add_argument("--cpu-seqs", type=int, default=8, help="sequences replayed through the CPU oracle on rank 0 (0 = skip)")
-    ap.add_argument("--cpu-procs", type=int, default=-1, help="oracle processes for the all-core CPU baseline, one sequence each "
-                    "(-1 = every core this process may run on, 0 = skip)")
-    ap.add_argument("--aux", type=int, default=1, help="1 (default): also measure S = 256 and S = 512 sequences per GPU and the lag-0 ordering "
-                    "at S (reported as aux_s256 / aux_s512 / lag0, never as value); 0 = skip")
+    ap.add_argument("--cpu-seqs", type=int, default=None, help="sequences replayed through the CPU oracle on rank 0 (0 = skip; default 0, --full: 8)")
+    ap.add_argument("--cpu-procs", type=int, default=None, help="oracle processes for the all-core CPU baseline, one sequence each "
+                    "(-1 = every core this process may run on, 0 = skip; default 0, --full: -1)")
+    ap.add_argument("--aux", type=int, default=None, help="1: also measure S = 256 and S = 512 sequences per GPU and the lag-0 ordering "
+                    "at S (reported as aux_s256 / aux_s512 / lag0, never as value); 0 = skip (default 0, --full: 1)")
     ap.add_argument("--seq-offset", type=int, default=0, help="global id of rank 0's first sequence (replays another rank's shard on one GPU)")
     ap.add_argument("--dump", default="", help="write the final windows / odometry rows of this rank's sequences to <dump>.rank<r>.npz")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (window.npy [S][W+1][17], "
+                    "odometry.npy [S][11], status.npy [S][fields of vio_status], float64, sequences in global order) to DIR")
     ap.add_argument("--tracker-lag", type=int, default=1, choices=[0, 1], help="vio_set_tracker_lag: 1 = the tracker of frame f+1 overlaps the "
                     "optimisation of frame f (the reference's two threads with the estimator one frame behind), 0 = it waits for it")
-    ap.add_argument("--pcie-steps", type=int, default=20, help="extra steps fed from HOST buffers after the timed region (0 = skip)")
-    ap.add_argument("--stream-steps", type=int, default=10, help="extra steps with the IMU pushed frame by frame")
+    ap.add_argument("--pcie-steps", type=int, default=None, help="extra steps fed from HOST buffers after the timed region (0 = skip; default 0, "
+                    "--full: 20)")
+    ap.add_argument("--stream-steps", type=int, default=None, help="extra steps with the IMU pushed frame by frame (default 0, --full: 10)")
     args = ap.parse_args()
+    for k, plain, full in (("repeats", 1, 10), ("cpu_seqs", 0, 8), ("cpu_procs", 0, -1), ("aux", 0, 1), ("pcie_steps", 0, 20), ("stream_steps", 0, 10)):
+        if getattr(args, k) is None:
+            setattr(args, k, full if args.full else plain)
 
     # ---- N ranks: spawn them ourselves when the caller did not (python bench.py --gpus N), never silently run fewer
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -272,11 +316,10 @@ def main():
     seq0 = args.seq_offset + shard.sequence_shard(rank, world, S)[0]
     syn = P.Synth(sc)
     dev = torch.device("cuda", local_rank)
-    gray = torch.empty((F, S, H, Wd), dtype=torch.uint8, device=dev)
-    depth = torch.empty((F, S, H, Wd), dtype=torch.uint16, device=dev)
+    slots = max(frame_slots(S, cfg, F), Ks)
+    gray = torch.empty((slots, S, H, Wd), dtype=torch.uint8, device=dev)
+    depth = torch.empty((slots, S, H, Wd), dtype=torch.uint16, device=dev)
     times = vio_ct.frame_times(sc, F)
-    for f in range(F):
-        syn.render_device(S, seq0, float(times[f]), gray[f], depth[f])
     nimu = int(F / sc.cam_rate * sc.imu_rate) + 64
     b = P.VioBatch(cfg, S, imu_capacity=nimu + 64)
     b.set_tracker_lag(args.tracker_lag)
@@ -287,34 +330,32 @@ def main():
     b.push_imu_batch(np.stack([x[0][:k_up] for x in imu_all]), np.stack([x[1][:k_up] for x in imu_all]), np.stack([x[2][:k_up] for x in imu_all]))
     imu_k = [k_up] * S
 
-    def feed(f):
-        b.feed(gray[f], depth[f], np.full(S, times[f]), on_device=True)
+    def render(f0, n):
+        """frames f0 .. f0 + n - 1 into slots 0 .. n - 1 (n <= slots; the handle is idle)"""
+        for i in range(n):
+            syn.render_device(S, seq0, float(times[f0 + i]), gray[i], depth[i])
+        torch.cuda.synchronize()
 
-    for f in range(n_pre + Wm):
-        feed(f)
-    b.sync()
+    def host_frame(f):
+        render(f, 1)
+        return gray[0].cpu().numpy(), depth[0].cpu().numpy()
+
+    feed_rendered(b, syn, torch, gray, depth, seq0, times, 0, n_pre + Wm)
     st0 = b.status_all()
     fp0 = np.array([st.frames_processed for st in st0])
     nl = np.array([st.solver_flag for st in st0])
     it0 = np.array([(st.iterations_total, st.solves_total) for st in st0], np.int64)
-    b.profile_begin(R * K)
-    elapsed_rep = []
-    for r in range(R):
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for k in range(K):
-            feed(n_pre + Wm + r * K + k)
-        b.sync()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        if world > 1:
-            dist.barrier()
-        elapsed_rep.append(t1 - t0)
-    nprof, kms = b.profile_end()
+    if args.full:
+        b.profile_begin(R * K)
+    elapsed_rep = [feed_rendered(b, syn, torch, gray, depth, seq0, times, n_pre + Wm + r * K, K, barrier=dist.barrier if world > 1 else None)
+                   for r in range(R)]
+    kms = b.profile_end()[1] if args.full else None
     st1 = b.status_all()
+    outputs = None
+    if args.dump_outputs:
+        # what a caller of vio_feed holds after the last timed step (read before the PCIe / streaming legs move the state on)
+        outputs = dict(window=np.stack([b.window(s) for s in range(S)]), odometry=b.odometry(),
+                       status=np.array([[float(getattr(st, n)) for n, _ in P.Status._fields_] for st in st1]))
     it1 = np.array([(st.iterations_total, st.solves_total) for st in st1], np.int64)
     d_it = (it1 - it0).sum(0)
     iters = float(d_it[0]) / max(float(d_it[1]), 1.0)          # mean solver iterations per solve over ALL timed steps and sequences
@@ -323,8 +364,7 @@ def main():
     # ---- PCIe-inclusive rate (never `value`): the same call handed pageable HOST buffers, S x 0.92 MB uploaded per step
     pcie = None
     if Kp > 0:
-        hg = [gray[f_timed_end + k].cpu().numpy() for k in range(Kp)]
-        hd = [depth[f_timed_end + k].cpu().numpy() for k in range(Kp)]
+        hg, hd = zip(*[host_frame(f_timed_end + k) for k in range(Kp)])
         torch.cuda.synchronize()
         c0 = time.perf_counter()
         for k in range(Kp):
@@ -337,7 +377,7 @@ def main():
         pg = [P.PinnedArray((S, H, Wd), np.uint8) for _ in range(Kp)]
         pd = [P.PinnedArray((S, H, Wd), np.uint16) for _ in range(Kp)]
         for k in range(Kp):
-            pg[k].a[...] = gray[f_timed_end + Kp + k].cpu().numpy(); pd[k].a[...] = depth[f_timed_end + Kp + k].cpu().numpy()
+            pg[k].a[...], pd[k].a[...] = host_frame(f_timed_end + Kp + k)
         # every buffer is DMA-ed once before the timed loop: the FIRST transfer out of a fresh page-locked allocation runs at a third of the
         # link rate (tools/h2d_pattern.py: 17.6 GB/s first use, 56 GB/s afterwards), and a deployment rotates a few long-lived image sets --
         # rounds 3 - 5 timed 20 first uses and reported page-locked uploads as slower than pageable ones for that reason
@@ -363,7 +403,7 @@ def main():
     if Ks > 0:
         legs = {}
         for name, f0 in (("per_sequence_calls", f_stream0), ("batched_call", f_stream0 + Ks)):
-            torch.cuda.synchronize()
+            render(f0, Ks)
             c0 = time.perf_counter()
             for k in range(Ks):
                 f = f0 + k
@@ -381,7 +421,7 @@ def main():
                         tt[s, :q] = imu_all[s][0][imu_k[s]:k2[s]]; aa[s, :q] = imu_all[s][1][imu_k[s]:k2[s]]; gg[s, :q] = imu_all[s][2][imu_k[s]:k2[s]]
                     b.push_imu_batch(tt, aa, gg, n=[k2[s] - imu_k[s] for s in range(S)])
                 imu_k = k2
-                feed(f)
+                b.feed(gray[k], depth[k], np.full(S, times[f]), on_device=True)
             b.sync()
             c1 = time.perf_counter()
             legs[name] = dict(frames_per_s=S * Ks / (c1 - c0), ms_per_step=(c1 - c0) / Ks * 1e3, steps=Ks)
@@ -429,66 +469,67 @@ def main():
     ntrk = float(np.mean([st.n_tracks for st in stats]))
     reboots = int(np.sum([st.reboot_count for st in stats]))
 
-    # ---- rooflines: algorithmic work of ONE kernel per launch (S sequences) / its average launch duration (HIP events on the
-    # handle's own streams, averaged over the R x K timed steps)
-    k_obs = nres / max(ninp, 1.0) + 1.0
-    flops = backend_flops(max(iters, 1.0), nres, nvar, k_obs, cfg.window_size, sc.imu_rate / sc.cam_rate)
-    fbytes = frontend_bytes(Wd, H, cfg.max_cnt, cfg.lk_max_level)
-    be_ms = sum(v for k, v in kms.items() if k.startswith("be_"))
-    fe_ms = sum(v for k, v in kms.items() if k.startswith("fe_"))
-    tj = None
-    for name in ("round6_pmc_traffic.json", "round5_pmc_traffic.json", "round4_pmc_traffic.json", "round3_pmc_traffic.json", "round2_pmc_traffic.json", "round1_pmc_traffic.json"):
-        tpath = os.path.join(ROOT, "profiles", name)
-        if os.path.exists(tpath):  # written by profiles/collect.sh from separate rocprofv3 --pmc passes over this same command
-            tj = (name, json.load(open(tpath)))
-            break
-
-    def traffic_of(kname):
-        if not tj or tj[1].get("sequences_per_gpu") != S or tj[1].get("sequences_per_launch", S) != S_launch:
-            return None
-        kk = "be_solve_phased" if (kname == "be_solve" and os.environ.get("VIO_SOLVE_MODE", "1") != "0") else kname
-        ent = next((v for k, v in tj[1].get("kernels", {}).items() if k.startswith(kk)), None)
-        return ent["hbm_bytes_per_launch"] if ent else None
-
     # the HIP events bracket the launches of stream group 0, which cover S / n_groups sequences each
     per_group = int(os.environ.get("VIO_GROUP_SEQS", S))
     n_groups = max(1, -(-S // max(per_group, 1)))
     S_launch = min(S, per_group)
 
-    def roof_flops(kname, sym, fl, note):
-        ach = fl * S_launch / (kms[kname] * 1e-3) / 1e12
-        return dict(bound="mfma", kernel=sym, achieved=ach, peak=FP64_PEAK_TFLOPS, unit="TFLOP/s", frac=ach / FP64_PEAK_TFLOPS, traffic=traffic_of(kname),
-                    ms=kms[kname], algorithmic_flops_per_launch=fl * S_launch, sequences_per_launch=S_launch, note=note)
+    # ---- rooflines: algorithmic work of ONE kernel per launch (S sequences) / its average launch duration (HIP events on the
+    # handle's own streams, averaged over the R x K timed steps)
+    if args.full:
+        k_obs = nres / max(ninp, 1.0) + 1.0
+        flops = backend_flops(max(iters, 1.0), nres, nvar, k_obs, cfg.window_size, sc.imu_rate / sc.cam_rate)
+        fbytes = frontend_bytes(Wd, H, cfg.max_cnt, cfg.lk_max_level)
+        be_ms = sum(v for k, v in kms.items() if k.startswith("be_"))
+        fe_ms = sum(v for k, v in kms.items() if k.startswith("fe_"))
+        tj = None
+        for name in ("round6_pmc_traffic.json", "round5_pmc_traffic.json", "round4_pmc_traffic.json", "round3_pmc_traffic.json", "round2_pmc_traffic.json", "round1_pmc_traffic.json"):
+            tpath = os.path.join(ROOT, "profiles", name)
+            if os.path.exists(tpath):  # written by profiles/collect.sh from separate rocprofv3 --pmc passes over this same command
+                tj = (name, json.load(open(tpath)))
+                break
 
-    def roof_bytes(kname, sym, by, note):
-        ach = by * S_launch / (kms[kname] * 1e-3) / 1e9
-        tr = traffic_of(kname)
-        return dict(bound="hbm", kernel=sym, achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS, traffic=tr, ms=kms[kname],
-                    algorithmic_bytes_per_launch=by * S_launch, sequences_per_launch=S_launch,
-                    traffic_over_algorithmic=(tr / (by * S_launch) if tr else None), note=note)
+        def traffic_of(kname):
+            if not tj or tj[1].get("sequences_per_gpu") != S or tj[1].get("sequences_per_launch", S) != S_launch:
+                return None
+            kk = "be_solve_phased" if (kname == "be_solve" and os.environ.get("VIO_SOLVE_MODE", "1") != "0") else kname
+            ent = next((v for k, v in tj[1].get("kernels", {}).items() if k.startswith(kk)), None)
+            return ent["hbm_bytes_per_launch"] if ent else None
 
-    phased = os.environ.get("VIO_SOLVE_MODE", "1") != "0"
-    solve_sym = ("ps_* (phased solver: ps_setup, slots of ps_eval / ps_asm_a / ps_asm_b / ps_schur / ps_serial, ps_final)" if phased else
-                 ("be_solve_kernel_512" if int(os.environ.get("VIO_BE_THREADS", "512")) <= 512 else "be_solve_kernel"))
-    rk = {
-        "be_solve": roof_flops("be_solve", solve_sym, flops["solve"],
-                               "FP64; solve-only algorithmic flops per launch = S x I x per-iteration flops (SURVEY.md 8d, measured I = mean "
-                               "iterations over all timed solves, O residuals, F variable landmarks) / average launch duration"),
-        "be_marg": roof_flops("be_marg", "be_marg_kernel", flops["marg"],
-                              "FP64; marginalisation flops of SURVEY.md 8d without the 10 n_p^3 eigen-decomposition the hot path does not perform"),
-        "be_ingest": roof_flops("be_ingest", "be_ingest_kernel", flops["ingest"], "FP64 vector; pre-integration flops (SURVEY.md 8d)"),
-        "fe_lk": roof_bytes("fe_lk", "fe_lk_kernel", fbytes["lk"], "algorithmic patch bytes: N x (L + 1) x 2 x 23^2 (SURVEY.md 8d)"),
-        "fe_pyrdown": roof_bytes("fe_pyrdown", "fe_pyrdown_kernel", fbytes["pyrdown"], "read the new frame + write the pyramid levels"),
-        "fe_fast": roof_bytes("fe_fast", "fe_fast_kernel", fbytes["fast"], "read the new frame once"),
-    }
-    dom = max(kms, key=lambda k: kms[k])
-    roof = dict(rk[dom]) if dom in rk else dict(rk["be_solve"])
-    if tj and roof.get("traffic") is not None:
-        roof["traffic_source"] = "profiles/%s (2 x FETCH_SIZE + WRITE_SIZE, gfx950 correction)" % tj[0]
-    roof["frontend_GBps"] = sum(fbytes.values()) * S_launch / (fe_ms * 1e-3) / 1e9 if fe_ms > 0 else None
-    roof["backend_TFLOPs"] = (flops["solve"] + flops["marg"] + flops["ingest"]) * S_launch / (be_ms * 1e-3) / 1e12 if be_ms > 0 else None
-    roof["stream_groups"] = n_groups
-    roofline_kernels = [rk[k] for k in sorted(rk, key=lambda k: -kms[k]) if k != dom]
+        def roof_flops(kname, sym, fl, note):
+            ach = fl * S_launch / (kms[kname] * 1e-3) / 1e12
+            return dict(bound="mfma", kernel=sym, achieved=ach, peak=FP64_PEAK_TFLOPS, unit="TFLOP/s", frac=ach / FP64_PEAK_TFLOPS, traffic=traffic_of(kname),
+                        ms=kms[kname], algorithmic_flops_per_launch=fl * S_launch, sequences_per_launch=S_launch, note=note)
+
+        def roof_bytes(kname, sym, by, note):
+            ach = by * S_launch / (kms[kname] * 1e-3) / 1e9
+            tr = traffic_of(kname)
+            return dict(bound="hbm", kernel=sym, achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS, traffic=tr, ms=kms[kname],
+                        algorithmic_bytes_per_launch=by * S_launch, sequences_per_launch=S_launch,
+                        traffic_over_algorithmic=(tr / (by * S_launch) if tr else None), note=note)
+
+        phased = os.environ.get("VIO_SOLVE_MODE", "1") != "0"
+        solve_sym = ("ps_* (phased solver: ps_setup, slots of ps_eval / ps_asm_a / ps_asm_b / ps_schur / ps_serial, ps_final)" if phased else
+                     ("be_solve_kernel_512" if int(os.environ.get("VIO_BE_THREADS", "512")) <= 512 else "be_solve_kernel"))
+        rk = {
+            "be_solve": roof_flops("be_solve", solve_sym, flops["solve"],
+                                   "FP64; solve-only algorithmic flops per launch = S x I x per-iteration flops (SURVEY.md 8d, measured I = mean "
+                                   "iterations over all timed solves, O residuals, F variable landmarks) / average launch duration"),
+            "be_marg": roof_flops("be_marg", "be_marg_kernel", flops["marg"],
+                                  "FP64; marginalisation flops of SURVEY.md 8d without the 10 n_p^3 eigen-decomposition the hot path does not perform"),
+            "be_ingest": roof_flops("be_ingest", "be_ingest_kernel", flops["ingest"], "FP64 vector; pre-integration flops (SURVEY.md 8d)"),
+            "fe_lk": roof_bytes("fe_lk", "fe_lk_kernel", fbytes["lk"], "algorithmic patch bytes: N x (L + 1) x 2 x 23^2 (SURVEY.md 8d)"),
+            "fe_pyrdown": roof_bytes("fe_pyrdown", "fe_pyrdown_kernel", fbytes["pyrdown"], "read the new frame + write the pyramid levels"),
+            "fe_fast": roof_bytes("fe_fast", "fe_fast_kernel", fbytes["fast"], "read the new frame once"),
+        }
+        dom = max(kms, key=lambda k: kms[k])
+        roof = dict(rk[dom]) if dom in rk else dict(rk["be_solve"])
+        if tj and roof.get("traffic") is not None:
+            roof["traffic_source"] = "profiles/%s (2 x FETCH_SIZE + WRITE_SIZE, gfx950 correction)" % tj[0]
+        roof["frontend_GBps"] = sum(fbytes.values()) * S_launch / (fe_ms * 1e-3) / 1e9 if fe_ms > 0 else None
+        roof["backend_TFLOPs"] = (flops["solve"] + flops["marg"] + flops["ingest"]) * S_launch / (be_ms * 1e-3) / 1e12 if be_ms > 0 else None
+        roof["stream_groups"] = n_groups
+        roofline_kernels = [rk[k] for k in sorted(rk, key=lambda k: -kms[k]) if k != dom]
 
     # ---- CPU baseline: the oracle (port of the reference algorithm) on the same workload, rank 0 at N = 1 only
     cpu1 = None
@@ -497,6 +538,11 @@ def main():
         ncs = min(args.cpu_seqs, S)
         Fc = min(F, n_pre + Wm + 44)      # bounded sample: ~44 steady-state frames per sequence
         tcpu, nfr, rm, ate_pairs = 0.0, 0, [], []
+        hgray, hdepth = np.empty((Fc, ncs, H, Wd), np.uint8), np.empty((Fc, ncs, H, Wd), np.uint16)
+        for c in range(0, Fc, slots):
+            m = min(slots, Fc - c)
+            render(c, m)
+            hgray[c:c + m], hdepth[c:c + m] = gray[:m, :ncs].cpu().numpy(), depth[:m, :ncs].cpu().numpy()
         for s in range(ncs):
             o = vio_ct.OraclePipeline(cfg)
             o.set_tracker_lag(args.tracker_lag)
@@ -504,8 +550,7 @@ def main():
             o.push_imu(ti, ai, gi)
             traj = []
             for f in range(Fc):
-                g = gray[f, s].cpu().numpy()
-                d = depth[f, s].cpu().numpy()
+                g, d = hgray[f, s], hdepth[f, s]
                 steady = o.status()["solver_flag"] == 1
                 c0 = time.perf_counter()
                 r = o.feed(g, d, float(times[f]))
@@ -584,15 +629,16 @@ def main():
     def r3(x):
         return None if x is None else float("%.4g" % x)
 
-    roof_c = {k: roof.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}
-    roof_c = {k: (r3(v) if isinstance(v, float) else v) for k, v in roof_c.items()}
-    roof_c["kernel"] = "ps_* (phased dogleg solver, %d sequences per launch chain)" % S_launch if dom == "be_solve" and phased else roof.get("kernel")
-    roof_c["ms"] = r3(roof.get("ms"))
-    # device-wide fraction next to the per-launch-chain one: the algorithmic FP64 flops of ALL stream groups' back-end
-    # work of one step (solve + marginalisation + pre-integration, S sequences) over the step time the driver sees, against the same peak
-    dev_tflops = (flops["solve"] + flops["marg"] + flops["ingest"]) * S / (elapsed / K) / 1e12
-    roof_c["device_wide"] = {"achieved": r3(dev_tflops), "frac": r3(dev_tflops / FP64_PEAK_TFLOPS),
-                             "note": "all %d stream groups: S x back-end flops per frame / ms_per_step" % n_groups}
+    if args.full:
+        roof_c = {k: roof.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}
+        roof_c = {k: (r3(v) if isinstance(v, float) else v) for k, v in roof_c.items()}
+        roof_c["kernel"] = "ps_* (phased dogleg solver, %d sequences per launch chain)" % S_launch if dom == "be_solve" and phased else roof.get("kernel")
+        roof_c["ms"] = r3(roof.get("ms"))
+        # device-wide fraction next to the per-launch-chain one: the algorithmic FP64 flops of ALL stream groups' back-end
+        # work of one step (solve + marginalisation + pre-integration, S sequences) over the step time the driver sees, against the same peak
+        dev_tflops = (flops["solve"] + flops["marg"] + flops["ingest"]) * S / (elapsed / K) / 1e12
+        roof_c["device_wide"] = {"achieved": r3(dev_tflops), "frac": r3(dev_tflops / FP64_PEAK_TFLOPS),
+                                 "note": "all %d stream groups: S x back-end flops per frame / ms_per_step" % n_groups}
     cpu_c = None
     if cpu:
         cpu_c = {k: cpu.get(k) for k in ("value", "unit", "cores", "cores_are", "hardware_threads_visible", "physical_cores", "kind", "one_worker_alone") if k in cpu}
@@ -624,8 +670,7 @@ def main():
         "repeats": {"n": R, "frames_per_s": [round(x) for x in rates], "timed_frames_per_sequence": R * K},
         "ate_m": {"mean": r3(float(np.mean(ates))) if ates else None, "job_rms": r3(shard.ate_from_sums(sq_err_all, n_ate_all))},
         "solver": {"mean_iterations": r3(iters), "timed_solves": int(d_it[1]), "reboots": reboots},
-        "frontend_ms": r3(fe_ms), "backend_ms": r3(be_ms),
-        "roofline": roof_c,
+        **({"frontend_ms": r3(fe_ms), "backend_ms": r3(be_ms), "roofline": roof_c} if args.full else {}),
         "cpu_baseline": cpu_c,
     }
     if parity:
@@ -654,11 +699,7 @@ def main():
                   "job_rms": shard.ate_from_sums(sq_err_all, n_ate_all)},
         "solver": {"mean_iterations": iters, "timed_solves": int(d_it[1]), "mean_residuals": nres, "mean_var_landmarks": nvar, "mean_tracks": ntrk,
                    "reboots": reboots},
-        "kernels_ms": kms,
-        "frontend_ms": fe_ms,
-        "backend_ms": be_ms,
-        "roofline": roof,
-        "roofline_kernels": roofline_kernels,
+        **({"kernels_ms": kms, "frontend_ms": fe_ms, "backend_ms": be_ms, "roofline": roof, "roofline_kernels": roofline_kernels} if args.full else {}),
         "cpu_baseline": cpu,
         "parity": parity,
         "pcie_inclusive": pcie,
@@ -667,6 +708,13 @@ def main():
     if args.dump:
         np.savez(args.dump + ".rank%d.npz" % rank, seq0=seq0, windows=np.stack([b.window(s) for s in range(S)]),
                  odometry=np.stack([hist[s][-min(len(hist[x]) for x in range(S)):] for s in range(S)]))
+    if args.dump_outputs:
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, outputs)
+            outputs = {k: np.concatenate([x[k] for x in parts]) for k in outputs}
+        if rank == 0:
+            write_outputs(args.dump_outputs, outputs)
     b.close()
     del gray, depth
     torch.cuda.empty_cache()
@@ -709,7 +757,7 @@ def main():
         cfg_x = P.canonical_config(marg_exact=1)
         detail["marg_exact"] = aux_rate(P, vio_ct, torch, cfg_x, sc, dev, S, n_pre, Wm, K, lag=args.tracker_lag, seq0=seq0)
         detail["marg_exact"]["note"] = "marg_exact = 1; be_marg per launch %.3f ms against %.3f ms of the default form" % (
-            detail["marg_exact"]["kernels_ms"].get("be_marg", float("nan")), kms.get("be_marg", float("nan")))
+            detail["marg_exact"]["kernels_ms"].get("be_marg", float("nan")), (kms or {}).get("be_marg", float("nan")))
         # marg_exact = 2: the same algorithm with the first eigen-decomposition replaced by a certified inverse (include/vio_abi.h)
         cfg_c = P.canonical_config(marg_exact=2)
         detail["marg_certified"] = aux_rate(P, vio_ct, torch, cfg_c, sc, dev, S, n_pre, Wm, K, lag=args.tracker_lag, seq0=seq0)
@@ -717,7 +765,7 @@ def main():
         aux_keys = ("lag0", "aux_s256", "aux_s512", "fused_s%d" % S, "fused_s256", "fused_s512", "config5", "marg_exact", "marg_certified")
         line["aux_frames_per_s"] = {k: round(detail[k]["frames_per_s"]) for k in aux_keys}
         line["aux_valid"] = all(detail[k]["valid"] for k in aux_keys)
-    if rank == 0:
+    if rank == 0 and args.full:
         # detail: everything the compact line summarises (per-kernel rooflines, ATE lists, PCIe / streaming legs, aux legs with their kernel
         # times), to a side file and to stderr; the LAST line of stdout is the one JSON line of the contract
         full = dict(line)
@@ -730,6 +778,7 @@ def main():
         except OSError:
             pass
         print(json.dumps(full), file=sys.stderr)
+    if rank == 0:
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()

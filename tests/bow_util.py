@@ -67,6 +67,13 @@ def view_of(place, seed, keep=0.8, noise_bits=12, extra=60):
     return np.ascontiguousarray(out[rng.permutation(len(out))])
 
 
+def ref_bowvector_inputs(weighting):
+    """the vocabulary and the four keyframe views whose (word, weight) sequences tests/golden/ref_bowvector.npz holds the reference
+    DBoW2::BowVector of (test_oracle_bow_cpu.py::test_bow_vector_against_the_reference_class_itself and the fixture's generator)"""
+    voc = make_vocabulary(7, 3, 40 + weighting, irregular=True, weighting=weighting, stop_fraction=0.1)
+    return voc, [view_of(place_descriptors(voc, seed, 700), 50 + seed, noise_bits=30, extra=200) for seed in range(4)]
+
+
 def bind_oracle():
     L = vio_ct.oracle()
     if not getattr(L, "_bow_bound", False):

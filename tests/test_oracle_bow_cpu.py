@@ -1,6 +1,7 @@
 """The oracle's restatement of the DBoW2 slice PoseGraph::detectLoop uses (oracle/bow.cpp) against independent Python restatements and
 hand-computed cases.  No GPU, no vocabulary blob (missing upstream): synthetic vocabularies in the reference's file format."""
 import importlib
+import os
 
 import numpy as np
 import pytest
@@ -113,21 +114,24 @@ def _ref_bowvector():
 
 @pytest.mark.parametrize("weighting", [0, 1, 2, 3])
 def test_bow_vector_against_the_reference_class_itself(weighting):
-    """The one piece of reference arithmetic that compiles in this image from its own source: DBoW2::BowVector (ThirdParty/DBoW/BowVector.cpp).
+    """The one piece of reference arithmetic that compiles from its own source: DBoW2::BowVector (ThirdParty/DBoW/BowVector.cpp).
     The restatement's bag-of-words vector -- accumulation per feature for TF-IDF / TF, first occurrence for IDF / BINARY, stopped words,
-    L1 normalisation -- must equal, bit for bit, what the reference's class makes of the same (word, weight) sequence."""
+    L1 normalisation -- must equal, bit for bit, what the reference's class makes of the same (word, weight) sequence: the class's outputs
+    are stored in tests/golden/ref_bowvector.npz (generator next to it), and where oracle/_ref is built the class is called here as well."""
     R = _ref_bowvector()
-    if R is None:
-        pytest.skip("reference tree not present and oracle/_ref not prebuilt")
-    voc = bow_util.make_vocabulary(7, 3, 40 + weighting, irregular=True, weighting=weighting, stop_fraction=0.1)
+    gold = np.load(os.path.join(vio_ct.ROOT, "tests", "golden", "ref_bowvector.npz"))
+    voc, views = bow_util.ref_bowvector_inputs(weighting)
     o = bow_util.OracleVoc(voc)
-    for seed in range(4):
-        feats = bow_util.view_of(bow_util.place_descriptors(voc, seed, 700), 50 + seed, noise_bits=30, extra=200)
+    for seed, feats in enumerate(views):
+        key = "w%d_s%d_" % (weighting, seed)
         w, wt = o.transform(feats)
-        ids, val = np.zeros(len(w), np.int32), np.zeros(len(w))
         w32 = np.ascontiguousarray(w, np.int32)
-        m = R.oref_bow_vector(len(w), w32.ctypes.data, wt.ctypes.data, weighting, len(w), ids.ctypes.data, val.ctypes.data)
+        assert np.array_equal(w32, gold[key + "word"]) and np.array_equal(wt, gold[key + "weight"])   # the sequence the fixture was made of
         bw, bv = o.bow(feats)
-        assert m == len(bw) > 20 and np.array_equal(ids[:m], bw) and np.array_equal(val[:m], bv)
+        assert len(bw) > 20 and np.array_equal(gold[key + "id"], bw) and np.array_equal(gold[key + "value"], bv)
+        if R is not None:
+            ids, val = np.zeros(len(w), np.int32), np.zeros(len(w))
+            m = R.oref_bow_vector(len(w), w32.ctypes.data, wt.ctypes.data, weighting, len(w), ids.ctypes.data, val.ctypes.data)
+            assert m == len(bw) and np.array_equal(ids[:m], bw) and np.array_equal(val[:m], bv)
         assert (np.bincount(w32).max() > 1)          # repeated words: the accumulation order matters
     o.close()

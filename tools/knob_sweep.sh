@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs ON THE GPU BOX: short bench runs under different runtime knobs; one JSON line each into gpurun_out/sweep_<tag>.json
 set -u
-ARGS="--steps ${STEPS:-20} --warmup 6 --repeats 3 --cpu-seqs 0 --cpu-procs 0 --pcie-steps 0 --stream-steps 0 --aux 0"
+ARGS="--full --steps ${STEPS:-20} --warmup 6 --repeats 3 --cpu-seqs 0 --cpu-procs 0 --pcie-steps 0 --stream-steps 0 --aux 0"
 run() { tag=$1; shift; env "$@" timeout 300 python bench.py $ARGS > gpurun_out/sweep_$tag.json 2> gpurun_out/sweep_$tag.err; python - "$tag" <<'P'
 import json, sys
 try:

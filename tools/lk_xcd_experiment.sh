@@ -6,7 +6,7 @@ R=$(pwd)
 for cfgname in ${CONFIGS:-nopart nopart_xcd}; do
   case $cfgname in part64) E="VIO_FE_CUS=64";; nopart) E="VIO_FE_CUS=0";; nopart_xcd) E="VIO_FE_CUS=0 VIO_FE_XCD_MAP=1";; part64_xcd) E="VIO_FE_CUS=64 VIO_FE_XCD_MAP=1";; esac
   echo "== $cfgname"
-  env $E timeout 200 python bench.py --steps 20 --warmup 5 --aux 0 --cpu-seqs 0 --cpu-procs 0 --pcie-steps 0 --stream-steps 0 --repeats 5 2>/dev/null | python -c "
+  env $E timeout 200 python bench.py --full --steps 20 --warmup 5 --aux 0 --cpu-seqs 0 --cpu-procs 0 --pcie-steps 0 --stream-steps 0 --repeats 5 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value']), d['frontend_ms'], d['backend_ms'])"
   B="python $R/bench.py --steps 10 --warmup 4 --repeats 1 --cpu-seqs 0 --cpu-procs 0 --pcie-steps 0 --stream-steps 0 --aux 0"

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs ON THE GPU BOX: short bench runs under runtime knobs, one line each.  bash tools/r4_sweep.sh [set]
-run() { tag=$1; shift; env "$@" python bench.py --steps 20 --warmup 5 --aux 0 --cpu-seqs 0 --cpu-procs 0 --pcie-steps 0 --stream-steps 0 --repeats 6 2>/dev/null | python -c "
+run() { tag=$1; shift; env "$@" python bench.py --full --steps 20 --warmup 5 --aux 0 --cpu-seqs 0 --cpu-procs 0 --pcie-steps 0 --stream-steps 0 --repeats 6 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$tag', round(d['value']), [round(x) for x in d['repeats']['frames_per_s']], 'fe', d['frontend_ms'], 'be', d['backend_ms'])"; }
