@@ -46,7 +46,10 @@ typedef struct vio_config {
     int32_t window_size;            /* WINDOW_SIZE (compile-time 10 upstream, parameters.h:12); 4..20 here */
     int32_t max_landmarks;          /* NUM_OF_F (parameters.h:14): capacity of the landmark table */
     int32_t fix_depth;              /* FIX_DEPTH */
-    int32_t estimate_extrinsic;     /* ESTIMATE_EXTRINSIC: 0 or 1 (2 = calibrate from scratch is out of scope) */
+    int32_t estimate_extrinsic;     /* ESTIMATE_EXTRINSIC: 0 fixed, 1 refined by the solver, 2 = no extrinsic: ric / tic are ignored (ric = I,
+                                       tic = 0, parameters.cpp:181-190) and the rotation is calibrated online per sequence (InitialEXRotation,
+                                       estimator.cpp:208-226; both initialisations wait for it), then refined as in mode 1: see
+                                       vio_get_ex_calibration.  Mode 2 needs use_imu = 1. */
     int32_t estimate_td;            /* ESTIMATE_TD */
     int32_t max_iterations;         /* NUM_ITERATIONS  max_num_iterations */
     int32_t ransac_max_iters;       /* cv::findFundamentalMat RANSAC iteration cap (1000) */
@@ -198,7 +201,8 @@ void vio_host_free(void *p);
 /* sizeof(vio_config) (what = 0) / sizeof(vio_status) (what = 1) as compiled into the library: lets a binding check its struct mirrors */
 int vio_abi_sizeof(int what);
 /* Contract version of this header: 4 = a vio_feed host image set is free when the next vio_feed has returned; 5 = two uploads in flight (see
- * "Host buffers" above, vio_host_buffers_done); 6 = + vio_get_bound_stats, the inverse-depth bound handled as Ceres does (projected line search). */
+ * "Host buffers" above, vio_host_buffers_done); 6 = + vio_get_bound_stats, the inverse-depth bound handled as Ceres does (projected line search);
+ * 7 = + estimate_extrinsic = 2 (vio_get_ex_calibration, vio_stage_relative_r). */
 int vio_abi_version(void);
 /* capacities derived from the configuration: out[0] = tracker points per sequence, out[1] = landmark slots, out[2] = IMU ring */
 int vio_get_capacity(vio_batch *h, int32_t *out3);
@@ -214,6 +218,18 @@ int vio_get_bound_stats(vio_batch *h, int seq, int64_t *out4);
  * keeps the block inverse without the proof that the reference's 1e-8 eigenvalue cut of marginalization_factor.cpp:281-291 drops nothing),
  * 1 if the last marginalisation was certified}.  Synchronises the device. */
 int vio_get_marg_certificate(vio_batch *h, int seq, int32_t *out2);
+/* estimate_extrinsic = 2: InitialEXRotation of sequence seq (initial_ex_rotation.cpp:12-68).  Every processed frame with frame_count != 0 of a
+ * calibrating sequence appends one pair (Rc = solveRelativeR of the correspondences of window frames frame_count - 1 and frame_count, Rimu = the
+ * delta_q of that frame's pre-integration, Rc_g = ric^-1 Rimu ric with the estimate of ric at that time) and re-solves the Huber-weighted
+ * averaging; success (calls >= window_size and the third singular value > 0.25) sets the sequence's ric, after which the initialisation runs and
+ * the solver refines ric / tic as in mode 1.  out16 = {state: 2 calibrating, 1 calibrated, 0 the handle is not in mode 2; stored pairs;
+ * frames_processed (vio_status) after the frame that succeeded, -1 while calibrating; the current estimate of ric (9, row-major); the four
+ * singular values of the last averaging step, descending}.  history (may be NULL when cap = 0) receives the oldest min(cap, pairs) stored pairs
+ * as 12 doubles each: q(Rc), q(Rimu), q(Rc_g) (w x y z, Eigen's matrix -> quaternion rule).  At most 2048 pairs are kept per sequence (the
+ * reference's list is unbounded): beyond that the oldest is dropped and the frame raises overflow flag 128.  vio_reset starts the calibration
+ * over; vio_reset_seq and a failure-detection reboot keep a calibrated rotation (with tic = 0), as setParameter() restores RIC[0] upstream.
+ * Returns the number of stored pairs (0 for a handle not in mode 2).  Synchronises the device. */
+int vio_get_ex_calibration(vio_batch *h, int seq, double *out16, int cap, double *history);
 
 /* Results read out of the path (SURVEY.md §8b "Results read out").  All getters synchronise first. */
 typedef struct vio_status {
@@ -231,8 +247,9 @@ typedef struct vio_status {
     double initial_cost, final_cost, td;
     int32_t overflow_flags;       /* capacity flags of the last frame: 1 landmark table, 2 IMU slot (> 64 samples per frame interval),
                                      4 FAST candidates of a cell, 8 residual list, 16 IMU ring overwritten, 32 solver iteration slots
-                                     exhausted before the trust-region loop finished, 64 relocalisation request dropped (vio_set_relo_frame)
-                                     (code = VIO_ECAPACITY) */
+                                     exhausted before the trust-region loop finished, 64 relocalisation request dropped (vio_set_relo_frame),
+                                     128 extrinsic-calibration history full: its oldest pair was dropped (estimate_extrinsic = 2, see
+                                     vio_get_ex_calibration) (code = VIO_ECAPACITY) */
     int32_t overflow_frames;      /* frames that raised any capacity flag since the last reset / reboot */
     int32_t iterations_total, solves_total; /* solver iterations / solves since vio_create */
 } vio_status;
@@ -323,6 +340,9 @@ int vio_stage_lk(const uint8_t *prev, const uint8_t *next, int w, int h, int max
                  float *next_pts_inout, uint8_t *status);
 /* cv::findFundamentalMat(FM_RANSAC, F_THRESHOLD, 0.99) on virtual-pinhole points (feature_tracker.cpp:462) */
 int vio_stage_ransac(const vio_config *cfg, int n, const float *p1, const float *p2, uint8_t *status);
+/* InitialEXRotation::solveRelativeR (initial_ex_rotation.cpp:70-147) through the device code of the calibration phase: corres6[n][6] =
+ * (x, y, z) of frame l, (x, y, z) of frame r (normalised points, z = 1); R9 = the rotation it returns, row-major (identity for n < 9) */
+int vio_stage_relative_r(int n, const double *corres6, double *R9);
 /* IntegrationBase::push_back x n + IMUFactor::Evaluate (integration_base.h:32-162, imu_factor.h:20-205)
  * out: delta_p(3) delta_q(wxyz) delta_v(3) sum_dt jacobian(225) covariance(225); r(15); J = 15x7,15x9,15x7,15x9 */
 int vio_stage_imu_factor(const vio_config *cfg, int n, const double *dt, const double *acc, const double *gyr,

@@ -111,6 +111,7 @@ class Estimator {
         h_ = vio_create(&cfg_, 1, imu_capacity);
         if (!h_) throw std::runtime_error(std::string("vio_create: ") + vio_last_error());
         WINDOW_SIZE = cfg_.window_size;
+        ESTIMATE_EXTRINSIC = cfg_.estimate_extrinsic;
         clearMirror();
     }
     ~Estimator() { vio_destroy(h_); }
@@ -195,6 +196,8 @@ class Estimator {
     double Ps[MAX_WINDOW + 1][3], Rs[MAX_WINDOW + 1][9] /* row-major */, Vs[MAX_WINDOW + 1][3], Bas[MAX_WINDOW + 1][3], Bgs[MAX_WINDOW + 1][3];
     double Headers[MAX_WINDOW + 1];
     double tic[3], ric[9], td;
+    // the global ESTIMATE_EXTRINSIC (parameters.h): 2 until the online calibration of the rotation succeeds, then 1 (estimator.cpp:219-224)
+    int ESTIMATE_EXTRINSIC;
     vio_status last_status() const { return status_; }
 
     // f_manager.feature (feature_manager.h:63-99) as rows of 12: {feature_id, start_frame, n_obs, estimated_depth, estimate_flag,
@@ -240,6 +243,17 @@ class Estimator {
         for (int i = 0; i <= MAX_WINDOW; i++) Rs[i][0] = Rs[i][4] = Rs[i][8] = 1.0;
         std::memcpy(tic, cfg_.tic, sizeof(tic)); std::memcpy(ric, cfg_.ric, sizeof(ric));
         depth_ = nullptr;
+        refreshExtrinsic();
+    }
+    void refreshExtrinsic() {
+        double ex[13];
+        check(vio_get_extrinsic(h_, 0, ex), "vio_get_extrinsic");
+        std::memcpy(tic, ex, sizeof(tic)); std::memcpy(ric, ex + 3, sizeof(ric)); td = ex[12];
+        if (cfg_.estimate_extrinsic == 2) {
+            double cal[16];
+            check(vio_get_ex_calibration(h_, 0, cal, 0, nullptr), "vio_get_ex_calibration");
+            ESTIMATE_EXTRINSIC = cal[0] == 1 ? 1 : 2;
+        }
     }
     void refresh() {
         check(vio_get_status(h_, 0, &status_), "vio_get_status");
@@ -258,9 +272,7 @@ class Estimator {
             R[6] = 2 * (qx * qz - qy * qw);     R[7] = 2 * (qy * qz + qx * qw);     R[8] = 1 - 2 * (qx * qx + qy * qy);
             Headers[i] = r[16];
         }
-        double ex[13];
-        check(vio_get_extrinsic(h_, 0, ex), "vio_get_extrinsic");
-        std::memcpy(tic, ex, sizeof(tic)); std::memcpy(ric, ex + 3, sizeof(ric)); td = ex[12];
+        refreshExtrinsic();
     }
     vio_config cfg_;
     vio_batch *h_;

@@ -1,0 +1,46 @@
+"""estimate_extrinsic = 2 without a GPU: the numpy restatement of InitialEXRotation (tests/excalib_ref.py) on the test-side generator, and
+the configuration path (dataio)."""
+import numpy as np
+import pytest
+
+import excalib_ref as X
+from test_dataio_cpu import YAML
+
+
+@pytest.fixture(scope="module")
+def io():
+    import importlib
+    return importlib.import_module("vins-rgbd-fast_amd.dataio")
+
+
+def test_restatement_recovers_ric_true(P):
+    """noise-free pairs of the three-axis trajectory: the averaging succeeds after 20 calls (window 10) and recovers ric_true to round-off;
+    tests/test_gpu_ex_calib.py holds the device to the same call count"""
+    cfg = P.canonical_config(estimate_extrinsic=2)
+    k, ric = X.predict_success(X.Scene(cfg, phase=0.0))
+    assert k == 20, k
+    assert X.rot_angle_deg(ric, X.RIC_TRUE) < 1e-3
+
+
+def test_restatement_relative_r_matches_truth():
+    """solveRelativeR on generated correspondences with a known motion: the returned matrix is the rotation of frame r in frame l"""
+    rs = np.random.RandomState(3)
+    R = X.rodrigues([0.1, -0.2, 0.05])
+    t = np.array([0.3, 0.05, -0.1])
+    Xl = np.stack([rs.uniform(-2, 2, 60), rs.uniform(-2, 2, 60), rs.uniform(3, 8, 60)], 1)
+    Xr = (Xl - t) @ R       # X_r = R^T (X_l - t): frame r sits at t, rotated by R, in frame l
+    co = np.hstack([Xl / Xl[:, 2:], Xr / Xr[:, 2:]])
+    assert X.rot_angle_deg(X.solve_relative_r(co), R) < 1e-3
+    assert np.array_equal(X.solve_relative_r(co[:8]), np.eye(3))
+
+
+def test_config_mode2_is_accepted_leniently(P, io):
+    """estimate_extrinsic: 2 with strict=False: a mode-2 configuration with ric = I and tic = 0 (parameters.cpp:181-190), one note"""
+    txt = "\n".join(l for l in YAML.splitlines() if not l.startswith("estimate_extrinsic:")) + "\nestimate_extrinsic: 2\n"
+    with pytest.raises(ValueError, match="strict=False"):
+        io.config_from_yaml(txt, P)
+    cfg, extra = io.config_from_yaml(txt, P, strict=False)
+    assert cfg.estimate_extrinsic == 2
+    assert np.array_equal(np.array(cfg.ric[:]), np.eye(3).ravel())
+    assert np.array_equal(np.array(cfg.tic[:]), np.zeros(3))
+    assert len(extra["notes"]) == 1

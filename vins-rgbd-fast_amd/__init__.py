@@ -140,6 +140,8 @@ def lib():
         L.vio_stage_fast_roi.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
         L.vio_stage_lk.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vio_stage_ransac.argtypes = [C.POINTER(Config), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vio_stage_relative_r.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        L.vio_get_ex_calibration.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.vio_stage_imu_factor.argtypes = [C.POINTER(Config), C.c_int] + [C.c_void_p] * 14
         L.vio_stage_projection.argtypes = [C.POINTER(Config)] + [C.c_void_p] * 3 + [C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                                                   C.c_int, C.c_void_p, C.c_void_p]
@@ -407,6 +409,19 @@ class VioBatch:
         self.L.vio_get_bound_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._chk(self.L.vio_get_bound_stats(self.h, int(seq), o.ctypes.data), "vio_get_bound_stats")
         return tuple(int(x) for x in o)
+
+    def ex_calibration(self, seq=0, history=False):
+        """estimate_extrinsic = 2 (InitialEXRotation): dict(state = 2 calibrating / 1 calibrated / 0 not a mode-2 handle, pairs, success_frame
+        (frames_processed after the frame that succeeded, -1 while calibrating), ric (3 x 3, current estimate), sv (4 singular values of the last
+        averaging step)); with history=True also history = [pairs][3][4]: q(Rc), q(Rimu), q(Rc_g) (w x y z) of every stored pair, oldest first."""
+        o = np.zeros(16, np.float64)
+        hist = np.zeros((2048 if history else 0, 12), np.float64)
+        n = self._chk(self.L.vio_get_ex_calibration(self.h, int(seq), o.ctypes.data, hist.shape[0], hist.ctypes.data if history else None),
+                      "vio_get_ex_calibration")
+        out = dict(state=int(o[0]), pairs=int(o[1]), success_frame=int(o[2]), ric=o[3:12].reshape(3, 3).copy(), sv=o[12:16].copy())
+        if history:
+            out["history"] = hist[:min(n, hist.shape[0])].reshape(-1, 3, 4).copy()
+        return out
 
     def marg_certificate(self, seq=0):
         """marg_exact = 2: (marginalisations whose certificate failed since creation, last one certified?)"""

@@ -90,6 +90,7 @@ __device__ __forceinline__ bool in_problem(const Ctx &c, int slot) {
 
 }  // namespace
 #include "be_linalg.h"
+#include "be_excalib.h"
 namespace {
 
 
@@ -568,6 +569,9 @@ __device__ void repropagate_window(Ctx &c, PreWork &pw) {
 // ====================================================================================================== be_ingest
 // src.ids == NULL: the feature map packaged by the last vio_track / front-end of vio_feed (B.obs_id / B.obs / FeSeq);
 // otherwise a caller-supplied map (vio_process_obs = Estimator::processImage(image, header), estimator.h:46): n_obs[s] < 0 skips s.
+// EXCALIB (estimate_extrinsic = 2 handles only): the extrinsic-rotation calibration phase (be_excalib.h) runs after the pre-integration; the
+// dynamic LDS then also holds the correspondences (4 NP doubles, see vio_abi.hip ingest_lds_bytes).
+template <bool EXCALIB>
 __global__ __launch_bounds__(256) void be_ingest_kernel(Batch B, const uint16_t *depth_base, size_t depth_stride, IngestSrc src) {
     const int s = blockIdx.x + B.s0, t = threadIdx.x, nt = blockDim.x;
     Ctx c = make_ctx(B, s);
@@ -887,6 +891,13 @@ __global__ __launch_bounds__(256) void be_ingest_kernel(Batch B, const uint16_t 
         __syncthreads();
     }
     PH(109);
+    if constexpr (EXCALIB) {
+        // ---- InitialEXRotation::CalibrationExRotation (estimator.cpp:208-226): before triangulateWithDepth, which already uses a rotation
+        // calibrated in this frame
+        __shared__ ExShared exs;
+        if (be.ex_pending && fc != 0)
+            ex_calibrate(B, c, s, fc, nlm, (double *)(((uintptr_t)htab + 15) & ~(uintptr_t)15), scratch, sred, exs);
+    }
     // ---- triangulateWithDepth (feature_manager.cpp:386-543); the dynamic initialisation triangulates after its SfM instead (estimator.cpp:921-933)
     if (!cfg.use_imu && be.solver_flag == 1) init_frame_pose_by_pnp(c, fc, c.res, sred);   // estimator.cpp:321-322 (VO mode, NON_LINEAR only)
     if (!(cfg.dynamic_init && be.solver_flag == 0)) triangulate_with_depth(c, nlm);
@@ -899,8 +910,12 @@ __global__ __launch_bounds__(256) void be_ingest_kernel(Batch B, const uint16_t 
             // static initialisation solves once the window is full; the dynamic one is decided by the host (vio_abi.hip run_dynamic_init)
             if (fc == W && !cfg.dynamic_init) { be.do_solve = 1; be.do_marg = 1; }
         } else { be.do_solve = 1; be.do_marg = 1; }
+        // both initialisations are held while the sequence calibrates (estimator.cpp:236, :275); be_finish slides its window
+        if constexpr (EXCALIB) { if (be.ex_pending) { be.do_solve = 0; be.do_marg = 0; } }
     }
 }
+template __global__ void be_ingest_kernel<false>(Batch, const uint16_t *, size_t, IngestSrc);
+template __global__ void be_ingest_kernel<true>(Batch, const uint16_t *, size_t, IngestSrc);
 
 // ====================================================================================================== be_solve
 namespace {
@@ -1791,7 +1806,8 @@ __device__ __forceinline__ void solve_epilogue(Ctx &c, const Params &X, double c
                     be.Headers[i] = 0;
                     be.pre_idx[i] = i;
                 }
-                for (int k = 0; k < 9; k++) be.ric[k] = cfg.ric[k];
+                // (estimate_extrinsic = 2: setParameter() restores RIC[0], the calibrated rotation, and TIC[0] = 0 -- cfg.tic on such a handle)
+                for (int k = 0; k < 9; k++) be.ric[k] = cfg.estimate_extrinsic == 2 ? be.ex_ric[k] : cfg.ric[k];
                 for (int k = 0; k < 3; k++) { be.tic[k] = cfg.tic[k]; be.latest_Bg[k] = 0; }
                 be.td = cfg.td;
                 be.g[0] = 0; be.g[1] = 0; be.g[2] = cfg.g_norm;   // setParameter(): g = G (estimator.cpp:26)
@@ -3068,8 +3084,10 @@ __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, un
     const int sflag0 = be.solver_flag;
     __syncthreads();
     // dynamic initialisation (static_init: 0, estimator.cpp:230-259): while INITIAL the frame counter just advances; with a full
-    // window and no (successful) attempt the window slides with INITIAL semantics (removeBack, no depth transfer)
-    const bool dyn_initial = sflag0 == 0 && cfg.dynamic_init;
+    // window and no (successful) attempt the window slides with INITIAL semantics (removeBack, no depth transfer).  A static-initialisation
+    // sequence whose full window is held by the extrinsic calibration (estimate_extrinsic = 2) slides the same way (DESIGN.md deviation 16;
+    // upstream it neither initialises nor slides, estimator.cpp:262-316)
+    const bool dyn_initial = sflag0 == 0 && (cfg.dynamic_init || (fc == W && !be.do_solve && be.ex_pending));
     if (dyn_initial) {
         if (fc < W) {
             if (t == 0) be.frame_count = fc + 1;
@@ -3343,6 +3361,22 @@ __global__ void be_stage_projection_kernel(vio_config cfg, const double *in /*pi
 // The IMU factor exactly as evaluate() + assemble() process it in the solver: raw residual whitened by thread 0, the four raw
 // Jacobian column groups by imu_raw_jacobian_part, then [Jw r]^T [Jw r] on the matrix cores (imu_block_mfma).  One wavefront.
 // G961: the 31 x 31 Gram matrix, row-major, columns = pose_i(6) speedbias_i(9) pose_j(6) speedbias_j(9) | r.
+// InitialEXRotation::solveRelativeR on one set of correspondences (vio_stage_relative_r): corres6[n][6] = (x, y, z) in frame l, (x, y, z) in
+// frame r; grid 1, 256 threads, dynamic LDS 40 n + 64 bytes.  The same device code as the calibration phase of be_ingest<true>.
+__global__ __launch_bounds__(256) void be_stage_relative_r_kernel(int n, const double *corres6, double *R9) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_rr[];
+    __shared__ ExShared S;
+    double *X1 = (double *)smem_rr, *Y1 = X1 + n, *X2 = Y1 + n, *Y2 = X2 + n;
+    int *st = (int *)(Y2 + n);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {   // cv::Point2f(corres[i].first(0), corres[i].first(1)) ...
+        X1[i] = (double)(float)corres6[6 * i]; Y1[i] = (double)(float)corres6[6 * i + 1];
+        X2[i] = (double)(float)corres6[6 * i + 3]; Y2[i] = (double)(float)corres6[6 * i + 4];
+    }
+    __syncthreads();
+    ex_relative_r(n, X1, Y1, X2, Y2, st, S);
+    if (threadIdx.x < 9) R9[threadIdx.x] = S.Rout[threadIdx.x];
+}
+
 __global__ __launch_bounds__(64) void be_stage_imu_block_kernel(const PreInt *P, const double *par /*pi7 sbi9 pj7 sbj9*/, double g_norm, double *G961) {
     __shared__ double raw_l[472], M_l[232];
     const int lane = threadIdx.x;

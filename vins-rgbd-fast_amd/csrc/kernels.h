@@ -50,7 +50,8 @@ struct IngestSrc {
     const double *stamps;   // [S] header stamps
     int cap;
 };
-__global__ void be_ingest_kernel(Batch B, const uint16_t *depth_base, size_t depth_stride, IngestSrc src);
+template <bool EXCALIB> __global__ void be_ingest_kernel(Batch B, const uint16_t *depth_base, size_t depth_stride, IngestSrc src);
+__global__ void be_stage_relative_r_kernel(int n, const double *corres6, double *R9);
 __global__ void be_solve_kernel(Batch B);
 __global__ void be_solve_kernel_512(Batch B);
 __global__ void be_marg_kernel(Batch B);

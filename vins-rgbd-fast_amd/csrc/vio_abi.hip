@@ -166,6 +166,12 @@ struct vio_batch {
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the kernel, not of a handle: with several handles of different
 // configurations alive, keep the largest value ever requested (monotonic), otherwise the handle created last would shrink the
 // limit under the others.
+// dynamic LDS of be_ingest: the id -> slot hash table; with the calibration phase (estimate_extrinsic = 2) also the correspondences of two
+// frames, 4 NP doubles behind a 16-byte alignment pad, which reuse that space once the table is no longer needed
+static size_t ingest_lds_bytes(const DevCfg &C, bool excalib) {
+    const size_t ht = (size_t)C.lm_hash_size * 8;
+    return excalib ? std::max(ht, (size_t)4 * C.NP * sizeof(double) + 16) : ht;
+}
 static int raise_lds_limit(const void *fn, size_t bytes) {
     // the attribute belongs to the function ON THE CURRENT DEVICE (a handle per GPU in one process sets it once per device)
     struct Seen { const void *fn; int dev; size_t bytes; };
@@ -287,10 +293,26 @@ int init_state(vio_batch *h, int s_lo, int s_hi, int what = VIO_RESET_ESTIMATOR 
     if (!(what & VIO_RESET_ESTIMATOR)) return VIO_OK;
     std::vector<BeSeq> be(n);
     memset(be.data(), 0, sizeof(BeSeq) * n);
+    // estimate_extrinsic = 2: InitialEXRotation lives outside clearState() (estimator.cpp:43-116 does not touch it): a full reset starts the
+    // calibration over, an estimator restart keeps it -- and with it the calibrated RIC[0] that setParameter() restores, with TIC[0] = 0
+    std::vector<ExSeq> ex;
+    if (h->hc.exc) {
+        ex.resize(n);
+        if (what == (VIO_RESET_ESTIMATOR | VIO_RESET_TRACKER)) {
+            memset(ex.data(), 0, sizeof(ExSeq) * n);
+            for (int s = 0; s < n; s++) { dm::stm(ex[s].ric, dm::eye()); ex[s].success_frame = -1; }
+            HIPCHK(hipMemcpy(h->hc.exc + s_lo, ex.data(), sizeof(ExSeq) * n, hipMemcpyHostToDevice));
+        } else
+            HIPCHK(hipMemcpy(ex.data(), h->hc.exc + s_lo, sizeof(ExSeq) * n, hipMemcpyDeviceToHost));
+    }
     for (int s = 0; s < n; s++) {
         BeSeq &b = be[s];
         for (int i = 0; i <= VIO_MAXW; i++) { b.Rs[i][0] = b.Rs[i][4] = b.Rs[i][8] = 1; b.pre_idx[i] = i; }
         for (int k = 0; k < 9; k++) b.ric[k] = C.c.ric[k];
+        if (!ex.empty()) {
+            b.ex_pending = ex[s].success_frame < 0 ? 1 : 0;
+            for (int k = 0; k < 9; k++) { b.ex_ric[k] = b.ex_pending ? C.c.ric[k] : ex[s].ric[k]; b.ric[k] = b.ex_ric[k]; }
+        }
         for (int k = 0; k < 3; k++) b.tic[k] = C.c.tic[k];
         b.td = C.c.td;
         b.track_td = C.c.td;
@@ -540,7 +562,7 @@ int dynamic_init_step(vio_batch *h, int s, const IngestSrc &src, bool *finalize)
     // ---- window full: attempt (estimator.cpp:232-240), at most every 0.1 s
     bool changed = false;
     vinit::Result res;
-    if (be.cur_stamp - D.initial_timestamp > 0.1) {
+    if (!be.ex_pending && be.cur_stamp - D.initial_timestamp > 0.1) {   // ESTIMATE_EXTRINSIC != 2 (estimator.cpp:236)
         D.attempts++;
         std::vector<int> order(NL), id(NL), st(NL), no(NL);
         const size_t o = (size_t)s * NL;
@@ -630,7 +652,8 @@ int launch_backend(vio_batch *h, vio_batch::Group &g, const uint16_t *d_depth, c
     Bg.s0 = one_seq >= 0 ? one_seq : g.s0;
     const bool prof = one_seq < 0;
     if (prof) PEV(h, 8);
-    be_ingest_kernel<<<S, 256, (size_t)C.lm_hash_size * 8, st>>>(Bg, d_depth, (size_t)C.c.width * C.c.height, src);
+    if (C.exc) be_ingest_kernel<true><<<S, 256, ingest_lds_bytes(C, true), st>>>(Bg, d_depth, (size_t)C.c.width * C.c.height, src);
+    else be_ingest_kernel<false><<<S, 256, ingest_lds_bytes(C, false), st>>>(Bg, d_depth, (size_t)C.c.width * C.c.height, src);
     if (prof) PEV(h, 9);
     if (one_seq < 0) { (void)hipEventRecord(g.ev_ingest, st); g.have_ingest_ev = true; }  // tracker lag 1: the next frame's front-end starts here
     if (h->dyn_active || (C.c.dynamic_init && one_seq >= 0)) {
@@ -810,8 +833,15 @@ static int build_devcfg(const vio_config *cfg, int imu_capacity, DevCfg &C) {
     if (c.grid_rows < 1 || c.grid_cols < 1 || c.grid_rows * c.grid_cols > VIO_MAX_CELLS) { g_err = "too many grid cells"; return VIO_EINVAL; }
     if (c.min_dist < 1 || c.min_dist > 63) { g_err = "min_dist must be 1..63"; return VIO_EINVAL; }
     if (c.lk_max_level < 0 || c.lk_max_level > 3) { g_err = "lk_max_level must be 0..3"; return VIO_EINVAL; }
-    if (c.estimate_extrinsic < 0 || c.estimate_extrinsic > 1) { g_err = "estimate_extrinsic must be 0 or 1"; return VIO_EINVAL; }
-    {   // readParameters() re-orthonormalises the extrinsic rotation through a normalised quaternion (parameters.cpp:202-209)
+    if (c.estimate_extrinsic < 0 || c.estimate_extrinsic > 2) { g_err = "estimate_extrinsic must be 0, 1 or 2"; return VIO_EINVAL; }
+    if (c.estimate_extrinsic == 2 && !c.use_imu) {
+        g_err = "estimate_extrinsic = 2 needs the IMU: the rotation is calibrated against the gyroscope's delta_q (identity without IMU)";
+        return VIO_EINVAL;
+    }
+    if (c.estimate_extrinsic == 2) {   // parameters.cpp:181-190: the file's extrinsic is ignored, RIC = I, TIC = 0
+        dm::stm(C.c.ric, dm::eye());
+        for (int k = 0; k < 3; k++) C.c.tic[k] = 0;
+    } else {   // readParameters() re-orthonormalises the extrinsic rotation through a normalised quaternion (parameters.cpp:202-209)
         dm::m3 Rc = dm::q2R(dm::qnormalized(dm::R2q(dm::ldm(c.ric))));
         dm::stm(C.c.ric, Rc);
     }
@@ -980,6 +1010,7 @@ vio_batch *vio_create_on_device(const vio_config *cfg, int n_seq, int imu_capaci
     DA(B.margA, S * mq * mq); DA(B.margB, S * mq); DA(B.margV, S * n * n); DA(B.margW, S * (n + 16) * (n + 16));
     if (C.MX > 0) DA(B.margE, S * ((size_t)3 * C.MX * C.MX + n * (size_t)C.MX));
     DA(B.odom, S * 11); DA(B.timings, 128); DA(B.fe_ticks, S * 4);
+    if (C.c.estimate_extrinsic == 2) { DA(h->hc.exc, S); DA(h->hc.exh, S * (size_t)VIO_EXCALIB_CAP * VIO_EXCALIB_PAIR_D); }
     B.hist_cap = 2048;
     B.s0 = 0;
     B.ns = 0; B.xcd_nb = 0; B.xcd_n = 8;
@@ -1125,13 +1156,15 @@ vio_batch *vio_create_on_device(const vio_config *cfg, int n_seq, int imu_capaci
         }
         (void)raise_lds_limit((const void *)be_marg_kernel, (size_t)(h->lds_marg));
         (void)raise_lds_limit((const void *)be_marg_exact_kernel, (size_t)(h->lds_marg));
-        (void)raise_lds_limit((const void *)be_ingest_kernel, (size_t)(C.lm_hash_size * 8));
+        const bool excalib = C.c.estimate_extrinsic == 2;
+        const void *ingest = excalib ? (const void *)be_ingest_kernel<true> : (const void *)be_ingest_kernel<false>;
+        (void)raise_lds_limit(ingest, ingest_lds_bytes(C, excalib));
 
         (void)raise_lds_limit((const void *)fe_select_kernel, (size_t)(h->lds_select));
         (void)raise_lds_limit((const void *)fe_add_kernel, (size_t)(h->lds_add));
         (void)raise_lds_limit((const void *)fe_fast_kernel, (size_t)(h->lds_fast));
         bool fits = lds_fits(C.MX > 0 ? (const void *)be_marg_exact_kernel : (const void *)be_marg_kernel, h->lds_marg, "be_marg") &&
-                    lds_fits((const void *)be_ingest_kernel, (size_t)C.lm_hash_size * 8, "be_ingest") &&
+                    lds_fits(ingest, ingest_lds_bytes(C, excalib), "be_ingest") &&
                     lds_fits((const void *)fe_select_kernel, h->lds_select, "fe_select") && lds_fits((const void *)fe_add_kernel, h->lds_add, "fe_add") &&
                     lds_fits((const void *)fe_fast_kernel, h->lds_fast, "fe_fast");
         if (fits && h->solve_mode == 1)
@@ -1429,7 +1462,7 @@ int vio_feed_modes(vio_batch *h, const uint8_t *gray, const uint16_t *depth_mm, 
     return VIO_OK;
 }
 
-int vio_abi_version(void) { return 6; }
+int vio_abi_version(void) { return 7; }
 
 // marg_exact = 2 (the literal marginalisation with a CERTIFIED first inverse): out2 = {marginalisations of sequence seq whose certificate failed
 // since vio_create / vio_reset -- those frames used the block inverse WITHOUT the proof that the reference's 1e-8 cut drops nothing --, 1 if the
@@ -1443,6 +1476,35 @@ int vio_get_marg_certificate(vio_batch *h, int seq, int32_t *out2) {
     HIPCHK(hipMemcpy(&be, h->B.be + seq, sizeof(BeSeq), hipMemcpyDeviceToHost));
     out2[0] = be.dbg[12]; out2[1] = be.dbg[11];
     return VIO_OK;
+}
+
+int vio_get_ex_calibration(vio_batch *h, int seq, double *out16, int cap, double *history) {
+    DevGuard dev_guard(h);
+    if (!h || !out16 || seq < 0 || seq >= h->S || cap < 0 || (cap > 0 && !history)) return VIO_EINVAL;
+    if (dev_guard.failed) { g_err = "hipSetDevice failed"; return VIO_EDEVICE; }
+    for (int k = 0; k < 16; k++) out16[k] = 0;
+    if (!h->hc.exc) return 0;
+    HIPCHK(hipDeviceSynchronize());
+    ExSeq x;
+    BeSeq be;
+    HIPCHK(hipMemcpy(&x, h->hc.exc + seq, sizeof(ExSeq), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&be, h->B.be + seq, sizeof(BeSeq), hipMemcpyDeviceToHost));
+    out16[0] = be.ex_pending ? 2 : 1;
+    out16[1] = x.count;
+    out16[2] = x.success_frame;
+    for (int k = 0; k < 9; k++) out16[3 + k] = x.ric[k];
+    for (int k = 0; k < 4; k++) out16[12 + k] = x.sv[k];
+    const int m = std::min(cap, x.count);
+    if (m > 0) {
+        // the ring holds the newest pairs; hand them out oldest first
+        std::vector<double> ring((size_t)VIO_EXCALIB_CAP * VIO_EXCALIB_PAIR_D);
+        HIPCHK(hipMemcpy(ring.data(), h->hc.exh + (size_t)seq * VIO_EXCALIB_CAP * VIO_EXCALIB_PAIR_D, ring.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int i = 0; i < m; i++) {
+            const double *src = &ring[(size_t)((x.head + i) % VIO_EXCALIB_CAP) * VIO_EXCALIB_PAIR_D];
+            for (int k = 0; k < VIO_EXCALIB_PAIR_D; k++) history[(size_t)i * VIO_EXCALIB_PAIR_D + k] = src[k];
+        }
+    }
+    return x.count;
 }
 
 int vio_host_buffers_done(vio_batch *h, int calls_ago) {
@@ -2173,6 +2235,25 @@ done:
     if (d1) (void)hipFree(d1);
     if (d2) (void)hipFree(d2);
     if (ds) (void)hipFree(ds);
+    return rc;
+}
+
+int vio_stage_relative_r(int n, const double *corres6, double *R9) {
+    if (n < 0 || (n > 0 && !corres6) || !R9) return VIO_EINVAL;
+    int rc = VIO_OK;
+    double *dc = nullptr, *dR = nullptr;
+    const size_t lds = (size_t)n * 40 + 64;   // four coordinate arrays + the RANSAC status flags
+    STAGE_CHK(hipMalloc((void **)&dc, sizeof(double) * 6 * (n + 1)));
+    STAGE_CHK(hipMalloc((void **)&dR, sizeof(double) * 9));
+    if (n > 0) STAGE_CHK(hipMemcpy(dc, corres6, sizeof(double) * 6 * n, hipMemcpyHostToDevice));
+    (void)raise_lds_limit((const void *)be_stage_relative_r_kernel, lds);
+    if (!lds_fits((const void *)be_stage_relative_r_kernel, lds, "be_stage_relative_r")) { rc = VIO_ECAPACITY; goto done; }
+    be_stage_relative_r_kernel<<<1, 256, lds>>>(n, dc, dR);
+    STAGE_CHK(hipDeviceSynchronize());
+    STAGE_CHK(hipMemcpy(R9, dR, sizeof(double) * 9, hipMemcpyDeviceToHost));
+done:
+    if (dc) (void)hipFree(dc);
+    if (dR) (void)hipFree(dR);
     return rc;
 }
 

@@ -28,6 +28,19 @@
 
 struct GridRect { int x, y, w, h; };
 
+// InitialEXRotation (initial_ex_rotation.h) of one sequence of an estimate_extrinsic = 2 handle; its (Rc, Rimu, Rc_g) history lives in
+// Batch::exh as [S][VIO_EXCALIB_CAP][12] doubles = q(Rc), q(Rimu), q(Rc_g) (w x y z each), a ring of the newest VIO_EXCALIB_CAP pairs
+#define VIO_EXCALIB_CAP 2048
+#define VIO_EXCALIB_PAIR_D 12
+struct ExSeq {
+    double ric[9];      // InitialEXRotation::ric, the current estimate (row-major)
+    double sv[4];       // singular values of A of the last call, descending
+    int count;          // stored pairs (<= VIO_EXCALIB_CAP)
+    int head;           // ring slot of the oldest stored pair
+    int calls;          // CalibrationExRotation calls (InitialEXRotation::frame_count; not capped)
+    int success_frame;  // BeSeq::frames_processed after the frame that succeeded, -1 while calibrating
+};
+
 // device-side copy of the configuration + derived constants
 struct DevCfg {
     vio_config c;
@@ -51,6 +64,10 @@ struct DevCfg {
     int MXL;            // marg_exact: largest block whose eigen-decomposition runs LDS-resident (Householder + implicit QL); larger ones use the HBM Jacobi
     int eig_jacobi;     // VIO_MARG_EIG_JACOBI: the eigen-decompositions of the literal marginalisation that do not fit LDS by cyclic Jacobi sweeps over HBM (rounds 3 - 5) instead of sym_eig_hbm
     int eig_one_wave;   // VIO_EIG_ONE_WAVE: the Householder tridiagonalisation of the LDS-resident eigen-decompositions on ONE wavefront (no workgroup barriers) instead of the whole workgroup
+    // estimate_extrinsic = 2 handles only (nullptr otherwise): calibration state [S] and pair history of every sequence (here rather than in
+    // Batch, which every kernel takes by value; only be_ingest<true> reads them)
+    ExSeq *exc;
+    double *exh;
 };
 
 // IntegrationBase (integration_base.h)
@@ -136,7 +153,12 @@ struct BeSeq {
     // bounds-constrained solves (estimator.cpp:1282-1297), sticky since vio_create / vio_reset: inverse depths cut by the bound while a point was
     // formed, bounded landmarks that entered solves, trial evaluations and shortened steps of the projected Armijo line search (vio_get_bound_stats)
     int bound_clamps, bounded_solves, ls_evals, ls_contractions;
+    // estimate_extrinsic = 2 (InitialEXRotation, estimator.cpp:208-226): the rotation a reboot restores (RIC[0] of setParameter(): the calibrated
+    // one once calibration succeeded) and whether the sequence is still calibrating (both initialisations are held while it is)
+    double ex_ric[9];
+    int ex_pending;
 };
+
 
 // flat parameter arrays of one solve (estimator.h para_Pose / para_SpeedBias / para_Ex_Pose / para_Td): pose = p(3) q(x,y,z,w)
 // relo: relo_Pose (estimator.h:179), the copy of the matched window frame's pose that the relocalisation factors act on

@@ -103,7 +103,10 @@ def parse_opencv_yaml(text):
 
 def config_from_yaml(path_or_text, P=None, strict=True):
     """vio_config from a reference configuration file (parameters.cpp:81-243).  Settings that select code paths outside the
-    built hot path raise ValueError when strict (``estimate_extrinsic: 2``, a camera model other than PINHOLE); with strict=False they are returned in the second element as a list of notes."""
+    built hot path (a camera model other than PINHOLE), or that discard part of the file (``estimate_extrinsic: 2``), raise ValueError when
+    strict; with strict=False they are returned in the second element as a list of notes.  ``estimate_extrinsic: 2`` then gives a mode-2
+    configuration with ric = I and tic = 0 (parameters.cpp:181-190: the file's extrinsicRotation / extrinsicTranslation are ignored and the
+    rotation is calibrated online, VioBatch.ex_calibration)."""
     if P is None:
         import importlib
         P = importlib.import_module("vins-rgbd-fast_amd")
@@ -140,12 +143,18 @@ def config_from_yaml(path_or_text, P=None, strict=True):
             setattr(c, k, float(dp[k]))
     need(str(g("model_type", "PINHOLE")).upper() != "PINHOLE", "only the PINHOLE camera model is on the hot path")
     c.estimate_extrinsic = int(g("estimate_extrinsic", 0))
-    need(c.estimate_extrinsic == 2, "estimate_extrinsic: 2 (online extrinsic initialisation) is out of scope")
-    if "extrinsicRotation" in y:
+    need(c.estimate_extrinsic == 2, "estimate_extrinsic: 2 (online extrinsic calibration) discards the file's extrinsicRotation / "
+                                    "extrinsicTranslation (ric = I, tic = 0); strict=False accepts it")
+    if c.estimate_extrinsic == 2:
+        for i in range(9):
+            c.ric[i] = 1.0 if i % 4 == 0 else 0.0
+        for i in range(3):
+            c.tic[i] = 0.0
+    elif "extrinsicRotation" in y:
         R = np.asarray(y["extrinsicRotation"], np.float64).reshape(3, 3)
         for i in range(9):
             c.ric[i] = float(R.ravel()[i])
-    if "extrinsicTranslation" in y:
+    if "extrinsicTranslation" in y and c.estimate_extrinsic != 2:
         T = np.asarray(y["extrinsicTranslation"], np.float64).ravel()
         for i in range(3):
             c.tic[i] = float(T[i])
