@@ -202,7 +202,9 @@ void vio_host_free(void *p);
 int vio_abi_sizeof(int what);
 /* Contract version of this header: 4 = a vio_feed host image set is free when the next vio_feed has returned; 5 = two uploads in flight (see
  * "Host buffers" above, vio_host_buffers_done); 6 = + vio_get_bound_stats, the inverse-depth bound handled as Ceres does (projected line search);
- * 7 = + estimate_extrinsic = 2 (vio_get_ex_calibration, vio_stage_relative_r). */
+ * 7 = + estimate_extrinsic = 2 (vio_get_ex_calibration, vio_stage_relative_r); 8 = overflow flag 128 means only "extrinsic-calibration history
+ * full": the fallback solver's clamp-only treatment of a bounded landmark moved to flag 512 (VIO_OVF_DEVIATION), which is no capacity error,
+ * and flag 256 is documented (vio_status). */
 int vio_abi_version(void);
 /* capacities derived from the configuration: out[0] = tracker points per sequence, out[1] = landmark slots, out[2] = IMU ring */
 int vio_get_capacity(vio_batch *h, int32_t *out3);
@@ -212,7 +214,8 @@ int vio_get_solver_kind(vio_batch *h);
 /* Bounds-constrained solves (estimator.cpp:1282-1297: SetParameterUpperBound(para_Feature, 0, 2 / DEPTH_MAX_DIST) on landmarks triangulated
  * without a depth measurement, which makes Ceres project x0 onto the box and run its Armijo line search along every step).  Counters of
  * sequence seq since vio_create / vio_reset: out4 = {inverse depths cut by the bound while a point was formed, bounded landmarks that
- * entered solves, trial evaluations of the line search, shortened steps}.  Synchronises the device. */
+ * entered solves, trial evaluations of the line search, shortened steps}; the fallback solver (vio_get_solver_kind() == 0) counts the first
+ * two and runs no line search.  Synchronises the device. */
 int vio_get_bound_stats(vio_batch *h, int seq, int64_t *out4);
 /* vio_config.marg_exact = 2 only: out2 = {marginalisations of sequence seq whose certificate FAILED since vio_create / vio_reset (such a frame
  * keeps the block inverse without the proof that the reference's 1e-8 eigenvalue cut of marginalization_factor.cpp:281-291 drops nothing),
@@ -232,6 +235,7 @@ int vio_get_marg_certificate(vio_batch *h, int seq, int32_t *out2);
 int vio_get_ex_calibration(vio_batch *h, int seq, double *out16, int cap, double *history);
 
 /* Results read out of the path (SURVEY.md §8b "Results read out").  All getters synchronise first. */
+enum { VIO_OVF_DEVIATION = 512 };   /* vio_status.overflow_flags bit that reports a deviation, not lost capacity */
 typedef struct vio_status {
     int32_t code;                 /* VIO_OK / VIO_NEED_IMU / VIO_REBOOTED of the last vio_process */
     int32_t solver_flag;          /* 0 INITIAL, 1 NON_LINEAR (estimator.h SolverFlag) */
@@ -249,8 +253,13 @@ typedef struct vio_status {
                                      4 FAST candidates of a cell, 8 residual list, 16 IMU ring overwritten, 32 solver iteration slots
                                      exhausted before the trust-region loop finished, 64 relocalisation request dropped (vio_set_relo_frame),
                                      128 extrinsic-calibration history full: its oldest pair was dropped (estimate_extrinsic = 2, see
-                                     vio_get_ex_calibration) (code = VIO_ECAPACITY) */
-    int32_t overflow_frames;      /* frames that raised any capacity flag since the last reset / reboot */
+                                     vio_get_ex_calibration), 256 a solve skipped: it did not fit the fused evaluate + assemble kernel on a
+                                     handle that launches nothing else (VIO_FUSE), the window is left unoptimised (code = VIO_ECAPACITY
+                                     for any of these); 512 (VIO_OVF_DEVIATION) NOT a capacity flag: the fallback solver
+                                     (vio_get_solver_kind() == 0) met a landmark under the inverse-depth bound and clamped its candidates
+                                     instead of running Ceres' projected line search -- a deviation from the reference; it leaves code and
+                                     overflow_frames alone */
+    int32_t overflow_frames;      /* frames that raised any capacity flag (512 excepted) since the last reset / reboot */
     int32_t iterations_total, solves_total; /* solver iterations / solves since vio_create */
 } vio_status;
 int vio_get_status(vio_batch *h, int seq, vio_status *out);

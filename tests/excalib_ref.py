@@ -212,17 +212,19 @@ TIC_TRUE = np.array([0.05, -0.02, 0.03])
 
 
 class Scene:
-    """rot: amplitude (rad) of yaw / pitch / roll, each a sine at about 3 rad/s (1.5 rad/s peak rate); rot = 0 is a pure translation"""
+    """rot: amplitude (rad) of yaw / pitch / roll, each a sine at about 3 rad/s (1.5 rad/s peak rate); rot = 0 is a pure translation.
+    axes: factors on the three amplitudes ((1, 0, 0): yaw only, a rotation about one axis, which leaves the extrinsic rotation unobservable)"""
 
-    def __init__(self, cfg, phase=0.0, rot=0.5, n_landmarks=1500, seed=7, ric=RIC_TRUE, tic=TIC_TRUE):
+    def __init__(self, cfg, phase=0.0, rot=0.5, n_landmarks=1500, seed=7, ric=RIC_TRUE, tic=TIC_TRUE, axes=(1.0, 1.0, 1.0)):
         self.cfg, self.phase, self.rot, self.ric, self.tic = cfg, float(phase), float(rot), np.asarray(ric), np.asarray(tic)
+        self.axes = tuple(float(a) for a in axes)
         rs = np.random.RandomState(seed)
         self.L = np.stack([rs.uniform(3.0, 9.0, n_landmarks), rs.uniform(-7, 7, n_landmarks), rs.uniform(-7, 7, n_landmarks)], 1)
         self.imu_rate, self.cam_rate, self.t0 = 200.0, 10.0, 1.0
 
     def pose(self, t):
-        a, ph = self.rot, self.phase
-        yaw, pitch, roll = a * np.sin(3.0 * t + ph), a * np.sin(2.6 * t + 1.3 * ph + 0.7), a * np.sin(3.4 * t + 0.7 * ph + 1.9)
+        a, ph, (ky, kp, kr) = self.rot, self.phase, self.axes
+        yaw, pitch, roll = a * ky * np.sin(3.0 * t + ph), a * kp * np.sin(2.6 * t + 1.3 * ph + 0.7), a * kr * np.sin(3.4 * t + 0.7 * ph + 1.9)
         cz, sz, cy, sy, cx, sx = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch), np.cos(roll), np.sin(roll)
         Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1.0]])
         Ry = np.array([[cy, 0, sy], [0, 1.0, 0], [-sy, 0, cy]])

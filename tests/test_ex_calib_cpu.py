@@ -22,6 +22,21 @@ def test_restatement_recovers_ric_true(P):
     assert X.rot_angle_deg(ric, X.RIC_TRUE) < 1e-3
 
 
+def test_rotation_about_one_axis_never_calibrates(P):
+    """yaw only (Scene axes = (1, 0, 0)): the hand-eye constraints leave a rotation about that axis free, the third singular value of the
+    averaging stays at round-off and the calibration never succeeds -- the scene tests/test_gpu_ex_calib.py drives past the history cap"""
+    cfg = P.canonical_config(estimate_extrinsic=2)
+    sc = X.Scene(cfg, phase=0.0, axes=(1.0, 0.0, 0.0))
+    k, _ = X.predict_success(sc, max_frames=120)
+    assert k is None
+    cal = X.InitialExRotation(cfg.window_size)
+    for f in range(1, 60):
+        _, Rl = sc.pose(sc.frame_time(f - 1))
+        _, Rr = sc.pose(sc.frame_time(f))
+        cal.step(sc.corres(sc.frame_time(f - 1), sc.frame_time(f)), X.R2q(Rl.T @ Rr))
+    assert cal.sv[1] > 0.5 and cal.sv[2] < 1e-6, cal.sv     # two-dimensional null space: the rotation about the yaw axis is free
+
+
 def test_restatement_relative_r_matches_truth():
     """solveRelativeR on generated correspondences with a known motion: the returned matrix is the rotation of frame r in frame l"""
     rs = np.random.RandomState(3)

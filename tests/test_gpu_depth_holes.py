@@ -99,14 +99,7 @@ def test_depthless_landmarks_of_a_blinded_sensor_match_the_oracle(P):
     triangulated from parallax only (flag 2) and optimised under the inverse-depth bound; the bound itself rarely cuts anything (a landmark
     beyond 3 m has an inverse depth below 1/3, half the bound), but the program IS bounds-constrained, so every step goes through the line
     search -- whose first trial, the full step, is usually accepted."""
-    cfg = P.canonical_config(depth_max=3.0)
-    sc = vio_ct.synth_like(cfg)
-    seq, n = 2, 60
-
-    def blind(f, g, d):
-        d[d > 3000] = 0
-        return g, d
-    frames = _frames(P, sc, seq, n, blind)
+    cfg, sc, seq, n, frames = _blind_scene(P)
     o, lm_o, b, traj, stat, lm_h = _run_both(P, cfg, sc, seq, n, frames)
     clamps, bounded = o["oracle"].bound_stats()
     evals, contractions = o["oracle"].line_search_stats()
@@ -117,10 +110,23 @@ def test_depthless_landmarks_of_a_blinded_sensor_match_the_oracle(P):
     _compare(o, lm_o, traj, stat, lm_h, n, pos_tol=1e-5)
 
 
-def _bound_scene(P, quirks=0):
-    cfg = P.canonical_config(depth_max=10.0, reference_quirks=quirks)
+def _blind_scene(P):
+    """DEPTH_MAX_DIST = 3 m, the depth image blinded beyond it"""
+    cfg = P.canonical_config(depth_max=3.0)
     sc = vio_ct.synth_like(cfg)
     seq, n = 2, 60
+
+    def blind(f, g, d):
+        d[d > 3000] = 0
+        return g, d
+    return cfg, sc, seq, n, _frames(P, sc, seq, n, blind)
+
+
+def _bound_scene(P, quirks=0, n=60, **kw):
+    """DEPTH_MAX_DIST = 10 m, the depth image blinded beyond 2.5 m (kw: further configuration fields, tests/test_gpu_solver_paths.py)"""
+    cfg = P.canonical_config(depth_max=10.0, reference_quirks=quirks, **kw)
+    sc = vio_ct.synth_like(cfg)
+    seq = 2
 
     def blind(f, g, d):
         d[d > 2500] = 0

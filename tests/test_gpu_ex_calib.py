@@ -233,3 +233,39 @@ def test_feed_path_mode2(P):
             if e["pairs"] > 0:
                 _check_against_restatement(e, cfg.window_size)
     assert all(b.status(s).frames_processed > 40 for s in range(S))
+
+
+def test_full_calibration_history_raises_flag_128_and_keeps_the_latest_pairs(P):
+    """A rotation about one axis never calibrates (tests/test_ex_calib_cpu.py): every frame adds a pair until the ring of VIO_EXCALIB_CAP =
+    2048 pairs is full.  From the first dropped pair on every frame carries overflow flag 128 and code VIO_ECAPACITY -- flag 128 means only
+    "calibration history full" (ABI 8; the fallback solver's deviation is flag 512, which never appears here) -- and the history holds the
+    latest 2048 pairs, oldest first."""
+    cap, extra = 2048, 4
+    cfg = P.canonical_config(estimate_extrinsic=2)
+    sc = X.Scene(cfg, phase=0.0, axes=(1.0, 0.0, 0.0))
+    assert X.predict_success(sc, max_frames=60)[0] is None
+    n = cap + 1 + extra                   # the frame of index f >= 1 adds pair f: index cap + 1 drops the first
+    d = Driver(P, cfg, [sc], n)
+    full = None
+    for f in range(n):
+        d.step()
+        st, e = d.b.status(0), d.b.ex_calibration(0)
+        assert e["state"] == 2 and st.solver_flag == 0, (f, e["state"])
+        assert st.overflow_flags & 512 == 0, (f, st.overflow_flags)
+        if f <= cap:
+            assert e["pairs"] == f and st.overflow_flags == 0 and st.code == P.VIO_OK, (f, e["pairs"], st.overflow_flags, st.code)
+        else:
+            assert e["pairs"] == cap and st.overflow_flags == 128 and st.code == P.VIO_ECAPACITY, (f, e["pairs"], st.overflow_flags, st.code)
+        if f == cap:
+            full = d.b.ex_calibration(0, history=True)
+    dropped = n - 1 - cap
+    assert st.overflow_frames == dropped, st.overflow_frames
+    e = d.b.ex_calibration(0, history=True)
+    assert e["history"].shape == (cap, 3, 4)
+    assert np.array_equal(e["history"][:cap - dropped], full["history"][dropped:])   # the oldest went first
+    # the newest pairs sit at the end, in frame order: their IMU rotation is the relative body rotation of their two frames
+    for j in range(dropped + 1):
+        _, Rl = sc.pose(sc.frame_time(n - 2 - j))
+        _, Rr = sc.pose(sc.frame_time(n - 1 - j))
+        assert X.rot_angle_deg(X.q2R(e["history"][cap - 1 - j][1]), Rl.T @ Rr) < 0.05, j   # (neighbouring pairs differ by > 0.3 degrees)
+    assert not X.average(e["history"], e["pairs"], cfg.window_size)[2] and e["sv"][2] < 0.25, e["sv"]

@@ -1906,11 +1906,13 @@ __device__ __forceinline__ void solve_body(const Batch &B, int s, int *scratch, 
     {
         // The persistent solver (VIO_SOLVE_MODE=0 and the fallback for residual counts beyond the phased solver's range) honours the inverse-depth
         // bound by clamping candidates only; Ceres' treatment of the bounds-constrained program (projection of x0, Armijo line search) lives in
-        // the phased solver (be_phased.h).  A frame that meets a bounded landmark here is flagged (overflow bit 128).
+        // the phased solver (be_phased.h).  A frame that meets a bounded landmark here is flagged (overflow bit 512: a deviation from the
+        // reference, not lost capacity), and the bounded landmarks / clamped candidates are counted as ps_setup / ps_form_candidate count them
+        // (vio_get_bound_stats; no line search runs here, its two counters stay 0)
         const int *al = c.pair_list + c.nres_cap - c.NL;
-        bool hit = false;
-        for (int k = t; k < Fa; k += nt) hit = hit || c.lm_est[al[k]] == 2;
-        if (hit) atomicOr(&c.be->overflow, 128);
+        int nb = 0;
+        for (int k = t; k < Fa; k += nt) nb += c.lm_est[al[k]] == 2 ? 1 : 0;
+        if (nb) { atomicOr(&c.be->overflow, 512); atomicAdd(&c.be->bounded_solves, nb); }
     }
     const int nlm = be.n_lm;
     int *alist = c.pair_list + c.nres_cap - c.NL;              // variable-landmark slots, kept for the whole solve
@@ -2148,7 +2150,7 @@ __device__ __forceinline__ void solve_body(const Batch &B, int s, int *scratch, 
             int slot = alist[k], pi = c.lm_pidx[slot];
             double v = c.feat[pi] + stl[k] * sl[k];
             double ub = (c.lm_est[slot] == 2) ? 2.0 / cfg.depth_max : 1.7976931348623157e308;
-            if (v > ub) v = ub;
+            if (v > ub) { v = ub; atomicAdd(&be.bound_clamps, 1); }
             c.cfeat[pi] = v;
         }
         __syncthreads();
@@ -3225,7 +3227,10 @@ __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, un
         lm_compact(c, flag, offs, scratch);
     }
     PH(29);
-    if (dyn_initial) return;   // still INITIAL: nothing to publish
+    if (dyn_initial) {   // still INITIAL: nothing to publish (the frame's flags still count)
+        if (t == 0 && (be.overflow & ~VIO_OVF_DEVIATION)) be.overflow_frames++;
+        return;
+    }
     // ---- removeFailures (feature_manager.cpp:225-233); not called on the STATIC initialisation frame (estimator.cpp:282-290)
     if (sflag0 == 1) {
         nlm = be.n_lm;
@@ -3246,7 +3251,7 @@ __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, un
         double *hrow = B.odom_hist + ((size_t)s * B.hist_cap + (hc % B.hist_cap)) * 11;  // ring: the getter un-rotates it
         for (int k = 0; k < 11; k++) hrow[k] = od[k];
         B.odom_count[s] = hc + 1;
-        if (be.overflow) be.overflow_frames++;
+        if (be.overflow & ~VIO_OVF_DEVIATION) be.overflow_frames++;   // (bit 512 reports a deviation, not lost capacity)
     }
     PH(30);
 }

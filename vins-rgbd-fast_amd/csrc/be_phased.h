@@ -166,10 +166,12 @@ __device__ void ps_accept(const Batch &B, int s) {
     Ctx c = make_ctx(B, s);
     const vio_config &cfg = c.C->c;
     const int W = c.W;
-    // total cost: the per-block partial sums, one per lane (n_eval_blocks <= PS_MAX_EVAL_BLOCKS <= 64), reduced in a fixed tree order
+    // total cost: the per-block partial sums, one per lane (at most PS_MAX_EVAL_BLOCKS <= 64; 2 + PS_FUSE_MAXBLK fused), reduced in a fixed tree order
     // (a device-scope read-modify-write as the load: it returns the value at the coherence point, whatever sits in this XCD's L2 -- no cache-wide
     // invalidate needed, see the tail of ps_eval_body)
-    double total = t < st.n_eval_blocks ? __longlong_as_double((long long)atomicOr((unsigned long long *)&st.part[t], 0ull)) : 0.0;
+    // (a fused solve: prior, IMU, then one partial cost per CHUNK -- more than its workgroups when they loop)
+    const int nparts = st.fused ? 2 + st.nblk : st.n_eval_blocks;
+    double total = t < nparts ? __longlong_as_double((long long)atomicOr((unsigned long long *)&st.part[t], 0ull)) : 0.0;
     total = wave_sum_dpp(total);
     if (st.stage == PS_EVAL_X0) {
         if (t == 0) { st.cost = total; c.be->initial_cost = total; st.point_new = 1; st.stage = PS_ASM; if (st.fused) st.rowbuf ^= 1; }
@@ -944,6 +946,7 @@ __global__ __launch_bounds__(256) void ps_evalf_kernel(Batch B) {
     const int W = c.W, W1 = W + 1, n = c.NPR, LW = c.LW;
     const int lane = t & 63, wave = t >> 6, li = lane & 15, lk = lane >> 4;
     __shared__ double sred[64];
+    __shared__ double ccost[PS_FUSE_MAXBLK];   // chunk workgroups: the cost of each chunk taken
     __shared__ Params X;
     {
         const double *src = (const double *)(cand ? &st.Xc : &st.X);
@@ -1219,10 +1222,23 @@ __global__ __launch_bounds__(256) void ps_evalf_kernel(Batch B) {
         }
         };
         // (the first chunk as straight-line code: as a general loop the kernel was 6 % slower)
+        // Every chunk's cost is reduced on its own and published as part[2 + chunk]: the total ps_accept forms must not depend on how many
+        // chunks a workgroup took (VIO_FUSE = n) -- the line search of a bounds-constrained solve interpolates on its last bits
         chunk(b - 2);
-        for (int pb = b - 2 + B.fuse; pb < nblk; pb += B.fuse) { __syncthreads(); chunk(pb); }   // (the previous chunk's records are still being read)
+        {
+            const double v = block_sum(cost, sred);
+            if (t == 0) ccost[0] = v;
+            cost = 0;
+        }
+        for (int pb = b - 2 + B.fuse, k = 1; pb < nblk; pb += B.fuse, k++) {
+            __syncthreads();   // (the previous chunk's records are still being read)
+            chunk(pb);
+            const double v = block_sum(cost, sred);
+            if (t == 0) ccost[k] = v;
+            cost = 0;
+        }
     }
-    cost = block_sum(cost, sred);
+    if (b < 2) cost = block_sum(cost, sred);
     // No cache-wide fence (on gfx950 __threadfence() is buffer_wbl2 sc1 + buffer_inv sc1: the XCD's whole L2 written back AND invalidated -- a
     // fence per published partial block made every workgroup on the device seven times slower, and even one per workgroup costs 10 % of the
     // whole pipeline, see ps_eval_body).  What crosses workgroups inside this kernel: the partial cost (published by a returning device-scope
@@ -1230,10 +1246,14 @@ __global__ __launch_bounds__(256) void ps_evalf_kernel(Batch B) {
     // the barriers of block_sum before thread 0 gets here; read back with device-scope atomic loads).  Rows and blocks go to later kernels.
     __shared__ int last, lastc;
     if (t == 0) {
-        const unsigned long long old = atomicExch((unsigned long long *)&st.part[b], (unsigned long long)__double_as_longlong(cost));
+        const int mine = b >= 2 ? (st.nblk - (b - 2) + B.fuse - 1) / B.fuse : 0;   // chunks this workgroup took
+        unsigned long long old = 0;
+        if (b < 2) old = atomicExch((unsigned long long *)&st.part[b], (unsigned long long)__double_as_longlong(cost));
+        else
+            for (int k = 0; k < mine; k++)   // (every returned value feeds the counter increments below)
+                old ^= atomicExch((unsigned long long *)&st.part[b + k * B.fuse], (unsigned long long)__double_as_longlong(ccost[k]));
         int zero;
         asm volatile("v_and_b32 %0, 0, %1" : "=v"(zero) : "v"((int)(old >> 32)));
-        const int mine = b >= 2 ? (st.nblk - (b - 2) + B.fuse - 1) / B.fuse : 0;   // chunks this workgroup took
         lastc = (mine > 0 && withJ) ? (atomicAdd(&st.chunk_done, mine + zero) == st.nblk - mine) : 0;
         last = atomicAdd(&st.eval_done, 1 + zero) == st.n_eval_blocks - 1;
     }
@@ -2053,7 +2073,11 @@ __global__ __launch_bounds__(256, 2) void ps_ls_kernel(Batch B) {   // (held to 
     ps_sel_rows(B, c, st.rowbuf);
     const BeSeq &be = *c.be;
     const vio_config &cfg = c.C->c;
-    const int W = c.W, W1 = W + 1, P = c.P, Fa = st.Fa, nblk = st.n_eval_blocks;
+    // the evaluation roles of ps_eval_role's layout -- prior, IMU, IMU, then 256 eval_rpt projection residuals each -- counted from the residual
+    // list, NOT st.n_eval_blocks: a fused solve sets that from its own chunking (2 + chunks of PS_FUSE_CAP - W residuals), which in this layout
+    // covers only part of the projection residuals (none with one chunk).  The handle's eligibility (W NP / 256 + 4 <= PS_MAX_EVAL_BLOCKS)
+    // keeps the count within part[] / lpart's 64 slots; the min() only guards the arrays
+    const int W = c.W, W1 = W + 1, P = c.P, Fa = st.Fa, nblk = min(PS_MAX_EVAL_BLOCKS, 3 + (st.nres + 256 * B.eval_rpt - 1) / (256 * B.eval_rpt));
     constexpr int XD = ((int)(sizeof(Params) / sizeof(double)) + 1) & ~1;
     Params &X = *(Params *)lds;
     double *lsw = (double *)lds + XD, *lpart = lsw + 104;                 // scalar workspace (96) + broadcast slot, partial costs (64)

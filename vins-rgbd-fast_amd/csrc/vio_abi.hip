@@ -1462,7 +1462,7 @@ int vio_feed_modes(vio_batch *h, const uint8_t *gray, const uint16_t *depth_mm, 
     return VIO_OK;
 }
 
-int vio_abi_version(void) { return 7; }
+int vio_abi_version(void) { return 8; }
 
 // marg_exact = 2 (the literal marginalisation with a CERTIFIED first inverse): out2 = {marginalisations of sequence seq whose certificate failed
 // since vio_create / vio_reset -- those frames used the block inverse WITHOUT the proof that the reference's 1e-8 cut drops nothing --, 1 if the
@@ -1854,7 +1854,8 @@ void *vio_get_stream(vio_batch *h) { DevGuard dev_guard(h); return h ? (void *)h
 
 static void fill_status(const BeSeq &be, const FeSeq &fe, vio_status *out) {
     const int ovf = be.overflow | fe.overflow;
-    out->code = (ovf && be.status_code == VIO_OK) ? VIO_ECAPACITY : be.status_code;  // a table overflowed in the last frame: results are truncated, say so
+    // a table overflowed in the last frame: results are truncated, say so (bit 512 reports a deviation, not lost capacity)
+    out->code = ((ovf & ~VIO_OVF_DEVIATION) && be.status_code == VIO_OK) ? VIO_ECAPACITY : be.status_code;
     out->overflow_flags = ovf; out->overflow_frames = be.overflow_frames;
     out->iterations_total = be.iter_total; out->solves_total = be.solve_total;
     out->solver_flag = be.solver_flag; out->frame_count = be.frame_count;
