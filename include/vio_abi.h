@@ -204,7 +204,8 @@ int vio_abi_sizeof(int what);
  * "Host buffers" above, vio_host_buffers_done); 6 = + vio_get_bound_stats, the inverse-depth bound handled as Ceres does (projected line search);
  * 7 = + estimate_extrinsic = 2 (vio_get_ex_calibration, vio_stage_relative_r); 8 = overflow flag 128 means only "extrinsic-calibration history
  * full": the fallback solver's clamp-only treatment of a bounded landmark moved to flag 512 (VIO_OVF_DEVIATION), which is no capacity error,
- * and flag 256 is documented (vio_status). */
+ * and flag 256 is documented (vio_status); 9 = + stage harnesses of the remaining be_linalg.h primitives (vio_stage_jacobi, vio_stage_sym_eig_lds,
+ * vio_stage_spd_inverse16, vio_stage_scan_flags, vio_stage_schur, vio_stage_pinv15, vio_stage_chol blocks = -8 / -9). */
 int vio_abi_version(void);
 /* capacities derived from the configuration: out[0] = tracker points per sequence, out[1] = landmark slots, out[2] = IMU ring */
 int vio_get_capacity(vio_batch *h, int32_t *out3);
@@ -396,13 +397,41 @@ int vio_stage_imu_block(const vio_config *cfg, int n, const double *dt, const do
  * x_out = S^-1 rhs (NaN when a pivot was not positive), usec5 = {factorisation with the forward substitution riding along, backward
  * substitution, then the factorisation as thread 0 sees it: panels, diagonal block + trailing update, barrier wait}: microseconds inside the kernel, mean over `reps` repetitions, with `blocks` identical workgroups side by side.  blocks = -1 .. -6
  * select the timing micro-modes of tools/chol_bench.py (one diagonal tile, panel tiles, dependent FP64 chains, v_mfma_f64_16x16x4 issue
- * rates; usec5 then carries clock64 ticks / 100 in slots 1 .. 4, L_out / x_out are not written): measurement only, see stage_linalg.hip. */
+ * rates; usec5 then carries clock64 ticks / 100 in slots 1 .. 4, L_out / x_out are not written): measurement only, see stage_linalg.hip.  blocks = -8 / -9:
+ * the HBM fallback of be_solve instead (chol_blocked + chol_solve_blocked, 1024 / 512 threads, nb <= 21, reps ignored, usec5 not written). */
 int vio_stage_chol(int nb, int reps, int blocks, const double *S, const double *rhs, double *L_out, double *x_out, double *usec5);
 /* Harness of the HBM-resident symmetric eigen-solver of the literal marginalisation (marg_exact = 1, blocks beyond the LDS-resident size: Householder
  * tridiagonalisation + implicit QL by one workgroup, be_linalg.h sym_eig_hbm; Eigen::SelfAdjointEigenSolver at marginalization_factor.cpp:281, :298 is
  * what it stands in for).  A: symmetric n x n, row-major, 2 <= n <= 512.  evals[n] unsorted, evecs[i * n + k] = component i of the eigenvector of
  * evals[k], usec (may be NULL; FOUR doubles) = device time of the decomposition and of its tridiagonalisation / accumulation / QL phases. */
 int vio_stage_sym_eig(int n, const double *A, double *evals, double *evecs, double *usec);
+/* Harnesses of the other dense primitives of be_linalg.h (stage_linalg.hip), each called directly by one workgroup; VIO_EINVAL for arguments the routine
+ * does not support.  Eigenvectors out as in vio_stage_sym_eig: evecs[i * n + k] = component i of the eigenvector of evals[k] (unsorted).
+ * vio_stage_jacobi: mode 0 = jacobi_small (thread 0, n <= 16, A / V in LDS), 1 = jacobi_block (A / V in LDS for n <= 96, in HBM beyond, n <= 256),
+ * 2 = jacobi_wave16 (wavefront 0, n <= 16, LDS), 3 = jacobi_block with A / V in HBM (as marg_exact runs it).  nt = threads of the workgroup (a
+ * multiple of 64, <= 1024).  sweeps_out (may be NULL) = sweeps the routine ran, 0 for mode 0 (jacobi_small does not report them). */
+int vio_stage_jacobi(int mode, int n, int nt, const double *A, double *evals, double *evecs, int *sweeps_out);
+/* sym_eig_tridiag (one_wave) or sym_eig_tridiag_mt, then tridiag_ql_wave, exactly as be_prior_factor_kernel calls them (512 threads; the matrix in
+ * LDS with leading dimension n | 1, or in HBM with n when in_hbm).  1 <= n <= 128.  Only the lower triangle of A is read. */
+int vio_stage_sym_eig_lds(int n, int one_wave, int in_hbm, const double *A, double *evals, double *evecs);
+/* spd_inverse_wave16 (n <= 16, wavefront 0 of a 512-thread workgroup): ok_out = the routine's result (factorisation succeeded and the eigenvalues are
+ * certified above floor), Ainv = A^-1 when ok_out is 1, NaN otherwise. */
+int vio_stage_spd_inverse16(int n, double floor, const double *A, double *Ainv, int *ok_out);
+/* block_scan_flags on flags[n] (0 / 1) with nt threads (a multiple of 64, <= 1024): offs = exclusive prefix sums, total_out[0] = the total.  skew & 3:
+ * 1 / 2 = thread 0 / the last thread starts the scan a few microseconds late; skew & 4: the flags are written just before the call by other threads
+ * behind a barrier, as the callers do; skew & 8: two scans back to back on the same scratch, the second into offs[n .. 2 n) (offs holds 2 n) and its
+ * total into total_out[1].  total_out[2] = 1 if the LDS words after the routine's 2 nt + 2 scratch ints kept their values.  total_out: 3 ints. */
+int vio_stage_scan_flags(int n, int nt, int skew, const int *flags, int *offs, int *total_out);
+/* The landmark Schur complement of be_solve: S = S_p H S_p + mu diag(dgp^2) - sum_k inv[k] (S_p Ws[k])^T (S_p Ws[k]) on its lower 16 x 16 tiles, n = 16 nb
+ * (nb <= 21), H n x n and Ws Kpad x n row-major (Kpad a multiple of 4), S_p = diag(sp); a column with sp = 0 becomes an identity row.  variant 0 =
+ * schur_mfma (S in HBM), 1 = schur_mfma_lds, 2 = schur_mfma_staged<9> with column-tile mask colmask (bit c: column tile c of Ws may be non-zero;
+ * only where be_solve would stage, schur_staged_ok), both in an LDS tile region of be_solve's size followed by guard words (guard_ok = 1 if they
+ * survived) and untiled into S_out.  nt threads.  S_out: only the lower tiles are written (diagonal tiles whole). */
+int vio_stage_schur(int variant, int nb, int nt, int Kpad, unsigned colmask, const double *H, const double *Ws, const double *inv, const double *dgp,
+                    const double *sp, double mu, double *S_out, int *guard_ok);
+/* be_marg's truncated pseudo-inverse (be_linalg.h marg_pinv15, n <= 15): Pinv of the symmetrised A with eigenvalues <= 1e-8 dropped; path_out = 0 if
+ * the certified inverse served (every eigenvalue provably above 1e-6), 1 if the Jacobi eigen-decomposition did. */
+int vio_stage_pinv15(int n, const double *A, double *Pinv, int *path_out);
 
 #ifdef __cplusplus
 }

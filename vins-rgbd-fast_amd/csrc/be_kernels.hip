@@ -1895,8 +1895,7 @@ __device__ __forceinline__ void solve_body(const Batch &B, int s, int *scratch, 
     __shared__ double chol_dinv[VIO_LWMAX];  // reciprocal Cholesky diagonal (LDS-tile path)
     const bool tiles_in_lds = ((LW >> 4) * ((LW >> 4) + 1) / 2) * 256 <= 16896 && !(B.flags & 1);  // S as 66 lower tiles = 132 KB for W = 10
     // column-aware Schur staging (schur_mfma_staged) and two-range Hpl mat-vecs in use: see assemble() / the solver loop
-    const bool schur_staged = tiles_in_lds && ((LW >> 4) * ((LW >> 4) + 1) / 2) <= 9 * (nt >> 6) &&
-                              2 * SCH_CH * (LW + 8) + 64 <= ((LW >> 4) * ((LW >> 4) + 1) / 2) * 256 && (LW >> 4) <= 32;
+    const bool schur_staged = tiles_in_lds && schur_staged_ok(LW, nt);
     const bool hpl_sparse = schur_staged && 6 * W1 + 7 <= 128;
 
     PH_INIT;
@@ -2819,7 +2818,7 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
     __syncthreads();
     // Pseudo-inverse with the eigenvalues <= 1e-8 dropped.  Fast path: when a Cholesky factorisation proves every eigenvalue above 1e-6
     // (lambda_min >= 1 / |A^-1|_F) nothing is dropped and the pseudo-inverse is the inverse, a few microseconds of one wavefront instead
-    // of ~100 Jacobi rounds; otherwise the eigen-decomposition decides.
+    // of ~100 Jacobi rounds; otherwise the eigen-decomposition decides.  Kept identical to be_linalg.h marg_pinv15 (its harness and tests).
     __shared__ int pinv_direct;
     __shared__ double L15[225];
     if (t < 64) {

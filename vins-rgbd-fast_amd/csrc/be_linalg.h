@@ -356,6 +356,36 @@ __device__ bool spd_inverse_wave16(const double *A, int n, double floor, double 
     return isfinite(fro) && fro > 0.0 && 1.0 / sqrt(fro) > floor;
 }
 
+// be_marg's truncated pseudo-inverse of the md x md block (md <= 15) in the leading corner of A (mq x mq, not necessarily symmetric):
+// Pinv = V diag(1 / lambda if lambda > eps else 0) V^T of the symmetrised block (marginalization_factor.cpp:281-291).  Fast path: when a
+// Cholesky factorisation proves every eigenvalue above 1e-6 (lambda_min >= 1 / |A^-1|_F) nothing is dropped and the pseudo-inverse is the
+// inverse, a few microseconds of one wavefront instead of ~100 Jacobi rounds; otherwise the eigen-decomposition (jacobi_wave16) decides.
+// A15 / V15 / L15 / Pinv: 225 doubles of LDS each, cs / sn / pp / qq: the Jacobi pairing arrays; *sh_direct (LDS) = 1 if the fast path
+// served.  All threads of the block call it; it ends with a barrier.  be_marg_kernel runs these same statements inline (be_kernels.hip, "eliminate
+// the m-block"): calling this function from there costs be_marg 51 spilled VGPRs, so the two must be kept identical by hand.
+__device__ __forceinline__ void marg_pinv15(const double *A, int mq, int md, double eps, double *A15, double *V15, double *L15, double *Pinv,
+                                            double *cs, double *sn, int *pp, int *qq, int *sh_direct) {
+    const int t = threadIdx.x, nt = blockDim.x;
+    for (int w = t; w < md * md; w += nt) { int i = w / md, j = w - i * md; A15[w] = 0.5 * (A[i * mq + j] + A[j * mq + i]); }
+    __syncthreads();
+    if (t < 64) {
+        const bool okc = spd_inverse_wave16(A15, md, 1e-6, L15, V15, Pinv);
+        if (t == 0) *sh_direct = okc ? 1 : 0;
+    }
+    __syncthreads();
+    if (!*sh_direct) {
+        if (t < 64) jacobi_wave16(A15, V15, md, md, cs, sn, pp, qq);   // md <= 15: one wavefront, no workgroup barriers inside
+        __syncthreads();
+        for (int w = t; w < md * md; w += nt) {
+            int i = w / md, j = w - i * md;
+            double sacc = 0;
+            for (int k = 0; k < md; k++) { double ev = A15[k * md + k]; if (ev > eps) sacc += V15[i * md + k] * V15[j * md + k] / ev; }
+            Pinv[w] = sacc;
+        }
+        __syncthreads();
+    }
+}
+
 // Symmetric eigen-decomposition (Householder tridiagonalisation + implicit-shift QL, the algorithm class of
 // Eigen::SelfAdjointEigenSolver used at marginalization_factor.cpp:277,298).  V (n x n, ld) holds A on entry (lower
 // triangle is read) and the eigenvectors (columns) on exit; d = eigenvalues (unsorted), e / gtmp = workspaces; all in LDS.
@@ -1034,6 +1064,14 @@ __device__ __forceinline__ void schur_mfma_lds(const double *Hs, const double *W
     __syncthreads();
 }
 
+#define SCH_CH 16
+// be_solve's condition for schur_mfma_staged<9> on n = LW columns with nt threads (given that the tiles live in LDS): every wavefront holds at
+// most 9 tiles, the two staged chunks and the tile order fit the tile region, the column mask fits 32 bits
+__host__ __device__ __forceinline__ bool schur_staged_ok(int n, int nt) {
+    const int nb = n >> 4, ntile = nb * (nb + 1) / 2;
+    return ntile <= 9 * (nt >> 6) && 2 * SCH_CH * (n + 8) + 64 <= ntile * 256 && nb <= 32;
+}
+
 // Same Schur complement, landmark rows staged through LDS once: every wavefront keeps the accumulators of its (<= MAXT)
 // tiles in registers for the whole k loop, the 16-row chunks of Hpl (scaled by sp on the way in) are double-buffered in the
 // tile region itself (it is only written at the end).  Global traffic drops from 2 * ntile * Kpad * 16 doubles (every
@@ -1042,7 +1080,6 @@ __device__ __forceinline__ void schur_mfma_lds(const double *Hs, const double *W
 // speed-bias columns (more than half of the row) are identically zero: tiles with an all-zero panel keep their H values and get no
 // MFMAs, their columns are not staged, and the active tiles are dealt round-robin over the wavefronts so that the work stays
 // balanced.  Skipping them is exact (they would only add zeros).
-#define SCH_CH 16
 template <int MAXT>
 __device__ __forceinline__ void schur_mfma_staged(const double *Hs, const double *Ws, const double *inv, const double *dgp, const double *sp, double mu,
                                   int Kpad, int n, int ld, double *T, unsigned colmask) {

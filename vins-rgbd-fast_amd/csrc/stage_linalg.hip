@@ -234,13 +234,16 @@ done:
     return rc;
 }
 
+static int stage_chol_blocked(int nb, int nt, const double *S, const double *rhs, double *L_out, double *x_out);
+
 // S: [16 nb][16 nb] row-major symmetric positive definite, rhs: [16 nb].  L_out (row-major, lower triangle written, the rest left as
 // passed in), x_out = S^-1 rhs, usec5 = {factorisation + forward substitution, backward substitution, and of the factorisation as
 // thread 0 sees it: panel phases, diagonal block + trailing update, barrier wait} in microseconds of one workgroup (mean over reps;
 // `blocks` identical workgroups run side by side).
 extern "C" int vio_stage_chol(int nb, int reps, int blocks, const double *S, const double *rhs, double *L_out, double *x_out, double *usec5) {
     double *usec2 = usec5;
-    if (nb < 1 || nb > 24 || reps < 1 || blocks == 0 || blocks < -7 || !S || !rhs || !L_out || !x_out) return VIO_EINVAL;
+    if (nb < 1 || nb > 24 || reps < 1 || blocks == 0 || blocks < -9 || !S || !rhs || !L_out || !x_out) return VIO_EINVAL;
+    if (blocks <= -8) return nb <= 21 ? stage_chol_blocked(nb, blocks == -8 ? 1024 : 512, S, rhs, L_out, x_out) : VIO_EINVAL;
     if (nb > 11 && blocks < 0 && blocks != -7) return VIO_EINVAL;
     int rc = VIO_OK;
     if (nb > 11 || blocks == -7) return stage_chol_stream(nb, reps, blocks, S, rhs, L_out, x_out, usec5);
@@ -262,5 +265,312 @@ extern "C" int vio_stage_chol(int nb, int reps, int blocks, const double *S, con
     if (usec2) for (int k = 0; k < 5; k++) usec2[k] = ht[k] / (rate_khz * 1e-3);
 done:
     if (dS) (void)hipFree(dS); if (dr) (void)hipFree(dr); if (dL) (void)hipFree(dL); if (dx) (void)hipFree(dx); if (dt) (void)hipFree(dt);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- ABI 9: the remaining primitives
+// One workgroup each, the be_linalg.h routine called directly (no restatement), at the block size of its production call site unless the entry takes
+// one.  Eigenvector arrays out: evecs[i * n + k] = component i of the eigenvector of evals[k] (the convention of vio_stage_sym_eig).
+#define JAC_LDS_MAX 96    // jacobi_block with A and V in LDS (2 n^2 doubles); beyond, in HBM as marg_exact runs it
+#define JAC_HBM_MAX 256   // cs / sn / pp / qq below hold n / 2 + 1 entries
+namespace {
+__global__ __launch_bounds__(1024) void be_stage_jacobi_kernel(int mode, int n, double *Ag, double *Vg, int *sweeps) {
+    extern __shared__ __attribute__((aligned(16))) double jl[];
+    __shared__ double cs[JAC_HBM_MAX / 2 + 1], sn[JAC_HBM_MAX / 2 + 1], sred[64];
+    __shared__ int pp[JAC_HBM_MAX / 2 + 1], qq[JAC_HBM_MAX / 2 + 1], sw;
+    const int t = threadIdx.x, nt = blockDim.x;
+    const bool hbm = mode == 3 || (mode == 1 && n > JAC_LDS_MAX);
+    double *A = hbm ? Ag : jl, *V = hbm ? Vg : jl + (size_t)n * n;
+    if (!hbm) for (int w = t; w < n * n; w += nt) A[w] = Ag[w];
+    if (t == 0) sw = 0;
+    __syncthreads();
+    if (mode == 0) { if (t == 0) jacobi_small(A, V, n); }
+    else if (mode == 2) { if (t < 64) { const int s = jacobi_wave16(A, V, n, n, cs, sn, pp, qq); if (t == 0) sw = s; } }
+    else { const int s = jacobi_block(A, V, n, n, cs, sn, pp, qq, sred); if (t == 0) sw = s; }
+    __syncthreads();
+    if (!hbm) for (int w = t; w < n * n; w += nt) { Ag[w] = A[w]; Vg[w] = V[w]; }
+    if (t == 0) *sweeps = sw;
+}
+
+// sym_eig_tridiag / sym_eig_tridiag_mt + tridiag_ql_wave with be_prior_factor_kernel's layout: LDS with leading dimension n | 1, or HBM with n, and
+// one call site per address space
+__global__ __launch_bounds__(512) void be_stage_sym_eig_lds_kernel(int n, int one_wave, int in_hbm, const double *A, double *Ag, double *evals, double *evecs) {
+    const int t = threadIdx.x, nt = blockDim.x;
+    __shared__ double sred[64];
+    extern __shared__ __attribute__((aligned(16))) double se_lds[];
+    const bool in_lds = !in_hbm;
+    const int ldj = in_lds ? (n | 1) : n;
+    double *As = in_lds ? se_lds : Ag;
+    for (int w = t; w < n * n; w += nt) { int i = w / n, j = w - i * n; As[i * ldj + j] = A[w]; }
+    __syncthreads();
+    __shared__ double ev_d[6 * VIO_MAXW + 16], ev_e[6 * VIO_MAXW + 16], ev_g[6 * VIO_MAXW + 16];
+    __shared__ double ev_part[8 * EIG_LD];
+    if (in_lds) {
+        double *Al = se_lds;
+        if (!one_wave) sym_eig_tridiag_mt(Al, n, ldj, ev_d, ev_e, ev_g, ev_part);
+        else sym_eig_tridiag(Al, n, ldj, ev_d, ev_e, ev_g, sred);
+        tridiag_ql_wave(Al, n, ldj, ev_d, ev_e);
+    } else {
+        double *Ag2 = Ag;
+        if (!one_wave) sym_eig_tridiag_mt(Ag2, n, ldj, ev_d, ev_e, ev_g, ev_part);
+        else sym_eig_tridiag(Ag2, n, ldj, ev_d, ev_e, ev_g, sred);
+        tridiag_ql_wave(Ag2, n, ldj, ev_d, ev_e);
+    }
+    for (int k = t; k < n; k += nt) evals[k] = ev_d[k];
+    for (int w = t; w < n * n; w += nt) { int i = w / n, k = w - i * n; evecs[w] = As[i * ldj + k]; }
+}
+
+// spd_inverse_wave16 by wavefront 0 of a be_marg-sized workgroup; Ainv stays NaN where the routine does not write it
+__global__ __launch_bounds__(512) void be_stage_spd_inv_kernel(int n, double floor, const double *A, double *Ainv, int *ok) {
+    const int t = threadIdx.x, nt = blockDim.x;
+    __shared__ double Al[256], L[256], Li[256], Ai[256];
+    for (int w = t; w < 256; w += nt) { Al[w] = w < n * n ? A[w] : 0.0; Ai[w] = nan(""); }
+    __syncthreads();
+    if (t < 64) { const bool okc = spd_inverse_wave16(Al, n, floor, L, Li, Ai); if (t == 0) *ok = okc ? 1 : 0; }
+    __syncthreads();
+    for (int w = t; w < n * n; w += nt) Ainv[w] = Ai[w];
+}
+
+// block_scan_flags with one thread late (skew & 3: 1 = thread 0, 2 = the last thread, a few microseconds of wall_clock64 as PH() costs in the timers
+// build), the flags written just before by other threads behind a barrier as the callers do (skew & 4: thread t writes the flags k = nt - 1 - t
+// mod nt, all of them in other threads' chunks), and two scans back to back on the same scratch (skew & 8: the second result goes to offs + n).
+// The scratch words beyond the 2 nt + 2 the routine may use are guards; guard_ok = 0 if one changed.
+#define SCAN_GUARDS 16
+__global__ __launch_bounds__(1024) void be_stage_scan_kernel(int n, int skew, const int *src, int *flags, int *offs, int *total, int *guard_ok) {
+    const int t = threadIdx.x, nt = blockDim.x;
+    __shared__ int scratch[2 * 1024 + 2 + SCAN_GUARDS];
+    const int g0 = 2 * nt + 2;
+    for (int k = t; k < SCAN_GUARDS; k += nt) scratch[g0 + k] = 0x5ca1ab1e ^ k;
+    if (skew & 4) {
+        for (int k = nt - 1 - t; k < n; k += nt) flags[k] = src[k];
+        __syncthreads();
+    }
+    const bool late = ((skew & 3) == 1 && t == 0) || ((skew & 3) == 2 && t == nt - 1);
+    if (late) { const long long c0 = (long long)wall_clock64(); while ((long long)wall_clock64() - c0 < 500) {} }
+    const int tot = block_scan_flags(flags, n, offs, scratch);
+    int tot2 = tot;
+    if (skew & 8) {
+        if (late) { const long long c0 = (long long)wall_clock64(); while ((long long)wall_clock64() - c0 < 500) {} }
+        tot2 = block_scan_flags(flags, n, offs + n, scratch);
+    }
+    if (t == 0) { total[0] = tot; total[1] = tot2; }
+    __syncthreads();
+    if (t == 0) {
+        int good = 1;
+        for (int k = 0; k < SCAN_GUARDS; k++) if (scratch[g0 + k] != (0x5ca1ab1e ^ k)) good = 0;
+        *guard_ok = good;
+    }
+}
+
+// chol_blocked + chol_solve_blocked on a matrix in HBM (be_solve when the Schur complement does not fit LDS), 16 x 16 diagonal block in LDS as there
+__global__ __launch_bounds__(1024) void be_stage_chol_blocked_kernel(int n, double *A, const double *rhs, double *xout) {
+    const int t = threadIdx.x, nt = blockDim.x;
+    __shared__ double Lpp[256];
+    __shared__ int flag;
+    extern __shared__ __attribute__((aligned(16))) double cb_xs[];
+    for (int q = t; q < n; q += nt) cb_xs[q] = rhs[q];
+    __syncthreads();
+    const bool ok = chol_blocked(A, n, n, &flag, Lpp);
+    if (ok) chol_solve_blocked(A, n, n, cb_xs, Lpp);
+    __syncthreads();
+    for (int q = t; q < n; q += nt) xout[q] = ok ? cb_xs[q] : nan("");
+}
+}  // namespace
+
+// dynamic LDS the kernel can still get: the per-block maximum less its static arrays
+static int stage_lds_cap(const void *kernel) {
+    int cap = 0, dev = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || cap <= 0) cap = 64 * 1024;
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) return 0;
+    return cap - (int)fa.sharedSizeBytes;
+}
+
+extern "C" int vio_stage_jacobi(int mode, int n, int nt, const double *A, double *evals, double *evecs, int *sweeps_out) {
+    if (mode < 0 || mode > 3 || n < 1 || !A || !evals || !evecs || nt < 64 || nt > 1024 || (nt & 63)) return VIO_EINVAL;
+    if ((mode == 0 || mode == 2) && n > 16) return VIO_EINVAL;
+    if (n > JAC_HBM_MAX) return VIO_EINVAL;
+    const bool hbm = mode == 3 || (mode == 1 && n > JAC_LDS_MAX);
+    int rc = VIO_OK, hs = 0;
+    const size_t nn = (size_t)n * n, lds = hbm ? 0 : 2 * nn * sizeof(double);
+    double *dA = nullptr, *dV = nullptr;
+    int *ds = nullptr;
+    std::vector<double> hA(nn);
+    if ((long)lds > (long)stage_lds_cap((const void *)be_stage_jacobi_kernel)) return VIO_EINVAL;
+    ST_CHK(hipMalloc((void **)&dA, nn * 8)); ST_CHK(hipMalloc((void **)&dV, nn * 8)); ST_CHK(hipMalloc((void **)&ds, 4));
+    ST_CHK(hipMemcpy(dA, A, nn * 8, hipMemcpyHostToDevice));
+    if (lds) ST_CHK(hipFuncSetAttribute((const void *)be_stage_jacobi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    be_stage_jacobi_kernel<<<1, nt, lds>>>(mode, n, dA, dV, ds);
+    ST_CHK(hipDeviceSynchronize());
+    ST_CHK(hipMemcpy(hA.data(), dA, nn * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(evecs, dV, nn * 8, hipMemcpyDeviceToHost));
+    ST_CHK(hipMemcpy(&hs, ds, 4, hipMemcpyDeviceToHost));
+    for (int k = 0; k < n; k++) evals[k] = hA[(size_t)k * n + k];
+    if (sweeps_out) *sweeps_out = mode == 0 ? 0 : hs;
+done:
+    if (dA) (void)hipFree(dA); if (dV) (void)hipFree(dV); if (ds) (void)hipFree(ds);
+    return rc;
+}
+
+extern "C" int vio_stage_sym_eig_lds(int n, int one_wave, int in_hbm, const double *A, double *evals, double *evecs) {
+    if (n < 1 || n > 128 || !A || !evals || !evecs) return VIO_EINVAL;
+    int rc = VIO_OK;
+    const size_t nn = (size_t)n * n, lds = in_hbm ? 0 : (size_t)n * (n | 1) * sizeof(double);
+    double *dA = nullptr, *dG = nullptr, *dw = nullptr, *dV = nullptr;
+    ST_CHK(hipMalloc((void **)&dA, nn * 8)); ST_CHK(hipMalloc((void **)&dG, nn * 8)); ST_CHK(hipMalloc((void **)&dw, (size_t)n * 8));
+    ST_CHK(hipMalloc((void **)&dV, nn * 8));
+    ST_CHK(hipMemcpy(dA, A, nn * 8, hipMemcpyHostToDevice));
+    if (lds) ST_CHK(hipFuncSetAttribute((const void *)be_stage_sym_eig_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    be_stage_sym_eig_lds_kernel<<<1, 512, lds>>>(n, one_wave ? 1 : 0, in_hbm ? 1 : 0, dA, dG, dw, dV);
+    ST_CHK(hipDeviceSynchronize());
+    ST_CHK(hipMemcpy(evals, dw, (size_t)n * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(evecs, dV, nn * 8, hipMemcpyDeviceToHost));
+done:
+    if (dA) (void)hipFree(dA); if (dG) (void)hipFree(dG); if (dw) (void)hipFree(dw); if (dV) (void)hipFree(dV);
+    return rc;
+}
+
+extern "C" int vio_stage_spd_inverse16(int n, double floor, const double *A, double *Ainv, int *ok_out) {
+    if (n < 1 || n > 16 || !A || !Ainv || !ok_out) return VIO_EINVAL;
+    int rc = VIO_OK;
+    const size_t nn = (size_t)n * n;
+    double *dA = nullptr, *dI = nullptr;
+    int *dok = nullptr;
+    ST_CHK(hipMalloc((void **)&dA, nn * 8)); ST_CHK(hipMalloc((void **)&dI, nn * 8)); ST_CHK(hipMalloc((void **)&dok, 4));
+    ST_CHK(hipMemcpy(dA, A, nn * 8, hipMemcpyHostToDevice));
+    be_stage_spd_inv_kernel<<<1, 512>>>(n, floor, dA, dI, dok);
+    ST_CHK(hipDeviceSynchronize());
+    ST_CHK(hipMemcpy(Ainv, dI, nn * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(ok_out, dok, 4, hipMemcpyDeviceToHost));
+done:
+    if (dA) (void)hipFree(dA); if (dI) (void)hipFree(dI); if (dok) (void)hipFree(dok);
+    return rc;
+}
+
+extern "C" int vio_stage_scan_flags(int n, int nt, int skew, const int *flags, int *offs, int *total_out) {
+    if (n < 0 || n > (1 << 20) || nt < 64 || nt > 1024 || (nt & 63) || skew < 0 || skew > 15 || (n > 0 && (!flags || !offs)) || !total_out) return VIO_EINVAL;
+    int rc = VIO_OK;
+    const size_t nb = (size_t)(n > 0 ? n : 1) * 4;
+    const int nout = (skew & 8) ? 2 : 1;
+    int *dsrc = nullptr, *dfl = nullptr, *doffs = nullptr, *dtot = nullptr, htot[3] = {0, 0, 0};
+    ST_CHK(hipMalloc((void **)&dsrc, nb)); ST_CHK(hipMalloc((void **)&dfl, nb)); ST_CHK(hipMalloc((void **)&doffs, nb * nout));
+    ST_CHK(hipMalloc((void **)&dtot, 12));
+    if (n > 0) {
+        ST_CHK(hipMemcpy(dsrc, flags, (size_t)n * 4, hipMemcpyHostToDevice));
+        if (skew & 4) ST_CHK(hipMemset(dfl, 0xff, (size_t)n * 4));   // (whatever the flags held before the writers ran)
+        else ST_CHK(hipMemcpy(dfl, flags, (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    be_stage_scan_kernel<<<1, nt>>>(n, skew, dsrc, dfl, doffs, dtot, dtot + 2);
+    ST_CHK(hipDeviceSynchronize());
+    if (n > 0) ST_CHK(hipMemcpy(offs, doffs, (size_t)n * 4 * nout, hipMemcpyDeviceToHost));
+    ST_CHK(hipMemcpy(htot, dtot, 12, hipMemcpyDeviceToHost));
+    total_out[0] = htot[0]; total_out[1] = htot[1]; total_out[2] = htot[2];
+done:
+    if (dsrc) (void)hipFree(dsrc); if (dfl) (void)hipFree(dfl); if (doffs) (void)hipFree(doffs); if (dtot) (void)hipFree(dtot);
+    return rc;
+}
+
+// blocks = -8 / -9 of vio_stage_chol: chol_blocked + chol_solve_blocked at be_solve_kernel's 1024 / be_solve_kernel_512's 512 threads
+static int stage_chol_blocked(int nb, int nt, const double *S, const double *rhs, double *L_out, double *x_out) {
+    int rc = VIO_OK;
+    const size_t n = 16 * (size_t)nb;
+    double *dA = nullptr, *dr = nullptr, *dx = nullptr;
+    std::vector<double> hA(n * n);
+    ST_CHK(hipMalloc((void **)&dA, n * n * 8)); ST_CHK(hipMalloc((void **)&dr, n * 8)); ST_CHK(hipMalloc((void **)&dx, n * 8));
+    ST_CHK(hipMemcpy(dA, S, n * n * 8, hipMemcpyHostToDevice)); ST_CHK(hipMemcpy(dr, rhs, n * 8, hipMemcpyHostToDevice));
+    be_stage_chol_blocked_kernel<<<1, nt, n * sizeof(double)>>>((int)n, dA, dr, dx);
+    ST_CHK(hipDeviceSynchronize());
+    ST_CHK(hipMemcpy(hA.data(), dA, n * n * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(x_out, dx, n * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) for (size_t j = 0; j <= i; j++) L_out[i * n + j] = hA[i * n + j];
+done:
+    if (dA) (void)hipFree(dA); if (dr) (void)hipFree(dr); if (dx) (void)hipFree(dx);
+    return rc;
+}
+
+// ---- the landmark Schur complement (be_solve, solve_mode 0) and be_marg's truncated pseudo-inverse
+#define SCHUR_GUARDS 64
+namespace {
+// variant 0: schur_mfma into S in HBM; 1: schur_mfma_lds, 2: schur_mfma_staged<9> into the LDS tile region of be_solve's size (ntile * 256 doubles),
+// followed by SCHUR_GUARDS guard words; the lower tiles are untiled into S on the way out
+__global__ __launch_bounds__(1024) void be_stage_schur_kernel(int variant, int n, int Kpad, unsigned colmask, const double *H, const double *Ws, const double *inv,
+                                                              const double *dgp, const double *sp, double mu, double *S, int *guard_ok) {
+    extern __shared__ __attribute__((aligned(16))) double sc_T[];
+    const int t = threadIdx.x, nt = blockDim.x, nb = n >> 4, ntile = nb * (nb + 1) / 2;
+    const double gval = -1.2345678901234567e300;
+    if (variant == 0) { schur_mfma(H, Ws, inv, dgp, sp, mu, Kpad, n, n, S); if (t == 0) *guard_ok = 1; return; }
+    double *guard = sc_T + (size_t)ntile * 256;
+    for (int q = t; q < SCHUR_GUARDS; q += nt) guard[q] = gval;
+    __syncthreads();
+    if (variant == 1) schur_mfma_lds(H, Ws, inv, dgp, sp, mu, Kpad, n, n, sc_T);
+    else schur_mfma_staged<9>(H, Ws, inv, dgp, sp, mu, Kpad, n, n, sc_T, colmask);
+    for (int q = t; q < ntile * 256; q += nt) {
+        int ti, tj;
+        tri_decode(q >> 8, ti, tj);
+        const int r = (q >> 4) & 15, c = q & 15;
+        S[(size_t)(16 * ti + r) * n + 16 * tj + c] = sc_T[tl_idx(ti, tj, r, c)];
+    }
+    __syncthreads();
+    if (t == 0) {
+        int good = 1;
+        for (int q = 0; q < SCHUR_GUARDS; q++) if (guard[q] != gval) good = 0;
+        *guard_ok = good;
+    }
+}
+
+// marg_pinv15 as be_marg calls it (512 threads, the same LDS arrays)
+__global__ __launch_bounds__(512) void be_stage_pinv15_kernel(int md, const double *A, double *Pout, int *path) {
+    const int t = threadIdx.x, nt = blockDim.x;
+    __shared__ double cs[VIO_MAXW * 3 + 10], sn[VIO_MAXW * 3 + 10];
+    __shared__ int pp[VIO_MAXW * 3 + 10], qq[VIO_MAXW * 3 + 10];
+    __shared__ double A15[225], V15[225], Pinv[225], L15[225], Am[225];
+    __shared__ int pinv_direct;
+    for (int w = t; w < md * md; w += nt) Am[w] = A[w];
+    __syncthreads();
+    marg_pinv15(Am, md, md, 1e-8, A15, V15, L15, Pinv, cs, sn, pp, qq, &pinv_direct);
+    for (int w = t; w < md * md; w += nt) Pout[w] = Pinv[w];
+    if (t == 0) *path = pinv_direct ? 0 : 1;
+}
+}  // namespace
+
+extern "C" int vio_stage_schur(int variant, int nb, int nt, int Kpad, unsigned colmask, const double *H, const double *Ws, const double *inv, const double *dgp,
+                               const double *sp, double mu, double *S_out, int *guard_ok) {
+    if (variant < 0 || variant > 2 || nb < 1 || nb > VIO_LWMAX / 16 || nt < 64 || nt > 1024 || (nt & 63) || Kpad < 0 || (Kpad & 3) || Kpad > 4096 ||
+        !H || !S_out || !guard_ok || !dgp || !sp || (Kpad > 0 && (!Ws || !inv)))
+        return VIO_EINVAL;
+    const int n = 16 * nb, ntile = nb * (nb + 1) / 2;
+    if (variant >= 1 && ntile * 256 > 16896) return VIO_EINVAL;                  // be_solve's tiles_in_lds
+    if (variant == 2 && !schur_staged_ok(n, nt)) return VIO_EINVAL;
+    int rc = VIO_OK, hg = 0;
+    const size_t nn = (size_t)n * n, kw = (size_t)(Kpad > 0 ? Kpad : 1) * n, lds = variant ? ((size_t)ntile * 256 + SCHUR_GUARDS) * sizeof(double) : 0;
+    double *dH = nullptr, *dW = nullptr, *di = nullptr, *dd = nullptr, *ds = nullptr, *dS = nullptr;
+    int *dg = nullptr;
+    ST_CHK(hipMalloc((void **)&dH, nn * 8)); ST_CHK(hipMalloc((void **)&dW, kw * 8)); ST_CHK(hipMalloc((void **)&di, (size_t)(Kpad + 1) * 8));
+    ST_CHK(hipMalloc((void **)&dd, (size_t)n * 8)); ST_CHK(hipMalloc((void **)&ds, (size_t)n * 8)); ST_CHK(hipMalloc((void **)&dS, nn * 8));
+    ST_CHK(hipMalloc((void **)&dg, 4));
+    ST_CHK(hipMemcpy(dH, H, nn * 8, hipMemcpyHostToDevice)); ST_CHK(hipMemcpy(dS, S_out, nn * 8, hipMemcpyHostToDevice));
+    if (Kpad > 0) { ST_CHK(hipMemcpy(dW, Ws, (size_t)Kpad * n * 8, hipMemcpyHostToDevice)); ST_CHK(hipMemcpy(di, inv, (size_t)Kpad * 8, hipMemcpyHostToDevice)); }
+    ST_CHK(hipMemcpy(dd, dgp, (size_t)n * 8, hipMemcpyHostToDevice)); ST_CHK(hipMemcpy(ds, sp, (size_t)n * 8, hipMemcpyHostToDevice));
+    if (lds) ST_CHK(hipFuncSetAttribute((const void *)be_stage_schur_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    be_stage_schur_kernel<<<1, nt, lds>>>(variant, n, Kpad, colmask, dH, dW, di, dd, ds, mu, dS, dg);
+    ST_CHK(hipDeviceSynchronize());
+    ST_CHK(hipMemcpy(S_out, dS, nn * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(&hg, dg, 4, hipMemcpyDeviceToHost));
+    *guard_ok = hg;
+done:
+    if (dH) (void)hipFree(dH); if (dW) (void)hipFree(dW); if (di) (void)hipFree(di); if (dd) (void)hipFree(dd); if (ds) (void)hipFree(ds);
+    if (dS) (void)hipFree(dS); if (dg) (void)hipFree(dg);
+    return rc;
+}
+
+extern "C" int vio_stage_pinv15(int n, const double *A, double *Pinv, int *path_out) {
+    if (n < 1 || n > 15 || !A || !Pinv || !path_out) return VIO_EINVAL;
+    int rc = VIO_OK;
+    const size_t nn = (size_t)n * n;
+    double *dA = nullptr, *dP = nullptr;
+    int *dp = nullptr;
+    ST_CHK(hipMalloc((void **)&dA, nn * 8)); ST_CHK(hipMalloc((void **)&dP, nn * 8)); ST_CHK(hipMalloc((void **)&dp, 4));
+    ST_CHK(hipMemcpy(dA, A, nn * 8, hipMemcpyHostToDevice));
+    be_stage_pinv15_kernel<<<1, 512>>>(n, dA, dP, dp);
+    ST_CHK(hipDeviceSynchronize());
+    ST_CHK(hipMemcpy(Pinv, dP, nn * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(path_out, dp, 4, hipMemcpyDeviceToHost));
+done:
+    if (dA) (void)hipFree(dA); if (dP) (void)hipFree(dP); if (dp) (void)hipFree(dp);
     return rc;
 }
