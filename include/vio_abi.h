@@ -101,6 +101,19 @@ enum { VIO_QUIRK_LATEST_FRONT = 1,
 
 typedef struct vio_batch vio_batch; /* opaque */
 
+/* Per-sequence calibration (ABI 10): the fields of vio_config that describe ONE sensor rig.  Every sequence of a handle has its own copy;
+ * vio_create gives every slot vio_calibration_from_config(cfg), vio_set_calibration replaces one.  All other vio_config fields stay
+ * handle-wide because they size buffers or select code paths: image size, grid, max_cnt, min_dist, window, landmark capacity, use_imu,
+ * dynamic_init, estimate_extrinsic, estimate_td, marg_exact, equalize, fix_depth, focal_length (FOCAL_LENGTH is a constant upstream,
+ * parameters.h:11), the depth range, thresholds and quirk bits. */
+typedef struct vio_calibration {
+    double fx, fy, cx, cy, k1, k2, p1, p2;   /* pinhole projection_parameters / distortion_parameters */
+    double ric[9];                            /* extrinsicRotation imu<-cam, row-major: initial value (estimate_extrinsic 1) or fixed (0) */
+    double tic[3];                            /* extrinsicTranslation */
+    double td, tr;                            /* TD (initial value when estimate_td), TR (rolling_shutter_tr) */
+    double acc_n, acc_w, gyr_n, gyr_w, g_norm;
+} vio_calibration;
+
 /* parameters.cpp:81-243 readParameters() defaults for config/realsense/vio.yaml at 150 features */
 void vio_config_default(vio_config *cfg);
 
@@ -198,14 +211,16 @@ int vio_device_download(void *dst_host, const void *src_device, size_t bytes);
  * memory the runtime stages every copy).  NULL on failure. */
 void *vio_host_alloc(size_t bytes);
 void vio_host_free(void *p);
-/* sizeof(vio_config) (what = 0) / sizeof(vio_status) (what = 1) as compiled into the library: lets a binding check its struct mirrors */
+/* sizeof(vio_config) (what = 0) / sizeof(vio_status) (what = 1) / sizeof(vio_calibration) (what = 2) as compiled into the library: lets a
+ * binding check its struct mirrors */
 int vio_abi_sizeof(int what);
 /* Contract version of this header: 4 = a vio_feed host image set is free when the next vio_feed has returned; 5 = two uploads in flight (see
  * "Host buffers" above, vio_host_buffers_done); 6 = + vio_get_bound_stats, the inverse-depth bound handled as Ceres does (projected line search);
  * 7 = + estimate_extrinsic = 2 (vio_get_ex_calibration, vio_stage_relative_r); 8 = overflow flag 128 means only "extrinsic-calibration history
  * full": the fallback solver's clamp-only treatment of a bounded landmark moved to flag 512 (VIO_OVF_DEVIATION), which is no capacity error,
  * and flag 256 is documented (vio_status); 9 = + stage harnesses of the remaining be_linalg.h primitives (vio_stage_jacobi, vio_stage_sym_eig_lds,
- * vio_stage_spd_inverse16, vio_stage_scan_flags, vio_stage_schur, vio_stage_pinv15, vio_stage_chol blocks = -8 / -9). */
+ * vio_stage_spd_inverse16, vio_stage_scan_flags, vio_stage_schur, vio_stage_pinv15, vio_stage_chol blocks = -8 / -9); 10 = + per-sequence
+ * calibration (vio_calibration, vio_calibration_from_config, vio_set_calibration, vio_get_calibration, vio_abi_sizeof(2)). */
 int vio_abi_version(void);
 /* capacities derived from the configuration: out[0] = tracker points per sequence, out[1] = landmark slots, out[2] = IMU ring */
 int vio_get_capacity(vio_batch *h, int32_t *out3);
@@ -313,6 +328,20 @@ int vio_set_relo_frame(vio_batch *h, int seq, double frame_stamp, int frame_inde
 int vio_get_relo(vio_batch *h, int seq, double *out30);
 /* tic(3), ric(9 row-major), td */
 int vio_get_extrinsic(vio_batch *h, int seq, double *out13);
+/* The calibration fields of cfg (no validation). */
+void vio_calibration_from_config(const vio_config *cfg, vio_calibration *out);
+/* Gives sequence seq its own sensor calibration.  A slot with calibration k computes, bit for bit, what slot 0 of a one-sequence handle created
+ * with the handle's configuration and k's fields computes.  Validated first: every value finite, fx, fy > 0, tr >= 0, acc_n, acc_w, gyr_n, gyr_w,
+ * g_norm > 0, ric a rotation (orthonormal within 1e-6, determinant +1); otherwise VIO_EINVAL with vio_last_error() naming the field, and the
+ * slot is left untouched.  ric is re-orthonormalised through a normalised quaternion as vio_create does with cfg->ric; on an
+ * estimate_extrinsic = 2 handle ric / tic become I / 0.  On success the slot restarts like a freshly created handle (synchronises as
+ * vio_reset_seq, then a fresh tracker and estimator: IMU ring and last IMU stamp, mode-2 calibration history, sticky diagnostics), so the new
+ * sensor's clock may start again from 0.  Other slots are not disturbed.  The calibration persists across vio_reset, vio_reset_seq,
+ * vio_reset_tracker_seq and the failure-detection reboot (which restores ric / tic / td / g from it; mode 2 keeps its calibrated rotation). */
+int vio_set_calibration(vio_batch *h, int seq, const vio_calibration *cal);
+/* The calibration in effect for seq: ric after re-orthonormalisation, I / 0 on estimate_extrinsic = 2 handles (vio_get_extrinsic returns the
+ * current estimate instead). */
+int vio_get_calibration(vio_batch *h, int seq, vio_calibration *out);
 /* FeatureTracker public vectors after readImage (estimator_nodelet.cpp:337-343): returns count */
 int vio_get_tracks(vio_batch *h, int seq, int cap, int32_t *ids, int32_t *track_cnt, float *cur_pts_xy, float *cur_un_pts_xy,
                    float *pts_velocity_xy);

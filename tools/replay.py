@@ -4,7 +4,9 @@
     python tools/replay.py --config <vio.yaml> --data <dir with rgb.txt depth.txt imu.txt> --out vins_result.csv [--gt gt.txt]
 
 The recording layout is described in vins-rgbd-fast_amd/dataio.py (RgbdImuDirectory).  --gt: ``stamp x y z ...`` ground truth
-(TUM format) for an ATE report."""
+(TUM format) for an ATE report.  Repeated --config / --data / --out triples replay several recordings in ONE handle, one slot each, every
+slot with the calibration of its own configuration file (dataio.batch_config_from_yamls: the files must agree on every handle-wide
+setting); --gt then applies to the first recording."""
 import argparse
 import importlib
 import os
@@ -15,23 +17,52 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main():
+def parse_args(argv=None):
+    """(argparse namespace, [(config, data, out)]): the i-th --config, --data and --out belong together; --out may be left out (one
+    recording: vins_result.csv, several: vins_result_<i>.csv)"""
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", required=True)
-    ap.add_argument("--data", required=True)
-    ap.add_argument("--out", default="vins_result.csv")
+    ap.add_argument("--config", action="append", required=True)
+    ap.add_argument("--data", action="append", required=True)
+    ap.add_argument("--out", action="append", default=None)
     ap.add_argument("--gt", default=None)
     ap.add_argument("--lenient", action="store_true", help="warn instead of failing on settings outside the built hot path")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    n = len(a.config)
+    if len(a.data) != n:
+        ap.error("%d --config but %d --data: give one --data per --config" % (n, len(a.data)))
+    outs = a.out if a.out is not None else (["vins_result.csv"] if n == 1 else ["vins_result_%d.csv" % i for i in range(n)])
+    if len(outs) != n:
+        ap.error("%d --config but %d --out: give one --out per --config, or none" % (n, len(outs)))
+    return a, list(zip(a.config, a.data, outs))
+
+
+def main():
+    a, triples = parse_args()
     P = importlib.import_module("vins-rgbd-fast_amd")
     io = importlib.import_module("vins-rgbd-fast_amd.dataio")
-    cfg, extra = io.config_from_yaml(a.config, P, strict=not a.lenient)
-    for n in extra["notes"]:
-        print("note:", n, file=sys.stderr)
-    rec = io.RgbdImuDirectory(a.data)
-    b = P.VioBatch(cfg, 1, imu_capacity=1 << 15)
-    rows = io.replay(b, rec, a.out, freq=extra["freq"], frontend_freq=extra["frontend_freq"])  # freq / frontend_freq: estimator_nodelet.cpp:264-286
-    print("%d frames, %d odometry rows -> %s" % (len(rec), len(rows), a.out))
+    if len(triples) > 1:
+        cfg, cals, extras = io.batch_config_from_yamls([t[0] for t in triples], P, strict=not a.lenient)
+        for e in extras:
+            for n in e["notes"]:
+                print("note:", n, file=sys.stderr)
+        recs = [io.RgbdImuDirectory(t[1]) for t in triples]
+        b = P.VioBatch(cfg, len(triples), imu_capacity=1 << 15)
+        for i, k in enumerate(cals):
+            b.set_calibration(i, k)
+        all_rows = io.replay_many(b, recs, [t[2] for t in triples], freqs=[e["freq"] for e in extras],
+                                  frontend_freqs=[e["frontend_freq"] for e in extras])
+        for (cfg_path, data, out), rec, rows in zip(triples, recs, all_rows):
+            print("%s: %d frames, %d odometry rows -> %s" % (data, len(rec), len(rows), out))
+        rows = all_rows[0]
+    else:
+        cfg_path, data, out = triples[0]
+        cfg, extra = io.config_from_yaml(cfg_path, P, strict=not a.lenient)
+        for n in extra["notes"]:
+            print("note:", n, file=sys.stderr)
+        rec = io.RgbdImuDirectory(data)
+        b = P.VioBatch(cfg, 1, imu_capacity=1 << 15)
+        rows = io.replay(b, rec, out, freq=extra["freq"], frontend_freq=extra["frontend_freq"])  # freq / frontend_freq: estimator_nodelet.cpp:264-286
+        print("%d frames, %d odometry rows -> %s" % (len(rec), len(rows), out))
     if a.gt and len(rows) > 3:
         gt = np.loadtxt(a.gt, comments="#", ndmin=2)
         gp = np.array([gt[np.argmin(np.abs(gt[:, 0] - t)), 1:4] for t in rows[:, 0]])

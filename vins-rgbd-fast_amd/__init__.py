@@ -39,6 +39,40 @@ class Config(C.Structure):
         [(n, C.c_double) for n in ("td", "tr", "min_parallax_px", "init_depth")]
 
 
+CALIBRATION_FIELDS = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "ric", "tic", "td", "tr", "acc_n", "acc_w", "gyr_n", "gyr_w", "g_norm")
+
+
+class Calibration(C.Structure):
+    """vio_calibration (include/vio_abi.h): the per-sequence sensor calibration of a VioBatch slot."""
+    _fields_ = [(n, C.c_double) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2")] + \
+        [("ric", C.c_double * 9), ("tic", C.c_double * 3)] + \
+        [(n, C.c_double) for n in ("td", "tr", "acc_n", "acc_w", "gyr_n", "gyr_w", "g_norm")]
+
+
+def _copy_fields(dst, src, names=CALIBRATION_FIELDS):
+    for n in names:
+        v = getattr(src, n)
+        if n in ("ric", "tic"):
+            arr = getattr(dst, n)
+            for i in range(len(arr)):
+                arr[i] = float(v[i])
+        else:
+            setattr(dst, n, float(v))
+    return dst
+
+
+def calibration_from_config(cfg):
+    """vio_calibration_from_config: the calibration fields of a Config."""
+    return _copy_fields(Calibration(), cfg)
+
+
+def config_with_calibration(cfg, cal):
+    """A copy of cfg with cal's fields merged in (every other field, handle-wide, unchanged)."""
+    c = Config()
+    C.memmove(C.byref(c), C.byref(cfg), C.sizeof(Config))
+    return _copy_fields(c, cal)
+
+
 class SynthConfig(C.Structure):
     """vio_synth_config (include/vio_synth.h)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32)] + \
@@ -121,6 +155,11 @@ def lib():
         L.vio_get_window.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.vio_get_odometry.argtypes = [C.c_void_p, C.c_void_p]
         L.vio_get_extrinsic.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.vio_calibration_from_config.argtypes = [C.POINTER(Config), C.POINTER(Calibration)]
+        L.vio_set_calibration.argtypes = [C.c_void_p, C.c_int, C.POINTER(Calibration)]
+        L.vio_get_calibration.argtypes = [C.c_void_p, C.c_int, C.POINTER(Calibration)]
+        if L.vio_abi_sizeof(2) != C.sizeof(Calibration):
+            raise VioError("vio_calibration mirror does not match the library (%d != %d bytes)" % (C.sizeof(Calibration), L.vio_abi_sizeof(2)))
         L.vio_get_latest_odometry.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.vio_set_tracker_lag.argtypes = [C.c_void_p, C.c_int]
         L.vio_set_fisheye_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -299,6 +338,29 @@ class VioBatch:
         if not self.h:
             raise VioError("vio_create failed: %s" % self.L.vio_last_error().decode())
         self.h = C.c_void_p(self.h)
+        # the calibration each slot was given, before the library re-orthonormalises ric: config_of() hands it on, so that a handle or the
+        # oracle built from that configuration applies the same re-orthonormalisation to the same input
+        self._cal_in = [calibration_from_config(self.cfg) for _ in range(n_seq)]
+
+    def set_calibration(self, seq, cal):
+        """vio_set_calibration: slot seq gets its own sensor calibration (a Calibration) and restarts like a fresh handle"""
+        if not isinstance(cal, Calibration):
+            raise TypeError("set_calibration takes a Calibration")
+        self._chk(self.L.vio_set_calibration(self.h, int(seq), C.byref(cal)), "vio_set_calibration")
+        self._cal_in[int(seq)] = _copy_fields(Calibration(), cal)
+
+    def calibration(self, seq=0):
+        """vio_get_calibration: the calibration in effect (ric re-orthonormalised; I / 0 on estimate_extrinsic = 2 handles)"""
+        k = Calibration()
+        self._chk(self.L.vio_get_calibration(self.h, int(seq), C.byref(k)), "vio_get_calibration")
+        return k
+
+    def config_of(self, seq):
+        """The handle's configuration with slot seq's calibration merged in: what a one-sequence handle, the oracle or posegraph needs to
+        compute what this slot computes"""
+        if not 0 <= int(seq) < self.S:
+            raise IndexError("seq out of range")
+        return config_with_calibration(self.cfg, self._cal_in[int(seq)])
 
     @property
     def device(self):

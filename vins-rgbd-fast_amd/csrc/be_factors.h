@@ -323,7 +323,8 @@ DM_HD void imu_raw_jacobian_part(const PreInt &p, v3 G, const double *pi, const 
 
 // ProjectionFactor / ProjectionTdFactor::Evaluate. obs = 9 doubles (x y z u v vx vy cur_td depth).
 // J (optional) = 2x20 row-major, columns [pose_i(6) pose_j(6) ex(6) td(1) inv_depth(1)] in tangent coordinates.
-DM_HD void eval_projection(const vio_config &c, const double *pi, const double *pj, const double *ex, double inv_dep, double td,
+// t_r: the sequence's rolling-shutter readout (vio_calibration::tr; c.tr is not read)
+DM_HD void eval_projection(const vio_config &c, const double *pi, const double *pj, const double *ex, double inv_dep, double td, double t_r,
                            const double *oi, const double *oj, bool use_td, double *r, double *J) {
     v3 Pi = ld3(pi), Pj = ld3(pj), tic = ld3(ex);
     quat Qi = mkq(pi[6], pi[3], pi[4], pi[5]), Qj = mkq(pj[6], pj[3], pj[4], pj[5]), qic = mkq(ex[6], ex[3], ex[4], ex[5]);
@@ -332,8 +333,8 @@ DM_HD void eval_projection(const vio_config &c, const double *pi, const double *
     if (use_td) {
         double ROW = (double)c.height;
         double row_i = oi[4] - ROW / 2, row_j = oj[4] - ROW / 2;
-        pts_i = sub(pts_i, scl(td - oi[7] + c.tr / ROW * row_i, vel_i));
-        pts_j = sub(pts_j, scl(td - oj[7] + c.tr / ROW * row_j, vel_j));
+        pts_i = sub(pts_i, scl(td - oi[7] + t_r / ROW * row_i, vel_i));
+        pts_j = sub(pts_j, scl(td - oj[7] + t_r / ROW * row_j, vel_j));
     }
     double sq = c.focal_length / 1.5;
     v3 pts_camera_i = scl(1.0 / inv_dep, pts_i);
@@ -413,7 +414,7 @@ DM_HD v3 matvec9(const double *A, v3 v) { return mk(A[0] * v.x + A[1] * v.y + A[
 // Row layout: rs = 20 (default): [pose_i(6) pose_j(6) ex(6) td inv_depth]; rs = 14 ("compact", ext = false): [pose_i(6) pose_j(6)
 // inv_depth -] for solves in which the extrinsic and td blocks are constant (Ceres does not evaluate Jacobians of constant blocks
 // either); the inverse-depth column sits at index lcol = rs == 20 ? 19 : 12.
-DM_HD void eval_projection_pair(const vio_config &c, const PairGeo &g, const double *ricm, const double *ticp, double inv_dep, double td,
+DM_HD void eval_projection_pair(const vio_config &c, const PairGeo &g, const double *ricm, const double *ticp, double inv_dep, double td, double t_r,
                                 const double *oi, const double *oj, bool use_td, double *r, double *J, bool cauchy, double *wgt,
                                 const int rs = 20, const bool ext = true) {
     v3 pts_i = mk(oi[0], oi[1], oi[2]), pts_j = mk(oj[0], oj[1], oj[2]);
@@ -421,8 +422,8 @@ DM_HD void eval_projection_pair(const vio_config &c, const PairGeo &g, const dou
     if (use_td) {
         double ROW = (double)c.height;
         double row_i = oi[4] - ROW / 2, row_j = oj[4] - ROW / 2;
-        pts_i = sub(pts_i, scl(td - oi[7] + c.tr / ROW * row_i, vel_i));
-        pts_j = sub(pts_j, scl(td - oj[7] + c.tr / ROW * row_j, vel_j));
+        pts_i = sub(pts_i, scl(td - oi[7] + t_r / ROW * row_i, vel_i));
+        pts_j = sub(pts_j, scl(td - oj[7] + t_r / ROW * row_j, vel_j));
     }
     const double sq = c.focal_length / 1.5;
     v3 pc_i = mk(pts_i.x / inv_dep, pts_i.y / inv_dep, pts_i.z / inv_dep);

@@ -31,6 +31,7 @@ struct Ctx {
     int s, W, P, LW, NL, NLs, NPR;
     BeSeq *be;
     FeSeq *fe;
+    const vio_calibration *K;   // the sequence's calibration (Batch::cal)
     PreInt *pre;
     int *lm_id, *lm_start, *lm_nobs, *lm_est, *lm_solve, *lm_dyn, *lm_order, *lm_free, *lm_tmp, *lm_pidx, *lm_aidx, *lm_relo;
     double *lm_depth, *lm_obs, *feat, *cfeat, *relo_xy, *relo_mp;
@@ -49,7 +50,7 @@ __device__ Ctx make_ctx(const Batch &B, int s) {
     struct { int W, P, LW, NL, NP, NRES, NPRIOR, MX; } C = {B.gW, B.gP, B.gLW, B.gNL, B.gNP, B.gNRES, B.gNPRIOR, B.gMX};
     c.timings = B.timings;
     c.C = B.cfg; c.s = s; c.W = C.W; c.P = C.P; c.LW = C.LW; c.NL = C.NL; c.NLs = C.NL + 8; c.NPR = C.NPRIOR;
-    c.be = B.be + s; c.fe = B.fe + s;
+    c.be = B.be + s; c.fe = B.fe + s; c.K = B.cal + s;
     c.pre = B.pre + (size_t)s * (C.W + 2);
     size_t o = (size_t)s * C.NL;
     c.lm_id = B.lm_id + o; c.lm_start = B.lm_start + o; c.lm_nobs = B.lm_nobs + o; c.lm_est = B.lm_est_flag + o;
@@ -138,7 +139,8 @@ __device__ __forceinline__ void preint_store(PreInt &p, PreWork &w) {
     __syncthreads();
 }
 // one propagate(dt, acc, gyr) on the LDS-resident jacobian/covariance; p's small state is updated by thread 0
-__device__ void preint_propagate(PreInt &p, PreWork &w, const vio_config &c, double dt, v3 acc1, v3 gyr1) {
+// N: the noise densities (acc_n, gyr_n, acc_w, gyr_w): the sequence's vio_calibration, or the vio_config of a stage harness
+template <class N> __device__ void preint_propagate(PreInt &p, PreWork &w, const N &c, double dt, v3 acc1, v3 gyr1) {
     const int t = threadIdx.x;
     if (t == 0) {
         bf::PreintStep o = bf::preint_midpoint(p, dt, acc1, gyr1, w.F, w.V);
@@ -177,7 +179,7 @@ __device__ void preint_propagate(PreInt &p, PreWork &w, const vio_config &c, dou
 // own buffers (IntegrationBase::push_back).  Used for the merge of MARGIN_SECOND_NEW (estimator.cpp:1651-1687), where the step-by-step
 // version was 100 of the 190 us of that branch.
 // PREINT_MANY_LDS_DOUBLES (kernels.h): F and V of a chunk, LDS the caller lends (the marginalisation's tile region is free by then)
-__device__ void preint_propagate_many(PreInt &p, PreWork &w, const vio_config &cfg, int n, const double *dt_src, const double (*acc_src)[3],
+template <class N> __device__ void preint_propagate_many(PreInt &p, PreWork &w, const N &cfg, int n, const double *dt_src, const double (*acc_src)[3],
                                       const double (*gyr_src)[3], bool append, double *lds_fv) {
     const int t = threadIdx.x;
     double (*pm_F)[225] = (double (*)[225])lds_fv;
@@ -561,7 +563,7 @@ __device__ void repropagate_window(Ctx &c, PreWork &pw) {
             }
             for (int i = t; i < 225; i += nt) { pw.J[i] = ((i / 15) == (i % 15)) ? 1.0 : 0.0; pw.Pm[i] = 0; }
             __syncthreads();
-            for (int q = 0; q < p.n_buf; q++) preint_propagate(p, pw, cfg, p.dt_buf[q], ld3(p.acc_buf[q]), ld3(p.gyr_buf[q]));
+            for (int q = 0; q < p.n_buf; q++) preint_propagate(p, pw, *c.K, p.dt_buf[q], ld3(p.acc_buf[q]), ld3(p.gyr_buf[q]));
             preint_store(p, pw);
         }
 }
@@ -577,6 +579,7 @@ __global__ __launch_bounds__(256) void be_ingest_kernel(Batch B, const uint16_t 
     Ctx c = make_ctx(B, s);
     const DevCfg &C = *B.cfg;
     const vio_config &cfg = C.c;
+    const vio_calibration &K = *c.K;   // the sequence's IMU noise
     BeSeq &be = *c.be;
     FeSeq &fe = *c.fe;
     const int W = c.W;
@@ -857,7 +860,7 @@ __global__ __launch_bounds__(256) void be_ingest_kernel(Batch B, const uint16_t 
                         int i = t / 15, j = t - i * 15;
                         double s1 = 0;
                         for (int u = 0; u < 15; u++) s1 += pw.FP[i * 15 + u] * Fk[j * 15 + u];
-                        const double nn[6] = {cfg.acc_n * cfg.acc_n, cfg.gyr_n * cfg.gyr_n, cfg.acc_n * cfg.acc_n, cfg.gyr_n * cfg.gyr_n, cfg.acc_w * cfg.acc_w, cfg.gyr_w * cfg.gyr_w};
+                        const double nn[6] = {K.acc_n * K.acc_n, K.gyr_n * K.gyr_n, K.acc_n * K.acc_n, K.gyr_n * K.gyr_n, K.acc_w * K.acc_w, K.gyr_w * K.gyr_w};
                         double tt = 0;
 #pragma unroll
                         for (int u = 0; u < 18; u++) tt += Vk[i * 18 + u] * nn[u / 3] * Vk[j * 18 + u];
@@ -1041,13 +1044,13 @@ __device__ __forceinline__ double evaluate(const Ctx &c, const Params &X, const 
             double sq;
             if (vext) {
                 double *out = c.res + (size_t)r * 42;
-                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
+                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, c.K->tr, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
                                          cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
                 if (withJ) { out[40] = wgt * rr[0]; out[41] = wgt * rr[1]; }
             } else {
                 double *out = c.res + (size_t)r * 28;
-                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
+                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, c.K->tr, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
                                          cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt, 14, false);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
                 if (withJ) { out[13] = wgt * rr[0]; out[27] = wgt * rr[1]; }
@@ -1806,11 +1809,13 @@ __device__ __forceinline__ void solve_epilogue(Ctx &c, const Params &X, double c
                     be.Headers[i] = 0;
                     be.pre_idx[i] = i;
                 }
-                // (estimate_extrinsic = 2: setParameter() restores RIC[0], the calibrated rotation, and TIC[0] = 0 -- cfg.tic on such a handle)
-                for (int k = 0; k < 9; k++) be.ric[k] = cfg.estimate_extrinsic == 2 ? be.ex_ric[k] : cfg.ric[k];
-                for (int k = 0; k < 3; k++) { be.tic[k] = cfg.tic[k]; be.latest_Bg[k] = 0; }
-                be.td = cfg.td;
-                be.g[0] = 0; be.g[1] = 0; be.g[2] = cfg.g_norm;   // setParameter(): g = G (estimator.cpp:26)
+                // setParameter() restores the sequence's calibration (Batch::cal).  (estimate_extrinsic = 2: RIC[0], the calibrated rotation,
+                // and TIC[0] = 0 -- the table's tic on such a handle)
+                const vio_calibration &K = *c.K;
+                for (int k = 0; k < 9; k++) be.ric[k] = cfg.estimate_extrinsic == 2 ? be.ex_ric[k] : K.ric[k];
+                for (int k = 0; k < 3; k++) { be.tic[k] = K.tic[k]; be.latest_Bg[k] = 0; }
+                be.td = K.td;
+                be.g[0] = 0; be.g[1] = 0; be.g[2] = K.g_norm;   // setParameter(): g = G (estimator.cpp:26)
                 be.first_imu = 0; be.frame_count = 0; be.solver_flag = 0; be.openExEstimation = 0; be.has_prior = 0;
                 be.initFirstPoseFlag = 0; be.prevTime = -1; be.n_lm = 0; be.n_free = c.NL; be.ring_base = 0;
                 be.imu_head = be.imu_count_ingest;  // clearState() empties imu_buf (samples pushed for the next frame while this one was
@@ -2608,7 +2613,7 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
             double rr[2], wgt = 1.0;
             const double inv_dep = 1.0 / c.lm_depth[slot];
             const bf::PairGeo &g = *(const bf::PairGeo *)(mgeo + (size_t)(k - 1) * 32);
-            bf::eval_projection_pair(cfg, g, mgeo + (size_t)W * 32, X.ex, inv_dep, X.td, obs_ptr(c, slot, 0), obs_ptr(c, slot, k), cfg.estimate_td != 0, rr, out,
+            bf::eval_projection_pair(cfg, g, mgeo + (size_t)W * 32, X.ex, inv_dep, X.td, c.K->tr, obs_ptr(c, slot, 0), obs_ptr(c, slot, k), cfg.estimate_td != 0, rr, out,
                                      true, &wgt);
             out[40] = wgt * rr[0];
             out[41] = wgt * rr[1];
@@ -3194,7 +3199,7 @@ __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, un
             for (int k = 0; k < 9; k++) be.Rs[W - 1][k] = be.Rs[W][k];
         }
         preint_load(dst, pw);
-        preint_propagate_many(dst, pw, cfg, src.n_buf, src.dt_buf, src.acc_buf, src.gyr_buf, true, (double *)smem_marg);
+        preint_propagate_many(dst, pw, *c.K, src.n_buf, src.dt_buf, src.acc_buf, src.gyr_buf, true, (double *)smem_marg);
         preint_store(dst, pw);
         if (t == 0) bf::preint_init(src, ld3(be.acc_0), ld3(be.gyr_0), ld3(be.Bas[W]), ld3(be.Bgs[W]));
         __syncthreads();
@@ -3284,7 +3289,7 @@ __global__ __launch_bounds__(256) void be_dyn_finalize_kernel(Batch B, int seq, 
         __syncthreads();
         for (int q = offs[j]; q < offs[j + 1]; q++) {
             const double *sm = samples + (size_t)q * 7;
-            preint_propagate(p, pw, cfg, sm[0], ld3(sm + 1), ld3(sm + 4));
+            preint_propagate(p, pw, *c.K, sm[0], ld3(sm + 1), ld3(sm + 4));
         }
         preint_store(p, pw);
     }
@@ -3352,9 +3357,9 @@ __global__ void be_stage_projection_kernel(vio_config cfg, const double *in /*pi
         bf::pair_geo(in, in + 7, in + 14, g);
         double ricm[9];
         stm(ricm, q2R(mkq(in[14 + 6], in[14 + 3], in[14 + 4], in[14 + 5])));
-        bf::eval_projection_pair(cfg, g, ricm, in + 14, in[21], in[22], in + 23, in + 32, use_td != 0, r2, J, false, &wgt);
+        bf::eval_projection_pair(cfg, g, ricm, in + 14, in[21], in[22], cfg.tr, in + 23, in + 32, use_td != 0, r2, J, false, &wgt);
     } else
-        bf::eval_projection(cfg, in, in + 7, in + 14, in[21], in[22], in + 23, in + 32, use_td != 0, r2, J);
+        bf::eval_projection(cfg, in, in + 7, in + 14, in[21], in[22], cfg.tr, in + 23, in + 32, use_td != 0, r2, J);
     for (int a = 0; a < 2; a++) {
         for (int d = 0; d < 6; d++) { J46[a * 7 + d] = J[a * 20 + d]; J46[14 + a * 7 + d] = J[a * 20 + 6 + d]; J46[28 + a * 7 + d] = J[a * 20 + 12 + d]; }
         J46[a * 7 + 6] = 0; J46[14 + a * 7 + 6] = 0; J46[28 + a * 7 + 6] = 0;

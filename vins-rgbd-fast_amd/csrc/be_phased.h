@@ -309,6 +309,7 @@ __device__ __forceinline__ double ps_eval_role(const Batch &B, const int s, cons
     const int nt = 256;
     const BeSeq &be = *c.be;
     const vio_config &cfg = c.C->c;
+    const double cal_tr = c.K->tr;   // the sequence's rolling-shutter readout (Batch::cal)
     const bool vext = st.vext != 0;
     const int W = c.W, W1 = W + 1, n = c.NPR;
     double cost = 0;
@@ -432,7 +433,7 @@ __device__ __forceinline__ double ps_eval_role(const Batch &B, const int s, cons
                 const double *oi = obs_ptr(c, slot, imu_i);
                 for (int q = 0; q < VIO_OBS_D; q++) oj[q] = oi[q];
                 oj[0] = c.relo_xy[2 * slot]; oj[1] = c.relo_xy[2 * slot + 1]; oj[2] = 1.0;
-                bf::eval_projection(cfg, &X.pose[imu_i * 7], X.relo, X.ex, feat[c.lm_pidx[slot]], X.td, oi, oj, false, rr, withJ ? J : nullptr);
+                bf::eval_projection(cfg, &X.pose[imu_i * 7], X.relo, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, oi, oj, false, rr, withJ ? J : nullptr);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
                 wgt = sqrt(1.0 / (1.0 + sq));
                 if (withJ) {
@@ -445,7 +446,7 @@ __device__ __forceinline__ double ps_eval_role(const Batch &B, const int s, cons
                 }
             } else if (vext) {
                 double *out = c.res + (size_t)r * 42;
-                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
+                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
                                          cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
                 if (withJ) {
@@ -455,7 +456,7 @@ __device__ __forceinline__ double ps_eval_role(const Batch &B, const int s, cons
                 }
             } else {
                 double *out = c.res + (size_t)r * 28;
-                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
+                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
                                          cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt, 14, false);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
                 if (withJ) { out[13] = wgt * rr[0]; out[27] = wgt * rr[1]; }
@@ -497,6 +498,7 @@ __device__ __forceinline__ void ps_eval_body(const Batch &B) {
     Ctx c = make_ctx(B, s);
     const BeSeq &be = *c.be;
     const vio_config &cfg = c.C->c;
+    const double cal_tr = c.K->tr;   // the sequence's rolling-shutter readout (Batch::cal)
     const bool cand = st.stage == PS_EVAL_C;
     const double *feat = cand ? c.cfeat : c.feat;
     const bool withJ = st.eval_with_J != 0, vext = st.vext != 0;
@@ -629,7 +631,7 @@ __device__ __forceinline__ void ps_eval_body(const Batch &B) {
                 const double *oi = obs_ptr(c, slot, imu_i);
                 for (int q = 0; q < VIO_OBS_D; q++) oj[q] = oi[q];
                 oj[0] = c.relo_xy[2 * slot]; oj[1] = c.relo_xy[2 * slot + 1]; oj[2] = 1.0;
-                bf::eval_projection(cfg, &X.pose[imu_i * 7], X.relo, X.ex, feat[c.lm_pidx[slot]], X.td, oi, oj, false, rr, withJ ? J : nullptr);
+                bf::eval_projection(cfg, &X.pose[imu_i * 7], X.relo, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, oi, oj, false, rr, withJ ? J : nullptr);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
                 wgt = sqrt(1.0 / (1.0 + sq));
                 if (withJ) {
@@ -642,7 +644,7 @@ __device__ __forceinline__ void ps_eval_body(const Batch &B) {
                 }
             } else if (vext) {
                 double *out = c.res + (size_t)r * 42;
-                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
+                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
                                          cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
                 if (withJ) {
@@ -652,7 +654,7 @@ __device__ __forceinline__ void ps_eval_body(const Batch &B) {
                 }
             } else {
                 double *out = c.res + (size_t)r * 28;
-                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
+                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
                                          cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt, 14, false);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
                 if (withJ) { out[13] = wgt * rr[0]; out[27] = wgt * rr[1]; }
@@ -940,6 +942,7 @@ __global__ __launch_bounds__(256) void ps_evalf_kernel(Batch B) {
     ps_sel_rows(B, c, st.rowbuf ^ 1);   // the rows of the point under evaluation
     const BeSeq &be = *c.be;
     const vio_config &cfg = c.C->c;
+    const double cal_tr = c.K->tr;   // the sequence's rolling-shutter readout (Batch::cal)
     const bool cand = st.stage == PS_EVAL_C;
     const double *feat = cand ? c.cfeat : c.feat;
     const bool withJ = st.eval_with_J != 0;
@@ -1103,7 +1106,7 @@ __global__ __launch_bounds__(256) void ps_evalf_kernel(Batch B) {
             const bf::PairGeo &g = *(const bf::PairGeo *)(geo + (size_t)pair_slot(imu_i, imu_j, W1) * 32);
             double rr[2], wgt = 1.0;
             double *out = rec + (size_t)t * 28;
-            bf::eval_projection_pair(cfg, g, ricm, X.ex, inv_dep, X.td, oi_p, oj_p, cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt, 14, false);
+            bf::eval_projection_pair(cfg, g, ricm, X.ex, inv_dep, X.td, cal_tr, oi_p, oj_p, cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt, 14, false);
             const double sq = rr[0] * rr[0] + rr[1] * rr[1];
             if (withJ) { out[13] = wgt * rr[0]; out[27] = wgt * rr[1]; }
             cost += 0.5 * log(1.0 + sq);

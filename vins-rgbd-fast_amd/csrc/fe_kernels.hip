@@ -72,14 +72,14 @@ __device__ __forceinline__ int blend4(int p00, int p01, int p10, int p11, int w0
 }
 
 // camera (camera_model/src/camera_models/PinholeCamera.cc:449-542,645-662)
-__device__ __forceinline__ void cam_distortion(const vio_config &c, double x, double y, double &dx, double &dy) {
+__device__ __forceinline__ void cam_distortion(const vio_calibration &c, double x, double y, double &dx, double &dy) {
     double mx2 = x * x, my2 = y * y, mxy = x * y;
     double rho2 = mx2 + my2;
     double rad = c.k1 * rho2 + c.k2 * rho2 * rho2;
     dx = x * rad + 2.0 * c.p1 * mxy + c.p2 * (rho2 + 2.0 * mx2);
     dy = y * rad + 2.0 * c.p2 * mxy + c.p1 * (rho2 + 2.0 * my2);
 }
-__device__ void cam_lift(const vio_config &c, double u, double v, double &x, double &y) {
+__device__ void cam_lift(const vio_calibration &c, double u, double v, double &x, double &y) {
     double inv_K11 = 1.0 / c.fx, inv_K13 = -c.cx / c.fx, inv_K22 = 1.0 / c.fy, inv_K23 = -c.cy / c.fy;
     double mx_d = inv_K11 * u + inv_K13, my_d = inv_K22 * v + inv_K23, dx, dy;
     cam_distortion(c, mx_d, my_d, dx, dy);
@@ -92,7 +92,7 @@ __device__ void cam_lift(const vio_config &c, double u, double v, double &x, dou
     x = mx_u;
     y = my_u;
 }
-__device__ void cam_project(const vio_config &c, double X, double Y, double Z, double &u, double &v) {
+__device__ void cam_project(const vio_calibration &c, double X, double Y, double Z, double &u, double &v) {
     double px = X / Z, py = Y / Z, dx, dy;
     cam_distortion(c, px, py, dx, dy);
     u = c.fx * (px + dx) + c.cx;
@@ -114,7 +114,7 @@ __device__ __forceinline__ bool in_disk(const int *hw, int r, int px, int py, in
 // ------------------------------------------------------------------------------------------------ fe_begin
 // Estimator::predictMotion(t0, t1) (estimator.cpp:1790-1860): gyro integration over the IMU ring, nothing is consumed.  The rotation
 // into the camera frame uses the CONFIGURED extrinsic (the global RIC.back(), :1852), which stays at its yaml value while
-// ESTIMATE_EXTRINSIC refines Estimator::ric.
+// ESTIMATE_EXTRINSIC refines Estimator::ric: here the sequence's calibration (Batch::cal).
 __device__ dm::m3 predict_motion(const Batch &B, int s, double t0, double t1) {
     const DevCfg &C = *B.cfg;
     const BeSeq &be = B.be[s];
@@ -131,7 +131,7 @@ __device__ dm::m3 predict_motion(const Batch &B, int s, double t0, double t1) {
     bool first = true;
     double prev_t = 0;
     dm::v3 prev_gyr = dm::mk(0, 0, 0);
-    dm::m3 ricT = dm::tr(dm::ldm(C.c.ric));
+    dm::m3 ricT = dm::tr(dm::ldm(B.cal[s].ric));
     dm::v3 bg = dm::ld3(B.tracker_lag ? be.track_Bg : be.latest_Bg);
     while (k < be.imu_count && it[k % C.NIMU] <= t1) {
         double tk = it[k % C.NIMU];
@@ -189,7 +189,7 @@ __device__ dm::m3 predict_motion_wave(const Batch &B, int s, double t0, double t
         k += __builtin_ctzll(~bal);   // stamps ascend: the lanes with t <= t0 are a prefix
         break;
     }
-    const dm::m3 ricT = dm::tr(dm::ldm(C.c.ric));
+    const dm::m3 ricT = dm::tr(dm::ldm(B.cal[s].ric));
     const dm::v3 bg = dm::ld3(B.tracker_lag ? be.track_Bg : be.latest_Bg);
     bool first = true;
     double prev_t = 0;
@@ -549,12 +549,13 @@ __global__ void fe_predict_kernel(Batch B) {
     if (i >= fe.n_pts) return;
     float2 p = B.cur_pts[(size_t)s * C.NP + i];
     if (!C.c.use_imu) { B.forw_pts[(size_t)s * C.NP + i] = p; return; }   // feature_tracker.cpp:307-311: nextPts start at prevPts
+    const vio_calibration K = B.cal[s];
     double x, y;
-    cam_lift(C.c, p.x, p.y, x, y);
+    cam_lift(K, p.x, p.y, x, y);
     const double *R = fe.R_rel;
     double X = R[0] * x + R[1] * y + R[2], Y = R[3] * x + R[4] * y + R[5], Z = R[6] * x + R[7] * y + R[8];
     double u, v;
-    cam_project(C.c, X, Y, Z, u, v);
+    cam_project(K, X, Y, Z, u, v);
     B.forw_pts[(size_t)s * C.NP + i] = make_float2((float)u, (float)v);
 }
 
@@ -960,12 +961,13 @@ __global__ __launch_bounds__(256) void fe_select_kernel(Batch B) {
         // ---- rejectWithF (:441-473)
         if (n >= 8) {
             double hc = c.width / 2.0, hr = c.height / 2.0;
+            const vio_calibration K = B.cal[s];
             for (int i = t; i < n; i += blockDim.x) {
                 double x, y;
-                cam_lift(c, cur[i].x, cur[i].y, x, y);
+                cam_lift(K, cur[i].x, cur[i].y, x, y);
                 float ux = (float)(c.focal_length * x + hc), uy = (float)(c.focal_length * y + hr);
                 X1[i] = ((double)ux - hc) / c.focal_length; Y1[i] = ((double)uy - hr) / c.focal_length;
-                cam_lift(c, forw[i].x, forw[i].y, x, y);
+                cam_lift(K, forw[i].x, forw[i].y, x, y);
                 ux = (float)(c.focal_length * x + hc); uy = (float)(c.focal_length * y + hr);
                 X2[i] = ((double)ux - hc) / c.focal_length; Y2[i] = ((double)uy - hr) / c.focal_length;
             }
@@ -1467,11 +1469,12 @@ __global__ __launch_bounds__(256) void fe_add_kernel(Batch B, int gate) {
     // ---- cur <- forw; undistortedPoints (:542-593); updateID (:485-495)
     double dt = fe.cur_time - fe.prev_time;
     int *newflag = flag, *newoff = offs;  // n <= NP <= VIO_FAST_CAP is checked at create time
+    const vio_calibration K = B.cal[s];
     for (int i = t; i < n; i += blockDim.x) {
         float2 p = g_forw[i];
         g_cur[i] = p;
         double x, y;
-        cam_lift(c, p.x, p.y, x, y);
+        cam_lift(K, p.x, p.y, x, y);
         float2 u = make_float2((float)x, (float)y);
         g_un[i] = u;
         float2 vel = make_float2(0.f, 0.f);

@@ -146,12 +146,15 @@ void vio_synth_render_host(const vio_synth_config *c, uint64_t seq, double t, ui
     static vio_synth_config key;
     static bool valid = false;
     const float *rp;
+    std::vector<float> mine;
     {
+        // the table is validated (or built) and copied in ONE critical section: between two, a thread rendering another camera could swap
+        // in its own table, and this one would render with the wrong camera's rays (or read past a smaller table)
         std::lock_guard<std::mutex> lk(mu);
         const bool same = valid && key.width == c->width && key.height == c->height && key.fx == c->fx && key.fy == c->fy && key.cx == c->cx &&
                           key.cy == c->cy && key.k1 == c->k1 && key.k2 == c->k2 && key.p1 == c->p1 && key.p2 == c->p2;
         if (!same) {
-            // (a new table, never resized in place: another thread may still be rendering from the old one -- it keeps its copy alive below)
+            // (a new table, never resized in place)
             std::vector<float> nr((size_t)c->width * c->height * 2);
             for (int y = 0; y < c->height; y++)
                 for (int x = 0; x < c->width; x++) {
@@ -164,10 +167,6 @@ void vio_synth_render_host(const vio_synth_config *c, uint64_t seq, double t, ui
             key = *c;
             valid = true;
         }
-    }
-    std::vector<float> mine;
-    {
-        std::lock_guard<std::mutex> lk(mu);
         mine = rays;   // 2.4 MB copy per frame (a frame costs ~100 ms): no lifetime questions when cameras alternate between threads
     }
     rp = mine.data();

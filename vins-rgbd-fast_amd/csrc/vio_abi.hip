@@ -2,6 +2,8 @@
 // There is no CPU fallback: every entry point fails with VIO_EDEVICE when HIP is unavailable.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <algorithm>
+#include <cmath>
 #include <stdlib.h>
 #include <mutex>
 #include <chrono>
@@ -104,6 +106,10 @@ struct vio_batch {
     int *d_in_n = nullptr, *d_in_ids = nullptr;
     double *d_in_obs = nullptr, *d_in_stamps = nullptr;
     double *d_r9 = nullptr;           // vio_predict_motion result
+    // per-sequence calibration (vio_set_calibration): host mirror of the device table B.cal, as in effect (ric re-orthonormalised, I / 0 on
+    // estimate_extrinsic = 2 handles)
+    std::vector<vio_calibration> cal;
+    vio_calibration *d_cal = nullptr;
     // ---- dynamic initialisation (static_init: 0): host mirror of Estimator::all_image_frame per sequence while it is INITIAL
     struct DynSeq {
         std::vector<vinit::ImageFrame> frames;
@@ -256,6 +262,22 @@ __global__ void imu_commit_kernel(Batch B, int total, const int *seq_of) {
 
 namespace {
 
+// the calibration fields of a vio_config (vio_calibration) and back
+void cal_from_config(const vio_config &c, vio_calibration &k) {
+    k.fx = c.fx; k.fy = c.fy; k.cx = c.cx; k.cy = c.cy; k.k1 = c.k1; k.k2 = c.k2; k.p1 = c.p1; k.p2 = c.p2;
+    for (int i = 0; i < 9; i++) k.ric[i] = c.ric[i];
+    for (int i = 0; i < 3; i++) k.tic[i] = c.tic[i];
+    k.td = c.td; k.tr = c.tr;
+    k.acc_n = c.acc_n; k.acc_w = c.acc_w; k.gyr_n = c.gyr_n; k.gyr_w = c.gyr_w; k.g_norm = c.g_norm;
+}
+void cal_into_config(const vio_calibration &k, vio_config &c) {
+    c.fx = k.fx; c.fy = k.fy; c.cx = k.cx; c.cy = k.cy; c.k1 = k.k1; c.k2 = k.k2; c.p1 = k.p1; c.p2 = k.p2;
+    for (int i = 0; i < 9; i++) c.ric[i] = k.ric[i];
+    for (int i = 0; i < 3; i++) c.tic[i] = k.tic[i];
+    c.td = k.td; c.tr = k.tr;
+    c.acc_n = k.acc_n; c.acc_w = k.acc_w; c.gyr_n = k.gyr_n; c.gyr_w = k.gyr_w; c.g_norm = k.g_norm;
+}
+
 template <class T> int dalloc(vio_batch *h, T **p, size_t n) {
     void *q = nullptr;
     size_t bytes = n * sizeof(T);
@@ -307,16 +329,17 @@ int init_state(vio_batch *h, int s_lo, int s_hi, int what = VIO_RESET_ESTIMATOR 
     }
     for (int s = 0; s < n; s++) {
         BeSeq &b = be[s];
+        const vio_calibration &K = h->cal[s_lo + s];   // setParameter() with the sequence's calibration
         for (int i = 0; i <= VIO_MAXW; i++) { b.Rs[i][0] = b.Rs[i][4] = b.Rs[i][8] = 1; b.pre_idx[i] = i; }
-        for (int k = 0; k < 9; k++) b.ric[k] = C.c.ric[k];
+        for (int k = 0; k < 9; k++) b.ric[k] = K.ric[k];
         if (!ex.empty()) {
             b.ex_pending = ex[s].success_frame < 0 ? 1 : 0;
-            for (int k = 0; k < 9; k++) { b.ex_ric[k] = b.ex_pending ? C.c.ric[k] : ex[s].ric[k]; b.ric[k] = b.ex_ric[k]; }
+            for (int k = 0; k < 9; k++) { b.ex_ric[k] = b.ex_pending ? K.ric[k] : ex[s].ric[k]; b.ric[k] = b.ex_ric[k]; }
         }
-        for (int k = 0; k < 3; k++) b.tic[k] = C.c.tic[k];
-        b.td = C.c.td;
-        b.track_td = C.c.td;
-        b.g[2] = C.c.g_norm;
+        for (int k = 0; k < 3; k++) b.tic[k] = K.tic[k];
+        b.td = K.td;
+        b.track_td = K.td;
+        b.g[2] = K.g_norm;
         b.prevTime = -1;
         b.n_free = C.NL;
     }
@@ -582,7 +605,9 @@ int dynamic_init_step(vio_batch *h, int s, const IngestSrc &src, bool *finalize)
                 lms[k].obs[a] = {q[0], q[1], q[8]};
             }
         }
-        vinit::run(C.c, W, be.Headers, be.Bgs[0], be.ric, be.tic, D.frames, lms, res);
+        vio_config cs = C.c;   // the handle's configuration with the sequence's calibration
+        cal_into_config(h->cal[s], cs);
+        vinit::run(cs, W, be.Headers, be.Bgs[0], be.ric, be.tic, D.frames, lms, res);
         D.last_stage = res.stage;
         if (!res.ok) D.failures++;
         D.initial_timestamp = be.cur_stamp;
@@ -821,6 +846,13 @@ void vio_config_default(vio_config *c) {
     c->init_depth = 5.0;
 }
 
+// readParameters() re-orthonormalises the extrinsic rotation through a normalised quaternion (parameters.cpp:202-209).  build_devcfg and
+// vio_set_calibration share it: a slot and a one-sequence handle of the same calibration then hold the same bits.
+static void ortho_ric(const double *in, double *out) {
+    dm::m3 Rc = dm::q2R(dm::qnormalized(dm::R2q(dm::ldm(in))));
+    dm::stm(out, Rc);
+}
+
 static int build_devcfg(const vio_config *cfg, int imu_capacity, DevCfg &C) {
     memset(&C, 0, sizeof(C));
     C.c = *cfg;
@@ -841,9 +873,8 @@ static int build_devcfg(const vio_config *cfg, int imu_capacity, DevCfg &C) {
     if (c.estimate_extrinsic == 2) {   // parameters.cpp:181-190: the file's extrinsic is ignored, RIC = I, TIC = 0
         dm::stm(C.c.ric, dm::eye());
         for (int k = 0; k < 3; k++) C.c.tic[k] = 0;
-    } else {   // readParameters() re-orthonormalises the extrinsic rotation through a normalised quaternion (parameters.cpp:202-209)
-        dm::m3 Rc = dm::q2R(dm::qnormalized(dm::R2q(dm::ldm(c.ric))));
-        dm::stm(C.c.ric, Rc);
+    } else {
+        ortho_ric(c.ric, C.c.ric);
     }
     C.W = c.window_size;
     C.ncells = c.grid_rows * c.grid_cols;
@@ -985,6 +1016,7 @@ vio_batch *vio_create_on_device(const vio_config *cfg, int n_seq, int imu_capaci
     int rc = VIO_OK;
 #define DA(ptr, n) if (rc == VIO_OK) rc = dalloc(h, &ptr, (size_t)(n))
     DA(B.cfg, 1); DA(B.fe, S); DA(B.be, S); DA(B.pre, S * (C.W + 2));
+    DA(h->d_cal, S); B.cal = h->d_cal;
     DA(B.img, S * 2 * HW); DA(B.pyr, S * 2 * (size_t)C.pyr_bytes);
     if (C.c.equalize) { DA(B.clahe_lut, S * 64 * 256); DA(B.clahe_img, S * HW); }
     DA(B.cur_pts, S * NP); DA(B.forw_pts, S * NP); DA(B.cur_un_pts, S * NP); DA(B.pts_velocity, S * NP); DA(B.prev_un_pt, S * NP);
@@ -1069,6 +1101,13 @@ vio_batch *vio_create_on_device(const vio_config *cfg, int n_seq, int imu_capaci
     }
     for (int i = 0; i < 4 && rc == VIO_OK; i++)
         if (hipEventCreate(&h->ev[i]) != hipSuccess) { g_err = "event create failed"; rc = VIO_EDEVICE; }
+    if (rc == VIO_OK) {
+        // every slot starts with the configuration's calibration (build_devcfg has re-orthonormalised ric, or set I / 0 on mode 2)
+        vio_calibration k;
+        cal_from_config(C.c, k);
+        h->cal.assign(n_seq, k);
+        if (hipMemcpy(h->d_cal, h->cal.data(), sizeof(vio_calibration) * n_seq, hipMemcpyHostToDevice) != hipSuccess) { g_err = "calibration upload failed"; rc = VIO_EDEVICE; }
+    }
     if (rc == VIO_OK) { h->last_imu_t.assign(n_seq, -1e300); rc = init_state(h, 0, n_seq); }
     if (rc == VIO_OK) for (auto &g : h->groups) (void)hipEventRecord(g.ev_be, g.stream);
     if (rc == VIO_OK) {
@@ -1462,7 +1501,7 @@ int vio_feed_modes(vio_batch *h, const uint8_t *gray, const uint16_t *depth_mm, 
     return VIO_OK;
 }
 
-int vio_abi_version(void) { return 9; }
+int vio_abi_version(void) { return 10; }
 
 // marg_exact = 2 (the literal marginalisation with a CERTIFIED first inverse): out2 = {marginalisations of sequence seq whose certificate failed
 // since vio_create / vio_reset -- those frames used the block inverse WITHOUT the proof that the reference's 1e-8 cut drops nothing --, 1 if the
@@ -1792,7 +1831,9 @@ void vio_host_free(void *p) { if (p) (void)hipHostFree(p); }
 int vio_device_upload(void *dst, const void *src, size_t bytes) { HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return VIO_OK; }
 int vio_device_download(void *dst, const void *src, size_t bytes) { HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); return VIO_OK; }
 
-int vio_abi_sizeof(int what) { return what == 0 ? (int)sizeof(vio_config) : (what == 1 ? (int)sizeof(vio_status) : -1); }
+int vio_abi_sizeof(int what) {
+    return what == 0 ? (int)sizeof(vio_config) : what == 1 ? (int)sizeof(vio_status) : what == 2 ? (int)sizeof(vio_calibration) : -1;
+}
 
 int vio_get_capacity(vio_batch *h, int32_t *out3) {
     DevGuard dev_guard(h);
@@ -1935,6 +1976,62 @@ int vio_get_odometry_history(vio_batch *h, int seq, int cap, double *out) {
         done += run;
     }
     return n;
+}
+
+void vio_calibration_from_config(const vio_config *cfg, vio_calibration *out) {
+    if (cfg && out) cal_from_config(*cfg, *out);
+}
+
+int vio_set_calibration(vio_batch *h, int seq, const vio_calibration *cal) {
+    DevGuard dev_guard(h);
+    if (dev_guard.failed) { g_err = "hipSetDevice failed for the handle's device"; return VIO_EDEVICE; }
+    if (!h || !cal) { g_err = "vio_set_calibration: bad arguments"; return VIO_EINVAL; }
+    if (seq < 0 || seq >= h->S) { g_err = "vio_set_calibration: seq out of range"; return VIO_EINVAL; }
+    const vio_calibration &k = *cal;
+    // validation first: the slot is left untouched by a refusal
+    const struct { const char *name; const double *v; int n; } fin[] = {
+        {"fx", &k.fx, 1}, {"fy", &k.fy, 1}, {"cx", &k.cx, 1}, {"cy", &k.cy, 1}, {"k1", &k.k1, 1}, {"k2", &k.k2, 1}, {"p1", &k.p1, 1},
+        {"p2", &k.p2, 1}, {"ric", k.ric, 9}, {"tic", k.tic, 3}, {"td", &k.td, 1}, {"tr", &k.tr, 1}, {"acc_n", &k.acc_n, 1},
+        {"acc_w", &k.acc_w, 1}, {"gyr_n", &k.gyr_n, 1}, {"gyr_w", &k.gyr_w, 1}, {"g_norm", &k.g_norm, 1}};
+    for (const auto &f : fin)
+        for (int i = 0; i < f.n; i++)
+            if (!std::isfinite(f.v[i])) { g_err = std::string("vio_set_calibration: ") + f.name + " is not finite"; return VIO_EINVAL; }
+    const struct { const char *name; double v; } pos[] = {
+        {"fx", k.fx}, {"fy", k.fy}, {"acc_n", k.acc_n}, {"acc_w", k.acc_w}, {"gyr_n", k.gyr_n}, {"gyr_w", k.gyr_w}, {"g_norm", k.g_norm}};
+    for (const auto &f : pos)
+        if (!(f.v > 0)) { g_err = std::string("vio_set_calibration: ") + f.name + " must be > 0"; return VIO_EINVAL; }
+    if (!(k.tr >= 0)) { g_err = "vio_set_calibration: tr must be >= 0"; return VIO_EINVAL; }
+    {
+        double err = 0;
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                double d = (i == j) ? -1.0 : 0.0;
+                for (int q = 0; q < 3; q++) d += k.ric[3 * i + q] * k.ric[3 * j + q];
+                err = std::max(err, std::fabs(d));
+            }
+        const double *R = k.ric;
+        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+        if (!(err <= 1e-6) || !(det > 0)) { g_err = "vio_set_calibration: ric is not a rotation (orthonormal within 1e-6, determinant +1)"; return VIO_EINVAL; }
+    }
+    vio_calibration e = k;
+    if (h->hc.c.estimate_extrinsic == 2) {   // as build_devcfg: the extrinsic is calibrated online from RIC = I, TIC = 0
+        dm::stm(e.ric, dm::eye());
+        for (int i = 0; i < 3; i++) e.tic[i] = 0;
+    } else {
+        ortho_ric(k.ric, e.ric);
+    }
+    // a fresh slot: synchronise as vio_reset_seq, then the state of a newly created handle for this sequence only
+    { int rc_ = sync_all(h); if (rc_ != VIO_OK) return rc_; }
+    { int rc_ = refresh_dynamic_state(h); if (rc_ != VIO_OK) return rc_; }   // a reboot of ANOTHER sequence decided by the last solve must not be lost
+    HIPCHK(hipMemcpy(h->d_cal + seq, &e, sizeof(vio_calibration), hipMemcpyHostToDevice));
+    h->cal[seq] = e;
+    return init_state(h, seq, seq + 1);
+}
+
+int vio_get_calibration(vio_batch *h, int seq, vio_calibration *out) {
+    if (!h || !out || seq < 0 || seq >= h->S) { g_err = "vio_get_calibration: bad arguments"; return VIO_EINVAL; }
+    *out = h->cal[seq];
+    return VIO_OK;
 }
 
 int vio_get_extrinsic(vio_batch *h, int seq, double *out13) {

@@ -214,6 +214,7 @@ struct Batch {
     int eval_rpt;         // projection residuals per thread of ps_eval (VIO_EVAL_RPT: 1 = 256 per workgroup; 2 halves the workgroups of the launch)
     FeSeq *fe;
     BeSeq *be;
+    const vio_calibration *cal;   // [S] per-sequence calibration (vio_set_calibration): the only calibration source of device code
     PreInt *pre;          // [S][W+2]
     // ---- tracker arrays, stride NP per sequence
     uint8_t *img;         // [S][2][H*W] ping-pong level 0

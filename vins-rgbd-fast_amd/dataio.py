@@ -180,6 +180,51 @@ def config_from_yaml(path_or_text, P=None, strict=True):
     return c, extra
 
 
+def calibration_from_yaml(path_or_text, P=None, strict=True):
+    """The per-sequence calibration (vio_calibration) of a reference configuration file, read with the key rules of config_from_yaml
+    (``rolling_shutter`` selects ``rolling_shutter_tr``; ``estimate_extrinsic: 2`` gives ric = I, tic = 0)."""
+    if P is None:
+        import importlib
+        P = importlib.import_module("vins-rgbd-fast_amd")
+    c, _ = config_from_yaml(path_or_text, P, strict=strict)
+    return P.calibration_from_config(c)
+
+
+# vio_config fields that stay handle-wide, and the configuration-file key each comes from
+_HANDLE_WIDE_KEYS = (("width", "image_width"), ("height", "image_height"), ("max_cnt", "max_cnt"), ("min_dist", "min_dist"),
+                     ("grid_rows", "num_grid_rows"), ("grid_cols", "num_grid_cols"), ("f_threshold", "F_threshold"),
+                     ("depth_min", "depth_min_dist"), ("depth_max", "depth_max_dist"), ("fix_depth", "fix_depth"),
+                     ("max_iterations", "max_num_iterations"), ("min_parallax_px", "keyframe_parallax"),
+                     ("estimate_extrinsic", "estimate_extrinsic"), ("estimate_td", "estimate_td"), ("use_imu", "imu"),
+                     ("lk_max_level", "imu"), ("dynamic_init", "static_init"), ("equalize", "equalize"))
+
+
+def batch_config_from_yamls(paths, P=None, strict=True):
+    """One handle for several rigs: returns (shared_cfg, [calibration per file], [extra per file]).  The files may differ in their
+    calibration (intrinsics, distortion, extrinsic, td, tr, IMU noise, gravity); a handle-wide setting on which two files disagree raises
+    ValueError naming the configuration key.  The extras (freq / frontend_freq, ...) stay per file: replay_many gates every recording on
+    its own."""
+    if P is None:
+        import importlib
+        P = importlib.import_module("vins-rgbd-fast_amd")
+    paths = list(paths)
+    if not paths:
+        raise ValueError("batch_config_from_yamls needs at least one file")
+    cfgs, cals, extras = [], [], []
+    for p in paths:
+        c, e = config_from_yaml(p, P, strict=strict)
+        cfgs.append(c)
+        cals.append(P.calibration_from_config(c))
+        extras.append(e)
+    for field, key in _HANDLE_WIDE_KEYS:
+        v0 = getattr(cfgs[0], field)
+        for p, c in zip(paths[1:], cfgs[1:]):
+            if getattr(c, field) != v0:
+                raise ValueError("%s: handle-wide setting differs between %s (%r) and %s (%r); one handle serves one setting"
+                                 % (key, paths[0], v0, p, getattr(c, field)))
+    return cfgs[0], cals, extras
+
+
 # ---------------------------------------------------------------------------------------------------------------- CSV
 def format_odometry_row(stamp, P, Q_wxyz, V):
     """One line of VINS_RESULT_PATH (visualization.cpp:214-225): stamp in ns with precision 0, then P, Q(w,x,y,z), V with
@@ -458,6 +503,84 @@ def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_fre
     if wr:
         wr.close()
     return np.array(rows).reshape(-1, 11)
+
+
+def replay_many(batch, recordings, csv_paths=None, freqs=None, frontend_freqs=None, on_frame=None):
+    """replay() for several recordings through ONE handle, recording i in slot i (give each slot its calibration first,
+    VioBatch.set_calibration).  Every step feeds the next frame of every recording; each keeps its own frame gate, discontinuity restart
+    (vio_reset_seq of its slot only) and empty-map bookkeeping.  A slot whose recording has ended, or whose frame restarted the estimator,
+    gets VIO_FRAME_SKIP with a stamp beyond its IMU, which leaves it untouched.  Returns the rows of every recording (list of [n][11]);
+    on_frame(i, f, status) is called per recording and frame.  On a handle without IMU (imu: 0) a restarted slot is not held that way:
+    the SKIP then takes the place of its next first image."""
+    n = len(recordings)
+    if n > batch.S:
+        raise ValueError("%d recordings for %d slots" % (n, batch.S))
+    csv_paths = list(csv_paths) if csv_paths is not None else [None] * n
+    freqs = list(freqs) if freqs is not None else [0] * n
+    frontend_freqs = list(frontend_freqs) if frontend_freqs is not None else [0] * n
+    S = batch.S
+    rows = [[] for _ in range(n)]
+    wrs = [OdometryCsvWriter(p, append=False) if p else None for p in csv_paths]
+    gates = [FrameGate(freqs[i], frontend_freqs[i]) if int(frontend_freqs[i]) > 0 else None for i in range(n)]
+    init_pub, init_feature = [False] * n, [False] * n
+    kimu = [0] * n
+    g = dd = None
+    for f in range(max([len(r) for r in recordings] + [0])):
+        fed, decided = set(), {}
+        modes = np.full(S, FrameGate.SKIP, np.uint8)
+        stamps = np.full(S, np.inf)
+        for i, rec in enumerate(recordings):
+            if f >= len(rec):
+                continue
+            t, gray, depth = rec.frame(f)
+            if g is None:
+                g = np.zeros((S,) + gray.shape, gray.dtype)
+                dd = np.zeros((S,) + depth.shape, depth.dtype)
+            k = k2 = kimu[i]
+            while k2 < len(rec.imu_t) and rec.imu_t[k2] <= t + 1e-9:
+                k2 += 1
+            k2 = min(len(rec.imu_t), k2 + 1)
+            if k2 > k:
+                batch.push_imu(i, rec.imu_t[k:k2], rec.imu_acc[k:k2], rec.imu_gyr[k:k2])
+                kimu[i] = k2
+            mode, d = FrameGate.PUBLISH, None
+            if gates[i] is not None:
+                d = gates[i].step(t)
+                decided[i] = d
+                if d == FrameGate.RESET:
+                    batch.reset_seq(i)   # estimator_nodelet.cpp:243-262, this slot only; the frame is not fed (replay())
+                    continue
+                mode = FrameGate.PUBLISH if d == FrameGate.FIRST else d
+            decided[i] = d
+            g[i], dd[i] = gray, depth
+            modes[i], stamps[i] = mode, t
+            fed.add(i)
+        if fed:
+            batch.feed(g, dd, stamps, modes=modes)
+        for i in sorted(decided):
+            if i not in fed:
+                if on_frame:
+                    on_frame(i, f, batch.status(i))
+                continue
+            st = batch.status(i)
+            if gates[i] is not None and modes[i] == FrameGate.PUBLISH and decided[i] != FrameGate.FIRST:
+                if not init_pub[i]:
+                    init_pub[i] = True
+                elif not init_feature[i]:
+                    init_feature[i] = True
+                elif not st.processed and st.code == 0:
+                    gates[i].empty_map(stamps[i])
+            if st.solver_flag == 1 and st.processed:
+                row = batch.odometry()[i]
+                rows[i].append(row.copy())
+                if wrs[i]:
+                    wrs[i].write(row[0], row[1:4], row[4:8], row[8:11])
+            if on_frame:
+                on_frame(i, f, st)
+    for w in wrs:
+        if w:
+            w.close()
+    return [np.array(r).reshape(-1, 11) for r in rows]
 
 
 # ---------------------------------------------------------------------------------------------------------------- ATE
