@@ -114,6 +114,17 @@ typedef struct vio_calibration {
     double acc_n, acc_w, gyr_n, gyr_w, g_norm;
 } vio_calibration;
 
+/* Per-sequence camera model (ABI 11), camodocal's CameraFactory model_type.  p[] holds, in this order:
+ *   VIO_CAMERA_PINHOLE         fx fy cx cy k1 k2 p1 p2       (the pinhole fields of vio_calibration)
+ *   VIO_CAMERA_KANNALA_BRANDT  k2 k3 k4 k5 mu mv u0 v0       (EquidistantCamera)
+ *   VIO_CAMERA_MEI             xi k1 k2 p1 p2 gamma1 gamma2 u0 v0   (CataCamera)
+ * and zeros after them.  reserved must be 0.  The back-end is model-free: it works on normalised-plane points (x / z, y / z). */
+enum { VIO_CAMERA_PINHOLE = 0, VIO_CAMERA_KANNALA_BRANDT = 1, VIO_CAMERA_MEI = 2 };
+typedef struct vio_camera {
+    int32_t model, reserved;
+    double p[12];
+} vio_camera;
+
 /* parameters.cpp:81-243 readParameters() defaults for config/realsense/vio.yaml at 150 features */
 void vio_config_default(vio_config *cfg);
 
@@ -211,8 +222,8 @@ int vio_device_download(void *dst_host, const void *src_device, size_t bytes);
  * memory the runtime stages every copy).  NULL on failure. */
 void *vio_host_alloc(size_t bytes);
 void vio_host_free(void *p);
-/* sizeof(vio_config) (what = 0) / sizeof(vio_status) (what = 1) / sizeof(vio_calibration) (what = 2) as compiled into the library: lets a
- * binding check its struct mirrors */
+/* sizeof(vio_config) (what = 0) / sizeof(vio_status) (what = 1) / sizeof(vio_calibration) (what = 2) / sizeof(vio_camera) (what = 3) as
+ * compiled into the library: lets a binding check its struct mirrors */
 int vio_abi_sizeof(int what);
 /* Contract version of this header: 4 = a vio_feed host image set is free when the next vio_feed has returned; 5 = two uploads in flight (see
  * "Host buffers" above, vio_host_buffers_done); 6 = + vio_get_bound_stats, the inverse-depth bound handled as Ceres does (projected line search);
@@ -220,7 +231,9 @@ int vio_abi_sizeof(int what);
  * full": the fallback solver's clamp-only treatment of a bounded landmark moved to flag 512 (VIO_OVF_DEVIATION), which is no capacity error,
  * and flag 256 is documented (vio_status); 9 = + stage harnesses of the remaining be_linalg.h primitives (vio_stage_jacobi, vio_stage_sym_eig_lds,
  * vio_stage_spd_inverse16, vio_stage_scan_flags, vio_stage_schur, vio_stage_pinv15, vio_stage_chol blocks = -8 / -9); 10 = + per-sequence
- * calibration (vio_calibration, vio_calibration_from_config, vio_set_calibration, vio_get_calibration, vio_abi_sizeof(2)). */
+ * calibration (vio_calibration, vio_calibration_from_config, vio_set_calibration, vio_get_calibration, vio_abi_sizeof(2)); 11 = + per-sequence
+ * camera models (vio_camera, vio_set_camera, vio_get_camera, vio_stage_camera, vio_stage_host_camera, vio_abi_sizeof(3);
+ * vio_synth_render_host_camera / _device_camera in vio_synth.h, vio_pg_describe_camera in vio_posegraph.h). */
 int vio_abi_version(void);
 /* capacities derived from the configuration: out[0] = tracker points per sequence, out[1] = landmark slots, out[2] = IMU ring */
 int vio_get_capacity(vio_batch *h, int32_t *out3);
@@ -342,6 +355,17 @@ int vio_set_calibration(vio_batch *h, int seq, const vio_calibration *cal);
 /* The calibration in effect for seq: ric after re-orthonormalisation, I / 0 on estimate_extrinsic = 2 handles (vio_get_extrinsic returns the
  * current estimate instead). */
 int vio_get_calibration(vio_batch *h, int seq, vio_calibration *out);
+/* Gives sequence seq its own camera model (feature_tracker.cpp:500, CameraFactory::generateCameraFromYamlFile).  The tracker lifts and projects
+ * through it (predictPtsInNextFrame, rejectWithF, undistortedPoints); everything downstream sees normalised-plane points x / z, y / z.  A slot
+ * with camera k computes, bit for bit, what slot 0 of a one-sequence handle given camera k computes.  Validated first: model known, reserved
+ * 0, every p[] finite, fx, fy, mu, mv, gamma1, gamma2 > 0, xi >= 0, and the four image corners and four edge midpoints lift to finite rays
+ * with z > 0 (the unit-plane factors cannot represent a ray at or beyond 90 degrees); otherwise VIO_EINVAL with vio_last_error() naming the
+ * field, and the slot is left untouched.  PINHOLE writes fx..p2 into the slot's vio_calibration.  On success the slot restarts as with
+ * vio_set_calibration; other slots are not disturbed.  vio_create gives every slot PINHOLE from cfg; vio_set_calibration never changes the
+ * model (its fx..p2 take effect while the model is PINHOLE); the camera persists across vio_reset* and the failure-detection reboot. */
+int vio_set_camera(vio_batch *h, int seq, const vio_camera *cam);
+/* The camera of seq (PINHOLE: p[] = the calibration's fx..p2). */
+int vio_get_camera(vio_batch *h, int seq, vio_camera *out);
 /* FeatureTracker public vectors after readImage (estimator_nodelet.cpp:337-343): returns count */
 int vio_get_tracks(vio_batch *h, int seq, int cap, int32_t *ids, int32_t *track_cnt, float *cur_pts_xy, float *cur_un_pts_xy,
                    float *pts_velocity_xy);
@@ -406,6 +430,11 @@ int vio_stage_pnp(int n, const double *obj, const double *img, double *rvec3, do
  * (w x y z), T[(W+1)*3], pts[nf*4] = (solved, X, Y, Z), stats[2] = (BA iterations, points in the BA); returns 0 ok, 1 no frame pair
  * with enough parallax, 2 SfM failed). */
 int vio_stage_host_pnp(int n, const double *obj, const double *img, double *R9, double *t3);
+/* camera_model.h on n pixels uv[n][2]: ray_out[n][3] = liftProjective (not normalised), un_out[n][2] = (x / z, y / z) as undistortedPoints
+ * stores it, uv_out[n][2] = spaceToPlane(R9 * ray) as predictPtsInNextFrame computes it (R9 row-major; NULL = identity).  Any of the outputs
+ * may be NULL.  vio_stage_camera runs on the device, vio_stage_host_camera on the CPU (no GPU needed). */
+int vio_stage_camera(const vio_camera *cam, int n, const double *uv, const double *R9, double *ray_out, double *un_out, double *uv_out);
+int vio_stage_host_camera(const vio_camera *cam, int n, const double *uv, const double *R9, double *ray_out, double *un_out, double *uv_out);
 int vio_stage_host_pnp_ransac(int n, const double *obj, const double *img, int max_iters, double thresh, double confidence, double *R9, double *t3);
 /* LinearAlignmentWithDepth + RefineGravityWithDepth (initial_aligment.cpp:170-244, 337-405): frames19 = n x {R[9] row-major, T[3], sum_dt,
  * delta_p[3], delta_v[3]}; g_out3 = gravity in the SfM frame, x_out[3 n + 3] = body velocities per frame + the last correction;

@@ -304,6 +304,10 @@ class FeatureTracker {
         ids.resize(n); track_cnt.resize(n); cur_pts.resize(n); cur_un_pts.resize(n); pts_velocity.resize(n);
         cur_time_ = cur_time;
     }
+    // void readIntrinsicParameter(const string &calib_file) (feature_tracker.h:43, feature_tracker.cpp:497-502: CameraFactory::
+    // generateCameraFromYamlFile).  device: the caller parses the file (the Python loader: dataio.config_from_yaml's extra["camera"]) and hands
+    // the model over; the sequence restarts as with vio_set_camera.  PINHOLE is the handle's default and needs no call.
+    void setCamera(const vio_camera &camera) { Estimator::check(vio_set_camera(e_.h_, 0, &camera), "vio_set_camera"); e_.clearMirror(); }
     // feature_tracker.h:41 -- the nodelet loops `for (i = 0;; i++) if (!updateID(i)) break;` (estimator_nodelet.cpp:324-330).
     // device: ids are already assigned inside readImage; the loop contract (true while i < ids.size()) is kept.
     bool updateID(unsigned int i) const { return i < ids.size(); }

@@ -25,6 +25,11 @@ extern "C" {
  * (support_files/brief_pattern.yml).  Returns the number of keypoints found (may exceed cap: only cap are written) or a negative status. */
 int vio_pg_describe(const vio_config *cfg, const uint8_t *gray, int n_win, const float *win_uv, const int32_t *pattern1024, int fast_threshold,
                     uint64_t *win_desc, int cap, float *kp_xy, uint64_t *kp_desc, float *kp_norm);
+/* vio_pg_describe with the keypoints lifted through a camera model (vio_abi.h's vio_camera, as KeyFrame::computeBRIEFPoint lifts them through
+ * m_camera): kp_norm = (x / z, y / z) of liftProjective.  cfg still gives the image size. */
+int vio_pg_describe_camera(const vio_config *cfg, const vio_camera *cam, const uint8_t *gray, int n_win, const float *win_uv,
+                           const int32_t *pattern1024, int fast_threshold, uint64_t *win_desc, int cap, float *kp_xy, uint64_t *kp_desc,
+                           float *kp_norm);
 
 /* KeyFrame::searchByBRIEFDes / searchInAera / HammingDis (keyframe.cpp:126-169, 530): for each of the n window descriptors the FIRST old
  * descriptor with the smallest Hamming distance below 128; best_index[i] = its index if the distance is below 80, else -1. */

@@ -7,6 +7,7 @@
 #ifndef VIO_SYNTH_H
 #define VIO_SYNTH_H
 #include <stdint.h>
+#include "vio_abi.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -38,6 +39,13 @@ void vio_synth_render_host(const vio_synth_config *c, uint64_t seq, double t, ui
  * stream is a hipStream_t (may be NULL). Returns 0 on success, a negative vio error code otherwise. */
 int vio_synth_render_device(const vio_synth_config *c, int S, uint64_t seq0, double t, uint8_t *d_gray, uint16_t *d_depth_mm,
                             void *stream);
+/* The same renderers through a camera model (vio_abi.h's vio_camera) instead of c's pinhole fields: every pixel's ray is camera_model.h's
+ * liftProjective of the pixel, normalised to z = 1 (one shared lift: host and device build the same table).  Depth stays the z-depth in
+ * millimetres, as a registered RealSense depth image, for every model.  A PINHOLE cam renders what the functions above render with c's
+ * fx..p2 replaced by cam->p[0..7].  The ray tables are cached per camera (model and every parameter). */
+void vio_synth_render_host_camera(const vio_synth_config *c, const vio_camera *cam, uint64_t seq, double t, uint8_t *gray, uint16_t *depth_mm);
+int vio_synth_render_device_camera(const vio_synth_config *c, const vio_camera *cam, int S, uint64_t seq0, double t, uint8_t *d_gray,
+                                   uint16_t *d_depth_mm, void *stream);
 
 #ifdef __cplusplus
 }

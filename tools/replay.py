@@ -47,8 +47,10 @@ def main():
                 print("note:", n, file=sys.stderr)
         recs = [io.RgbdImuDirectory(t[1]) for t in triples]
         b = P.VioBatch(cfg, len(triples), imu_capacity=1 << 15)
-        for i, k in enumerate(cals):
+        for i, (k, e) in enumerate(zip(cals, extras)):
             b.set_calibration(i, k)
+            if e["camera"] is not None:   # KANNALA_BRANDT / MEI (dataio.config_from_yaml)
+                b.set_camera(i, e["camera"])
         all_rows = io.replay_many(b, recs, [t[2] for t in triples], freqs=[e["freq"] for e in extras],
                                   frontend_freqs=[e["frontend_freq"] for e in extras])
         for (cfg_path, data, out), rec, rows in zip(triples, recs, all_rows):
@@ -61,6 +63,8 @@ def main():
             print("note:", n, file=sys.stderr)
         rec = io.RgbdImuDirectory(data)
         b = P.VioBatch(cfg, 1, imu_capacity=1 << 15)
+        if extra["camera"] is not None:   # KANNALA_BRANDT / MEI (dataio.config_from_yaml)
+            b.set_camera(0, extra["camera"])
         rows = io.replay(b, rec, out, freq=extra["freq"], frontend_freq=extra["frontend_freq"])  # freq / frontend_freq: estimator_nodelet.cpp:264-286
         print("%d frames, %d odometry rows -> %s" % (len(rec), len(rows), out))
     if a.gt and len(rows) > 3:

@@ -73,6 +73,71 @@ def config_with_calibration(cfg, cal):
     return _copy_fields(c, cal)
 
 
+CAMERA_PINHOLE, CAMERA_KANNALA_BRANDT, CAMERA_MEI = 0, 1, 2
+CAMERA_PARAMS = {CAMERA_PINHOLE: ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2"),
+                 CAMERA_KANNALA_BRANDT: ("k2", "k3", "k4", "k5", "mu", "mv", "u0", "v0"),
+                 CAMERA_MEI: ("xi", "k1", "k2", "p1", "p2", "gamma1", "gamma2", "u0", "v0")}
+
+
+class Camera(C.Structure):
+    """vio_camera (include/vio_abi.h): a slot's camera model; p holds CAMERA_PARAMS[model] in order, zeros after them."""
+    _fields_ = [("model", C.c_int32), ("reserved", C.c_int32), ("p", C.c_double * 12)]
+
+    def params(self):
+        """{name: value} of the model's parameters"""
+        return {n: float(self.p[i]) for i, n in enumerate(CAMERA_PARAMS[int(self.model)])}
+
+    def __eq__(self, other):
+        return isinstance(other, Camera) and int(self.model) == int(other.model) and list(self.p) == list(other.p)
+
+    def __repr__(self):
+        return "Camera(%d, %s)" % (int(self.model), self.params())
+
+
+def _camera(model, values):
+    c = Camera()
+    c.model = model
+    for i, v in enumerate(values):
+        c.p[i] = float(v)
+    return c
+
+
+def camera_pinhole(cal):
+    """The PINHOLE Camera of a Calibration's (or Config's) fx fy cx cy k1 k2 p1 p2"""
+    return _camera(CAMERA_PINHOLE, [getattr(cal, n) for n in CAMERA_PARAMS[CAMERA_PINHOLE]])
+
+
+def camera_kannala_brandt(k2, k3, k4, k5, mu, mv, u0, v0):
+    """KANNALA_BRANDT (camodocal EquidistantCamera) projection_parameters"""
+    return _camera(CAMERA_KANNALA_BRANDT, (k2, k3, k4, k5, mu, mv, u0, v0))
+
+
+def camera_mei(xi, k1, k2, p1, p2, gamma1, gamma2, u0, v0):
+    """MEI (camodocal CataCamera): mirror_parameters xi, distortion_parameters k1 k2 p1 p2, projection_parameters gamma1 gamma2 u0 v0"""
+    return _camera(CAMERA_MEI, (xi, k1, k2, p1, p2, gamma1, gamma2, u0, v0))
+
+
+def _stage_camera(fn, cam, uv, R=None):
+    uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 2)
+    n = len(uv)
+    ray, un, uvo = np.zeros((n, 3)), np.zeros((n, 2)), np.zeros((n, 2))
+    Rm = None if R is None else np.ascontiguousarray(R, np.float64).reshape(9)
+    rc = fn(C.byref(cam), n, uv.ctypes.data, None if Rm is None else Rm.ctypes.data, ray.ctypes.data, un.ctypes.data, uvo.ctypes.data)
+    if rc != 0:
+        raise VioError("camera stage failed (%d): %s" % (rc, lib().vio_last_error().decode()))
+    return ray, un, uvo
+
+
+def stage_camera(cam, uv, R=None):
+    """vio_stage_camera (device): (ray [n][3] = liftProjective, un [n][2] = (x / z, y / z), uv_out [n][2] = spaceToPlane(R * ray))"""
+    return _stage_camera(lib().vio_stage_camera, cam, uv, R)
+
+
+def stage_host_camera(cam, uv, R=None):
+    """vio_stage_host_camera: the same on the CPU (no GPU needed)"""
+    return _stage_camera(lib().vio_stage_host_camera, cam, uv, R)
+
+
 class SynthConfig(C.Structure):
     """vio_synth_config (include/vio_synth.h)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32)] + \
@@ -158,6 +223,13 @@ def lib():
         L.vio_calibration_from_config.argtypes = [C.POINTER(Config), C.POINTER(Calibration)]
         L.vio_set_calibration.argtypes = [C.c_void_p, C.c_int, C.POINTER(Calibration)]
         L.vio_get_calibration.argtypes = [C.c_void_p, C.c_int, C.POINTER(Calibration)]
+        L.vio_set_camera.argtypes = [C.c_void_p, C.c_int, C.POINTER(Camera)]
+        L.vio_get_camera.argtypes = [C.c_void_p, C.c_int, C.POINTER(Camera)]
+        L.vio_stage_camera.argtypes = [C.POINTER(Camera), C.c_int] + [C.c_void_p] * 5
+        L.vio_stage_host_camera.argtypes = [C.POINTER(Camera), C.c_int] + [C.c_void_p] * 5
+        L.vio_synth_render_host_camera.argtypes = [C.POINTER(SynthConfig), C.POINTER(Camera), C.c_uint64, C.c_double, C.c_void_p, C.c_void_p]
+        L.vio_synth_render_device_camera.argtypes = [C.POINTER(SynthConfig), C.POINTER(Camera), C.c_int, C.c_uint64, C.c_double, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]
         if L.vio_abi_sizeof(2) != C.sizeof(Calibration):
             raise VioError("vio_calibration mirror does not match the library (%d != %d bytes)" % (C.sizeof(Calibration), L.vio_abi_sizeof(2)))
         L.vio_get_latest_odometry.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -312,14 +384,21 @@ class Synth:
         self.L.vio_synth_imu(C.byref(self.cfg), seq, n, t.ctypes.data, a.ctypes.data, g.ctypes.data)
         return t, a, g
 
-    def render_host(self, seq, t):
+    def render_host(self, seq, t, camera=None):
+        """camera: a Camera to render through (vio_synth_render_host_camera) instead of the configuration's pinhole"""
         g = np.zeros((self.cfg.height, self.cfg.width), np.uint8)
         d = np.zeros((self.cfg.height, self.cfg.width), np.uint16)
-        self.L.vio_synth_render_host(C.byref(self.cfg), seq, t, g.ctypes.data, d.ctypes.data)
+        if camera is None:
+            self.L.vio_synth_render_host(C.byref(self.cfg), seq, t, g.ctypes.data, d.ctypes.data)
+        else:
+            self.L.vio_synth_render_host_camera(C.byref(self.cfg), C.byref(camera), seq, t, g.ctypes.data, d.ctypes.data)
         return g, d
 
-    def render_device(self, n_seq, seq0, t, d_gray, d_depth, stream=None):
-        rc = self.L.vio_synth_render_device(C.byref(self.cfg), n_seq, seq0, t, _ptr(d_gray), _ptr(d_depth), stream)
+    def render_device(self, n_seq, seq0, t, d_gray, d_depth, stream=None, camera=None):
+        if camera is None:
+            rc = self.L.vio_synth_render_device(C.byref(self.cfg), n_seq, seq0, t, _ptr(d_gray), _ptr(d_depth), stream)
+        else:
+            rc = self.L.vio_synth_render_device_camera(C.byref(self.cfg), C.byref(camera), n_seq, seq0, t, _ptr(d_gray), _ptr(d_depth), stream)
         if rc != 0:
             raise VioError("vio_synth_render_device failed (%d)" % rc)
 
@@ -353,6 +432,22 @@ class VioBatch:
         """vio_get_calibration: the calibration in effect (ric re-orthonormalised; I / 0 on estimate_extrinsic = 2 handles)"""
         k = Calibration()
         self._chk(self.L.vio_get_calibration(self.h, int(seq), C.byref(k)), "vio_get_calibration")
+        return k
+
+    def set_camera(self, seq, cam):
+        """vio_set_camera: slot seq gets its own camera model (a Camera) and restarts like a fresh handle; PINHOLE also sets the
+        calibration's fx..p2"""
+        if not isinstance(cam, Camera):
+            raise TypeError("set_camera takes a Camera")
+        self._chk(self.L.vio_set_camera(self.h, int(seq), C.byref(cam)), "vio_set_camera")
+        if int(cam.model) == CAMERA_PINHOLE:
+            for i, n in enumerate(CAMERA_PARAMS[CAMERA_PINHOLE]):
+                setattr(self._cal_in[int(seq)], n, float(cam.p[i]))
+
+    def camera(self, seq=0):
+        """vio_get_camera: the slot's camera model (PINHOLE: the calibration's fx..p2)"""
+        k = Camera()
+        self._chk(self.L.vio_get_camera(self.h, int(seq), C.byref(k)), "vio_get_camera")
         return k
 
     def config_of(self, seq):

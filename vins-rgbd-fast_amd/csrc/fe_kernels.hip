@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "fe_ransac.h"
+#include "camera_model.h"
 
 // in-kernel phase timers of sequence 0 (thread 0, 100 MHz ticks into Batch::timings, slots 64..; tools/phase_profile.py)
 #if VIO_TIMERS
@@ -71,32 +72,44 @@ __device__ __forceinline__ int blend4(int p00, int p01, int p10, int p11, int w0
     return __mul24(p00, w00) + __mul24(p01, w01) + __mul24(p10, w10) + __mul24(p11, w11);
 }
 
-// camera (camera_model/src/camera_models/PinholeCamera.cc:449-542,645-662)
-__device__ __forceinline__ void cam_distortion(const vio_calibration &c, double x, double y, double &dx, double &dy) {
-    double mx2 = x * x, my2 = y * y, mxy = x * y;
-    double rho2 = mx2 + my2;
-    double rad = c.k1 * rho2 + c.k2 * rho2 * rho2;
-    dx = x * rad + 2.0 * c.p1 * mxy + c.p2 * (rho2 + 2.0 * mx2);
-    dy = y * rad + 2.0 * c.p2 * mxy + c.p1 * (rho2 + 2.0 * my2);
-}
+// camera (camera_model/src/camera_models/PinholeCamera.cc:449-542,645-662): the PINHOLE slots, inline
 __device__ void cam_lift(const vio_calibration &c, double u, double v, double &x, double &y) {
-    double inv_K11 = 1.0 / c.fx, inv_K13 = -c.cx / c.fx, inv_K22 = 1.0 / c.fy, inv_K23 = -c.cy / c.fy;
-    double mx_d = inv_K11 * u + inv_K13, my_d = inv_K22 * v + inv_K23, dx, dy;
-    cam_distortion(c, mx_d, my_d, dx, dy);
-    double mx_u = mx_d - dx, my_u = my_d - dy;
-    for (int i = 1; i < 8; i++) {
-        cam_distortion(c, mx_u, my_u, dx, dy);
-        mx_u = mx_d - dx;
-        my_u = my_d - dy;
-    }
-    x = mx_u;
-    y = my_u;
+    vcam::pinhole_lift(c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2, u, v, x, y);
 }
 __device__ void cam_project(const vio_calibration &c, double X, double Y, double Z, double &u, double &v) {
-    double px = X / Z, py = Y / Z, dx, dy;
-    cam_distortion(c, px, py, dx, dy);
-    u = c.fx * (px + dx) + c.cx;
-    v = c.fy * (py + dy) + c.cy;
+    vcam::pinhole_project(c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2, X, Y, Z, u, v);
+}
+// the other models (camera_model.h).  The branch on the slot's model is uniform (one sequence per workgroup or grid row), so a PINHOLE
+// slot runs the code above only.  Inline: an out-of-line call would not help, since a kernel's register count includes its callees' and
+// the call itself raises the caller's.  The ray is (x, y, z), not normalised, as liftProjective returns it.
+__device__ __forceinline__ void cam_predict_model(const vio_camera *cam, const double *R, float2 p, float2 *out) {
+    const vio_camera K = *cam;
+    double x, y, z;
+    vcam::lift(K, p.x, p.y, x, y, z);
+    double X = R[0] * x + R[1] * y + R[2] * z, Y = R[3] * x + R[4] * y + R[5] * z, Z = R[6] * x + R[7] * y + R[8] * z;
+    double u, v;
+    vcam::project(K, X, Y, Z, u, v);
+    *out = make_float2((float)u, (float)v);
+}
+// rejectWithF's virtual pinhole (feature_tracker.cpp:450-457): FOCAL_LENGTH * b.x / b.z + COL / 2, evaluated left to right
+__device__ __forceinline__ void cam_virtual_pinhole_model(const vio_camera *cam, double f, double hc, double hr, const float2 *cur, const float2 *forw,
+                                                       int n, double *X1, double *Y1, double *X2, double *Y2) {
+    const vio_camera K = *cam;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        double x, y, z;
+        vcam::lift(K, cur[i].x, cur[i].y, x, y, z);
+        float ux = (float)(f * x / z + hc), uy = (float)(f * y / z + hr);
+        X1[i] = ((double)ux - hc) / f; Y1[i] = ((double)uy - hr) / f;
+        vcam::lift(K, forw[i].x, forw[i].y, x, y, z);
+        ux = (float)(f * x / z + hc); uy = (float)(f * y / z + hr);
+        X2[i] = ((double)ux - hc) / f; Y2[i] = ((double)uy - hr) / f;
+    }
+}
+// undistortedPoints (feature_tracker.cpp:555): b.x / b.z, b.y / b.z
+__device__ __forceinline__ float2 cam_undistort_model(const vio_camera *cam, float2 p) {
+    double x, y;
+    vcam::lift_plane(*cam, p.x, p.y, x, y);
+    return make_float2((float)x, (float)y);
 }
 
 // mask(p) == 0 <=> p lies in the cv::circle(filled, r = MIN_DIST) raster of some accepted centre
@@ -549,6 +562,7 @@ __global__ void fe_predict_kernel(Batch B) {
     if (i >= fe.n_pts) return;
     float2 p = B.cur_pts[(size_t)s * C.NP + i];
     if (!C.c.use_imu) { B.forw_pts[(size_t)s * C.NP + i] = p; return; }   // feature_tracker.cpp:307-311: nextPts start at prevPts
+    if (cam_of(B, s)->model != VIO_CAMERA_PINHOLE) { cam_predict_model(cam_of(B, s), fe.R_rel, p, B.forw_pts + (size_t)s * C.NP + i); return; }
     const vio_calibration K = B.cal[s];
     double x, y;
     cam_lift(K, p.x, p.y, x, y);
@@ -557,6 +571,19 @@ __global__ void fe_predict_kernel(Batch B) {
     double u, v;
     cam_project(K, X, Y, Z, u, v);
     B.forw_pts[(size_t)s * C.NP + i] = make_float2((float)u, (float)v);
+}
+
+__global__ __launch_bounds__(256) void fe_camera_stage_kernel(vio_camera cam, int n, const double *uv, const double *R9, double *ray, double *un,
+                                                              double *uv_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double x, y, z;
+    vcam::lift(cam, uv[2 * i], uv[2 * i + 1], x, y, z);
+    ray[3 * i] = x; ray[3 * i + 1] = y; ray[3 * i + 2] = z;
+    vcam::lift_plane(cam, uv[2 * i], uv[2 * i + 1], un[2 * i], un[2 * i + 1]);
+    const double *R = R9;
+    double X = R[0] * x + R[1] * y + R[2] * z, Y = R[3] * x + R[4] * y + R[5] * z, Z = R[6] * x + R[7] * y + R[8] * z;
+    vcam::project(cam, X, Y, Z, uv_out[2 * i], uv_out[2 * i + 1]);
 }
 
 // ------------------------------------------------------------------------------------------------ fe_lk
@@ -962,7 +989,8 @@ __global__ __launch_bounds__(256) void fe_select_kernel(Batch B) {
         if (n >= 8) {
             double hc = c.width / 2.0, hr = c.height / 2.0;
             const vio_calibration K = B.cal[s];
-            for (int i = t; i < n; i += blockDim.x) {
+            if (cam_of(B, s)->model != VIO_CAMERA_PINHOLE) cam_virtual_pinhole_model(cam_of(B, s), c.focal_length, hc, hr, cur, forw, n, X1, Y1, X2, Y2);
+            else for (int i = t; i < n; i += blockDim.x) {
                 double x, y;
                 cam_lift(K, cur[i].x, cur[i].y, x, y);
                 float ux = (float)(c.focal_length * x + hc), uy = (float)(c.focal_length * y + hr);
@@ -1470,12 +1498,21 @@ __global__ __launch_bounds__(256) void fe_add_kernel(Batch B, int gate) {
     double dt = fe.cur_time - fe.prev_time;
     int *newflag = flag, *newoff = offs;  // n <= NP <= VIO_FAST_CAP is checked at create time
     const vio_calibration K = B.cal[s];
+    const bool pinhole = cam_of(B, s)->model == VIO_CAMERA_PINHOLE;
+    // the other models lift in a loop of their own (each thread writes the points it reads back below)
+    if (!pinhole)
+        for (int i = t; i < n; i += blockDim.x) g_un[i] = cam_undistort_model(cam_of(B, s), g_forw[i]);
     for (int i = t; i < n; i += blockDim.x) {
         float2 p = g_forw[i];
         g_cur[i] = p;
-        double x, y;
-        cam_lift(K, p.x, p.y, x, y);
-        float2 u = make_float2((float)x, (float)y);
+        float2 u;
+        if (pinhole) {
+            double x, y;
+            cam_lift(K, p.x, p.y, x, y);
+            u = make_float2((float)x, (float)y);
+        } else {
+            u = g_un[i];
+        }
         g_un[i] = u;
         float2 vel = make_float2(0.f, 0.f);
         int idv = g_id[i];

@@ -38,6 +38,8 @@ __global__ void fe_predict_kernel(Batch B);
 __global__ void fe_lk_kernel(Batch B);
 __global__ void fe_lk_stage_kernel(LkImages im, int maxLevel, int n, const float2 *prevPts, float2 *nextPts, uint8_t *status);
 __global__ void fe_ransac_stage_kernel(vio_config c, int n, const float2 *p1, const float2 *p2, uint8_t *status);
+// vio_stage_camera: camera_model.h through the tracker's device code (lift, x / z and y / z, spaceToPlane(R * ray)); R9 = 9 doubles
+__global__ void fe_camera_stage_kernel(vio_camera cam, int n, const double *uv, const double *R9, double *ray, double *un, double *uv_out);
 __global__ void fe_select_kernel(Batch B);
 __global__ void fe_fast_kernel(Batch B);
 __global__ void fe_fast_stage_kernel(const uint8_t *img, int W, GridRect r, uint32_t *out, int cap, int *count);

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "../../include/vio_posegraph.h"
+#include "camera_model.h"
 
 extern thread_local std::string g_err;   // vio_abi.hip
 
@@ -161,6 +162,15 @@ __global__ void pg_lift_kernel(vio_config c, const float *xy, int n, float *nrm)
     nrm[2 * i] = (float)mx_u; nrm[2 * i + 1] = (float)my_u;
 }
 
+// the same through a camera model (KeyFrame::computeBRIEFPoint, keyframe.cpp:114-124): (x / z, y / z) of m_camera->liftProjective
+__global__ void pg_lift_camera_kernel(vio_camera cam, const float *xy, int n, float *nrm) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double x, y;
+    vcam::lift_plane(cam, xy[2 * i], xy[2 * i + 1], x, y);
+    nrm[2 * i] = (float)x; nrm[2 * i + 1] = (float)y;
+}
+
 // one wavefront per window descriptor
 __global__ __launch_bounds__(64) void pg_match_kernel(const unsigned long long *wd, int n, const unsigned long long *od, int m, int *best_index, int *best_dist) {
     const int i = blockIdx.x, lane = threadIdx.x;
@@ -209,8 +219,9 @@ extern "C" int vio_pg_stage_blur(const uint8_t *gray, int width, int height, uin
     return VIO_OK;
 }
 
-extern "C" int vio_pg_describe(const vio_config *cfg, const uint8_t *gray, int n_win, const float *win_uv, const int32_t *pattern1024, int fast_threshold,
-                               uint64_t *win_desc, int cap, float *kp_xy, uint64_t *kp_desc, float *kp_norm) {
+// vio_pg_describe (cam == nullptr: cfg's pinhole) and vio_pg_describe_camera
+static int pg_describe(const vio_config *cfg, const vio_camera *cam, const uint8_t *gray, int n_win, const float *win_uv, const int32_t *pattern1024,
+                       int fast_threshold, uint64_t *win_desc, int cap, float *kp_xy, uint64_t *kp_desc, float *kp_norm) {
     if (!cfg || !gray || !pattern1024 || n_win < 0 || cap < 0 || (n_win > 0 && (!win_uv || !win_desc)) || (cap > 0 && (!kp_xy || !kp_desc || !kp_norm))) return VIO_EINVAL;
     const int W = cfg->width, H = cfg->height;
     if (W < 16 || H < 16 || W > 4095 || H > 4095 || fast_threshold < 1 || fast_threshold > 254) return VIO_EINVAL;
@@ -236,7 +247,8 @@ extern "C" int vio_pg_describe(const vio_config *cfg, const uint8_t *gray, int n
     const int m = total < cap ? total : cap;
     if (m > 0) {
         pg_brief_kernel<<<m, 64>>>(blur.as<uint8_t>(), W, H, kxy.as<float>(), m, pat.as<int>(), kdesc.as<unsigned long long>());
-        pg_lift_kernel<<<(m + 255) / 256, 256>>>(*cfg, kxy.as<float>(), m, knrm.as<float>());
+        if (cam) pg_lift_camera_kernel<<<(m + 255) / 256, 256>>>(*cam, kxy.as<float>(), m, knrm.as<float>());
+        else pg_lift_kernel<<<(m + 255) / 256, 256>>>(*cfg, kxy.as<float>(), m, knrm.as<float>());
     }
     PGCHK(hipDeviceSynchronize());
     if (n_win > 0) PGCHK(hipMemcpy(win_desc, wdesc.p, (size_t)n_win * 32, hipMemcpyDeviceToHost));
@@ -246,6 +258,18 @@ extern "C" int vio_pg_describe(const vio_config *cfg, const uint8_t *gray, int n
         PGCHK(hipMemcpy(kp_norm, knrm.p, (size_t)m * 8, hipMemcpyDeviceToHost));
     }
     return total;
+}
+
+extern "C" int vio_pg_describe(const vio_config *cfg, const uint8_t *gray, int n_win, const float *win_uv, const int32_t *pattern1024, int fast_threshold,
+                               uint64_t *win_desc, int cap, float *kp_xy, uint64_t *kp_desc, float *kp_norm) {
+    return pg_describe(cfg, nullptr, gray, n_win, win_uv, pattern1024, fast_threshold, win_desc, cap, kp_xy, kp_desc, kp_norm);
+}
+
+extern "C" int vio_pg_describe_camera(const vio_config *cfg, const vio_camera *cam, const uint8_t *gray, int n_win, const float *win_uv,
+                                      const int32_t *pattern1024, int fast_threshold, uint64_t *win_desc, int cap, float *kp_xy, uint64_t *kp_desc,
+                                      float *kp_norm) {
+    if (!cam) return VIO_EINVAL;
+    return pg_describe(cfg, cam, gray, n_win, win_uv, pattern1024, fast_threshold, win_desc, cap, kp_xy, kp_desc, kp_norm);
 }
 
 extern "C" int vio_pg_match(const uint64_t *win_desc, int n, const uint64_t *old_desc, int m, int32_t *best_index, int32_t *best_dist) {

@@ -126,7 +126,7 @@ void vio_synth_imu(const vio_synth_config *c, uint64_t seq, int n, double *t, do
     }
 }
 
-void vio_synth_render_host(const vio_synth_config *c, uint64_t seq, double t, uint8_t *gray, uint16_t *depth_mm) {
+void vio_synth_render_host_camera(const vio_synth_config *c, const vio_camera *cam, uint64_t seq, double t, uint8_t *gray, uint16_t *depth_mm) {
     TrajParams tp = traj_params(c, seq);
     double p[3], R[9];
     pose_at(c, tp, t, p, R);
@@ -143,29 +143,19 @@ void vio_synth_render_host(const vio_synth_config *c, uint64_t seq, double t, ui
     // the undistorted ray of every pixel depends on the camera only: computed once per camera (the device renderer keeps the same table)
     static std::mutex mu;
     static std::vector<float> rays;
-    static vio_synth_config key;
-    static bool valid = false;
+    static RayKey key;
     const float *rp;
     std::vector<float> mine;
     {
         // the table is validated (or built) and copied in ONE critical section: between two, a thread rendering another camera could swap
         // in its own table, and this one would render with the wrong camera's rays (or read past a smaller table)
         std::lock_guard<std::mutex> lk(mu);
-        const bool same = valid && key.width == c->width && key.height == c->height && key.fx == c->fx && key.fy == c->fy && key.cx == c->cx &&
-                          key.cy == c->cy && key.k1 == c->k1 && key.k2 == c->k2 && key.p1 == c->p1 && key.p2 == c->p2;
-        if (!same) {
+        if (!ray_key_same(key, c, cam)) {
             // (a new table, never resized in place)
             std::vector<float> nr((size_t)c->width * c->height * 2);
-            for (int y = 0; y < c->height; y++)
-                for (int x = 0; x < c->width; x++) {
-                    double rx, ry;
-                    syn_lift(c, (double)x, (double)y, &rx, &ry);
-                    nr[2 * ((size_t)y * c->width + x)] = (float)rx;
-                    nr[2 * ((size_t)y * c->width + x) + 1] = (float)ry;
-                }
+            build_rays(c, cam, nr.data());
             rays.swap(nr);
-            key = *c;
-            valid = true;
+            key = ray_key(c, cam);
         }
         mine = rays;   // 2.4 MB copy per frame (a frame costs ~100 ms): no lifetime questions when cameras alternate between threads
     }
@@ -175,6 +165,10 @@ void vio_synth_render_host(const vio_synth_config *c, uint64_t seq, double t, ui
             const size_t i = (size_t)y * c->width + x;
             render_pixel(seed, cp, rp[2 * i], rp[2 * i + 1], &gray[i], &depth_mm[i]);
         }
+}
+
+void vio_synth_render_host(const vio_synth_config *c, uint64_t seq, double t, uint8_t *gray, uint16_t *depth_mm) {
+    vio_synth_render_host_camera(c, nullptr, seq, t, gray, depth_mm);
 }
 
 }  // extern "C"

@@ -25,36 +25,27 @@ __global__ __launch_bounds__(256) void synth_render_kernel(vio_synth_config c, i
 
 namespace {
 struct RayCache {
-    vio_synth_config key;
+    RayKey key{};
     float *d_rays = nullptr;
-    bool valid = false;
 };
 RayCache g_rays;
 std::mutex g_mu;
 }  // namespace
 
-extern "C" int vio_synth_render_device(const vio_synth_config *c, int S, uint64_t seq0, double t, uint8_t *d_gray, uint16_t *d_depth_mm,
-                                       void *stream) {
+extern "C" int vio_synth_render_device_camera(const vio_synth_config *c, const vio_camera *cam, int S, uint64_t seq0, double t, uint8_t *d_gray,
+                                              uint16_t *d_depth_mm, void *stream) {
     std::lock_guard<std::mutex> lk(g_mu);
     hipStream_t st = (hipStream_t)stream;
     int npx = c->width * c->height;
-    bool same = g_rays.valid && g_rays.key.width == c->width && g_rays.key.height == c->height && g_rays.key.fx == c->fx &&
-                g_rays.key.fy == c->fy && g_rays.key.cx == c->cx && g_rays.key.cy == c->cy && g_rays.key.k1 == c->k1 &&
-                g_rays.key.k2 == c->k2 && g_rays.key.p1 == c->p1 && g_rays.key.p2 == c->p2;
-    if (!same) {
+    if (!ray_key_same(g_rays.key, c, cam)) {
         if (g_rays.d_rays) (void)hipFree(g_rays.d_rays);
+        g_rays.d_rays = nullptr;
+        g_rays.key.valid = false;
         std::vector<float> rays((size_t)npx * 2);
-        for (int y = 0; y < c->height; y++)
-            for (int x = 0; x < c->width; x++) {
-                double rx, ry;
-                syn_lift(c, (double)x, (double)y, &rx, &ry);
-                rays[2 * ((size_t)y * c->width + x)] = (float)rx;
-                rays[2 * ((size_t)y * c->width + x) + 1] = (float)ry;
-            }
+        build_rays(c, cam, rays.data());
         if (hipMalloc(&g_rays.d_rays, rays.size() * sizeof(float)) != hipSuccess) return -2;
         if (hipMemcpy(g_rays.d_rays, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return -2;
-        g_rays.key = *c;
-        g_rays.valid = true;
+        g_rays.key = ray_key(c, cam);
     }
     std::vector<float> poses((size_t)S * 12);
     for (int s = 0; s < S; s++) {
@@ -77,4 +68,9 @@ extern "C" int vio_synth_render_device(const vio_synth_config *c, int S, uint64_
     hipError_t e = hipStreamSynchronize(st);
     (void)hipFree(d_poses);
     return e == hipSuccess ? 0 : -2;
+}
+
+extern "C" int vio_synth_render_device(const vio_synth_config *c, int S, uint64_t seq0, double t, uint8_t *d_gray, uint16_t *d_depth_mm,
+                                       void *stream) {
+    return vio_synth_render_device_camera(c, nullptr, S, seq0, t, d_gray, d_depth_mm, stream);
 }

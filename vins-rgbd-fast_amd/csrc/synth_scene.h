@@ -13,6 +13,8 @@
 #endif
 
 #include "../../include/vio_synth.h"
+#include "camera_model.h"
+#include <string.h>
 
 namespace vsyn {
 
@@ -136,6 +138,48 @@ VIO_HD void syn_lift(const vio_synth_config *c, double u, double v, double *x, d
     }
     *x = mx;
     *y = my;
+}
+
+// the ray table's entry of pixel (u, v): (x / z, y / z) of c's pinhole (cam == nullptr) or of the camera model
+VIO_HD void syn_ray(const vio_synth_config *c, const vio_camera *cam, double u, double v, double *x, double *y) {
+    if (!cam) { syn_lift(c, u, v, x, y); return; }
+    if (cam->model == VIO_CAMERA_PINHOLE) {
+        vio_synth_config k = *c;
+        k.fx = cam->p[0]; k.fy = cam->p[1]; k.cx = cam->p[2]; k.cy = cam->p[3]; k.k1 = cam->p[4]; k.k2 = cam->p[5]; k.p1 = cam->p[6]; k.p2 = cam->p[7];
+        syn_lift(&k, u, v, x, y);
+        return;
+    }
+    vcam::lift_plane(*cam, u, v, *x, *y);
+}
+// what a ray table depends on: the image size and the camera (c's pinhole fields, or the whole vio_camera)
+struct RayKey {
+    vio_synth_config c;
+    vio_camera cam;
+    bool has_cam, valid;
+};
+inline bool ray_key_same(const RayKey &k, const vio_synth_config *c, const vio_camera *cam) {
+    if (!k.valid || k.c.width != c->width || k.c.height != c->height || k.has_cam != (cam != nullptr)) return false;
+    if (cam) return k.cam.model == cam->model && memcmp(k.cam.p, cam->p, sizeof(cam->p)) == 0;
+    return k.c.fx == c->fx && k.c.fy == c->fy && k.c.cx == c->cx && k.c.cy == c->cy && k.c.k1 == c->k1 && k.c.k2 == c->k2 && k.c.p1 == c->p1 &&
+           k.c.p2 == c->p2;
+}
+inline RayKey ray_key(const vio_synth_config *c, const vio_camera *cam) {
+    RayKey k;
+    memset(&k, 0, sizeof(k));
+    k.c = *c;
+    if (cam) k.cam = *cam;
+    k.has_cam = cam != nullptr;
+    k.valid = true;
+    return k;
+}
+inline void build_rays(const vio_synth_config *c, const vio_camera *cam, float *rays) {
+    for (int y = 0; y < c->height; y++)
+        for (int x = 0; x < c->width; x++) {
+            double rx, ry;
+            syn_ray(c, cam, (double)x, (double)y, &rx, &ry);
+            rays[2 * ((size_t)y * c->width + x)] = (float)rx;
+            rays[2 * ((size_t)y * c->width + x) + 1] = (float)ry;
+        }
 }
 
 struct CamPose { float R[9]; float p[3]; };  // world <- camera

@@ -12,6 +12,7 @@
 #include <vector>
 #include "kernels.h"
 #include "dyninit_host.h"
+#include "camera_model.h"
 
 thread_local std::string g_err;   // last failure of the calling thread (vio_last_error); also set by pg_kernels.hip / posegraph_host.cpp
 
@@ -110,6 +111,9 @@ struct vio_batch {
     // estimate_extrinsic = 2 handles)
     std::vector<vio_calibration> cal;
     vio_calibration *d_cal = nullptr;
+    // per-sequence camera model (vio_set_camera): host mirror of the device table (cam_of, after B.cal).  A PINHOLE slot's parameters live in cal (vio_get_camera reads them there)
+    std::vector<vio_camera> cam;
+    vio_camera *d_cam = nullptr;
     // ---- dynamic initialisation (static_init: 0): host mirror of Estimator::all_image_frame per sequence while it is INITIAL
     struct DynSeq {
         std::vector<vinit::ImageFrame> frames;
@@ -276,6 +280,16 @@ void cal_into_config(const vio_calibration &k, vio_config &c) {
     for (int i = 0; i < 3; i++) c.tic[i] = k.tic[i];
     c.td = k.td; c.tr = k.tr;
     c.acc_n = k.acc_n; c.acc_w = k.acc_w; c.gyr_n = k.gyr_n; c.gyr_w = k.gyr_w; c.g_norm = k.g_norm;
+}
+
+// the PINHOLE vio_camera of a calibration's fx..p2
+vio_camera pinhole_camera(const vio_calibration &k) {
+    vio_camera m;
+    memset(&m, 0, sizeof(m));
+    m.model = VIO_CAMERA_PINHOLE;
+    const double p[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
+    for (int i = 0; i < 8; i++) m.p[i] = p[i];
+    return m;
 }
 
 template <class T> int dalloc(vio_batch *h, T **p, size_t n) {
@@ -1016,7 +1030,10 @@ vio_batch *vio_create_on_device(const vio_config *cfg, int n_seq, int imu_capaci
     int rc = VIO_OK;
 #define DA(ptr, n) if (rc == VIO_OK) rc = dalloc(h, &ptr, (size_t)(n))
     DA(B.cfg, 1); DA(B.fe, S); DA(B.be, S); DA(B.pre, S * (C.W + 2));
-    DA(h->d_cal, S); B.cal = h->d_cal;
+    // the camera table follows the calibration table (cam_of, vio_state.h)
+    static_assert(sizeof(vio_calibration) % alignof(vio_camera) == 0, "camera table alignment");
+    DA(h->d_cal, S * (sizeof(vio_calibration) + sizeof(vio_camera)) / sizeof(vio_calibration) + 1); B.cal = h->d_cal;
+    h->d_cam = (vio_camera *)(h->d_cal + S);
     DA(B.img, S * 2 * HW); DA(B.pyr, S * 2 * (size_t)C.pyr_bytes);
     if (C.c.equalize) { DA(B.clahe_lut, S * 64 * 256); DA(B.clahe_img, S * HW); }
     DA(B.cur_pts, S * NP); DA(B.forw_pts, S * NP); DA(B.cur_un_pts, S * NP); DA(B.pts_velocity, S * NP); DA(B.prev_un_pt, S * NP);
@@ -1107,6 +1124,10 @@ vio_batch *vio_create_on_device(const vio_config *cfg, int n_seq, int imu_capaci
         cal_from_config(C.c, k);
         h->cal.assign(n_seq, k);
         if (hipMemcpy(h->d_cal, h->cal.data(), sizeof(vio_calibration) * n_seq, hipMemcpyHostToDevice) != hipSuccess) { g_err = "calibration upload failed"; rc = VIO_EDEVICE; }
+        // and the PINHOLE model of the configuration
+        vio_camera m = pinhole_camera(k);
+        h->cam.assign(n_seq, m);
+        if (rc == VIO_OK && hipMemcpy(h->d_cam, h->cam.data(), sizeof(vio_camera) * n_seq, hipMemcpyHostToDevice) != hipSuccess) { g_err = "camera upload failed"; rc = VIO_EDEVICE; }
     }
     if (rc == VIO_OK) { h->last_imu_t.assign(n_seq, -1e300); rc = init_state(h, 0, n_seq); }
     if (rc == VIO_OK) for (auto &g : h->groups) (void)hipEventRecord(g.ev_be, g.stream);
@@ -1501,7 +1522,7 @@ int vio_feed_modes(vio_batch *h, const uint8_t *gray, const uint16_t *depth_mm, 
     return VIO_OK;
 }
 
-int vio_abi_version(void) { return 10; }
+int vio_abi_version(void) { return 11; }
 
 // marg_exact = 2 (the literal marginalisation with a CERTIFIED first inverse): out2 = {marginalisations of sequence seq whose certificate failed
 // since vio_create / vio_reset -- those frames used the block inverse WITHOUT the proof that the reference's 1e-8 cut drops nothing --, 1 if the
@@ -1832,7 +1853,8 @@ int vio_device_upload(void *dst, const void *src, size_t bytes) { HIPCHK(hipMemc
 int vio_device_download(void *dst, const void *src, size_t bytes) { HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); return VIO_OK; }
 
 int vio_abi_sizeof(int what) {
-    return what == 0 ? (int)sizeof(vio_config) : what == 1 ? (int)sizeof(vio_status) : what == 2 ? (int)sizeof(vio_calibration) : -1;
+    return what == 0 ? (int)sizeof(vio_config) : what == 1 ? (int)sizeof(vio_status) : what == 2 ? (int)sizeof(vio_calibration)
+         : what == 3 ? (int)sizeof(vio_camera) : -1;
 }
 
 int vio_get_capacity(vio_batch *h, int32_t *out3) {
@@ -2031,6 +2053,81 @@ int vio_set_calibration(vio_batch *h, int seq, const vio_calibration *cal) {
 int vio_get_calibration(vio_batch *h, int seq, vio_calibration *out) {
     if (!h || !out || seq < 0 || seq >= h->S) { g_err = "vio_get_calibration: bad arguments"; return VIO_EINVAL; }
     *out = h->cal[seq];
+    return VIO_OK;
+}
+
+// vio_set_camera's validation: "" when cam is usable on a width x height image, else the message naming the offending field
+static std::string camera_check(const vio_camera &m, int width, int height) {
+    static const char *const names[3][9] = {{"fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", nullptr},
+                                            {"k2", "k3", "k4", "k5", "mu", "mv", "u0", "v0", nullptr},
+                                            {"xi", "k1", "k2", "p1", "p2", "gamma1", "gamma2", "u0", "v0"}};
+    if (m.model < VIO_CAMERA_PINHOLE || m.model > VIO_CAMERA_MEI) return "model is not VIO_CAMERA_PINHOLE, _KANNALA_BRANDT or _MEI";
+    if (m.reserved != 0) return "reserved must be 0";
+    const char *const *nm = names[m.model];
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(m.p[i])) return std::string(i < 9 && nm[i] ? nm[i] : "p[" + std::to_string(i) + "]") + " is not finite";
+    const int pos[3][2] = {{0, 1}, {4, 5}, {5, 6}};   // fx fy / mu mv / gamma1 gamma2
+    for (int j = 0; j < 2; j++)
+        if (!(m.p[pos[m.model][j]] > 0)) return std::string(nm[pos[m.model][j]]) + " must be > 0";
+    if (m.model == VIO_CAMERA_MEI && !(m.p[0] >= 0)) return "xi must be >= 0";
+    // the four corners and the four edge midpoints must lift in front of the camera: the unit-plane factors hold x / z, y / z
+    const double W1 = width - 1, H1 = height - 1;
+    const double pts[8][2] = {{0, 0}, {W1, 0}, {0, H1}, {W1, H1}, {W1 / 2, 0}, {W1 / 2, H1}, {0, H1 / 2}, {W1, H1 / 2}};
+    for (const auto &q : pts) {
+        double x, y, z;
+        vcam::lift(m, q[0], q[1], x, y, z);
+        if (!(std::isfinite(x) && std::isfinite(y) && std::isfinite(z) && z > 0)) {
+            char b[160];
+            snprintf(b, sizeof(b), "pixel (%g, %g) does not lift to a finite ray in front of the camera (z = %g): the field of view reaches 90 degrees",
+                     q[0], q[1], z);
+            return b;
+        }
+    }
+    return "";
+}
+
+int vio_set_camera(vio_batch *h, int seq, const vio_camera *cam) {
+    DevGuard dev_guard(h);
+    if (dev_guard.failed) { g_err = "hipSetDevice failed for the handle's device"; return VIO_EDEVICE; }
+    if (!h || !cam) { g_err = "vio_set_camera: bad arguments"; return VIO_EINVAL; }
+    if (seq < 0 || seq >= h->S) { g_err = "vio_set_camera: seq out of range"; return VIO_EINVAL; }
+    // validation first: the slot is left untouched by a refusal
+    const std::string why = camera_check(*cam, h->hc.c.width, h->hc.c.height);
+    if (!why.empty()) { g_err = "vio_set_camera: " + why; return VIO_EINVAL; }
+    vio_camera m = *cam;
+    vio_calibration k = h->cal[seq];
+    if (m.model == VIO_CAMERA_PINHOLE) {   // the pinhole parameters live in the calibration
+        k.fx = m.p[0]; k.fy = m.p[1]; k.cx = m.p[2]; k.cy = m.p[3]; k.k1 = m.p[4]; k.k2 = m.p[5]; k.p1 = m.p[6]; k.p2 = m.p[7];
+        m = pinhole_camera(k);
+    }
+    // a fresh slot, as vio_set_calibration
+    { int rc_ = sync_all(h); if (rc_ != VIO_OK) return rc_; }
+    { int rc_ = refresh_dynamic_state(h); if (rc_ != VIO_OK) return rc_; }
+    HIPCHK(hipMemcpy(h->d_cal + seq, &k, sizeof(vio_calibration), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_cam + seq, &m, sizeof(vio_camera), hipMemcpyHostToDevice));
+    h->cal[seq] = k;
+    h->cam[seq] = m;
+    return init_state(h, seq, seq + 1);
+}
+
+int vio_get_camera(vio_batch *h, int seq, vio_camera *out) {
+    if (!h || !out || seq < 0 || seq >= h->S) { g_err = "vio_get_camera: bad arguments"; return VIO_EINVAL; }
+    *out = h->cam[seq].model == VIO_CAMERA_PINHOLE ? pinhole_camera(h->cal[seq]) : h->cam[seq];
+    return VIO_OK;
+}
+
+int vio_stage_host_camera(const vio_camera *cam, int n, const double *uv, const double *R9, double *ray_out, double *un_out, double *uv_out) {
+    if (!cam || n < 0 || (n > 0 && !uv)) return VIO_EINVAL;
+    const double I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    const double *R = R9 ? R9 : I9;
+    for (int i = 0; i < n; i++) {
+        double x, y, z, X, Y, Z;
+        vcam::lift(*cam, uv[2 * i], uv[2 * i + 1], x, y, z);
+        if (ray_out) { ray_out[3 * i] = x; ray_out[3 * i + 1] = y; ray_out[3 * i + 2] = z; }
+        if (un_out) vcam::lift_plane(*cam, uv[2 * i], uv[2 * i + 1], un_out[2 * i], un_out[2 * i + 1]);
+        X = R[0] * x + R[1] * y + R[2] * z; Y = R[3] * x + R[4] * y + R[5] * z; Z = R[6] * x + R[7] * y + R[8] * z;
+        if (uv_out) vcam::project(*cam, X, Y, Z, uv_out[2 * i], uv_out[2 * i + 1]);
+    }
     return VIO_OK;
 }
 
@@ -2333,6 +2430,25 @@ done:
     if (d1) (void)hipFree(d1);
     if (d2) (void)hipFree(d2);
     if (ds) (void)hipFree(ds);
+    return rc;
+}
+
+int vio_stage_camera(const vio_camera *cam, int n, const double *uv, const double *R9, double *ray_out, double *un_out, double *uv_out) {
+    if (!cam || n < 0 || (n > 0 && !uv)) return VIO_EINVAL;
+    int rc = VIO_OK;
+    double *d = nullptr;
+    const double I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    const size_t m = (size_t)n + 1;   // uv(2) ray(3) un(2) uv_out(2) per point, R9
+    STAGE_CHK(hipMalloc((void **)&d, sizeof(double) * (9 * m + 9)));
+    STAGE_CHK(hipMemcpy(d, uv, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+    STAGE_CHK(hipMemcpy(d + 9 * m, R9 ? R9 : I9, sizeof(double) * 9, hipMemcpyHostToDevice));
+    if (n > 0) fe_camera_stage_kernel<<<(n + 255) / 256, 256>>>(*cam, n, d, d + 9 * m, d + 2 * m, d + 5 * m, d + 7 * m);
+    STAGE_CHK(hipDeviceSynchronize());
+    if (ray_out) STAGE_CHK(hipMemcpy(ray_out, d + 2 * m, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+    if (un_out) STAGE_CHK(hipMemcpy(un_out, d + 5 * m, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
+    if (uv_out) STAGE_CHK(hipMemcpy(uv_out, d + 7 * m, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
+done:
+    if (d) (void)hipFree(d);
     return rc;
 }
 

@@ -214,7 +214,8 @@ struct Batch {
     int eval_rpt;         // projection residuals per thread of ps_eval (VIO_EVAL_RPT: 1 = 256 per workgroup; 2 halves the workgroups of the launch)
     FeSeq *fe;
     BeSeq *be;
-    const vio_calibration *cal;   // [S] per-sequence calibration (vio_set_calibration): the only calibration source of device code
+    const vio_calibration *cal;   // [S] per-sequence calibration (vio_set_calibration): the only calibration source of device code,
+                                  // followed by the [S] per-sequence camera models (vio_set_camera, cam_of)
     PreInt *pre;          // [S][W+2]
     // ---- tracker arrays, stride NP per sequence
     uint8_t *img;         // [S][2][H*W] ping-pong level 0
@@ -276,6 +277,9 @@ struct Batch {
     float *fe_ticks;      // [S][4] debug: 100 MHz ticks fe_select / fe_add / fe_fast(max cell) of each sequence spent in the last frame
     SolveSt *sst;         // [S] phased solver state
 };
+// the camera model of sequence s (PINHOLE slots take fx..p2 from B.cal[s]); the table follows B.cal in the same allocation, so Batch, which
+// every kernel takes by value, keeps its layout
+DM_HD const vio_camera *cam_of(const Batch &B, int s) { return (const vio_camera *)(B.cal + B.S) + s; }
 
 #define VEC_SLOTS 24
 #define NRES_PER_LM VIO_MAXW

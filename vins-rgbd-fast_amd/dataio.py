@@ -101,10 +101,38 @@ def parse_opencv_yaml(text):
     return root
 
 
+# camodocal's key layout per model (CameraFactory.cc:99-125; EquidistantCamera.cc:171-176, CataCamera.cc:186-196): (section, key) in the
+# order of vio_camera::p
+_CAMERA_KEYS = {"KANNALA_BRANDT": [("projection_parameters", k) for k in ("k2", "k3", "k4", "k5", "mu", "mv", "u0", "v0")],
+                "MEI": [("mirror_parameters", "xi")] + [("distortion_parameters", k) for k in ("k1", "k2", "p1", "p2")] +
+                       [("projection_parameters", k) for k in ("gamma1", "gamma2", "u0", "v0")]}
+
+
+def _camera_from_yaml(y, P, need):
+    """model_type (matched case-insensitively, as CameraFactory does) -> a Camera, or None for PINHOLE (the pinhole keys are the config's).
+    A KANNALA_BRANDT or MEI file missing one of its model's keys is refused (strict) or noted once, keeping the file's pinhole keys."""
+    model = str(y.get("model_type", "PINHOLE")).upper()
+    if model == "PINHOLE":
+        return None
+    if model not in _CAMERA_KEYS:
+        need(True, "camera model %s is not supported (PINHOLE, KANNALA_BRANDT, MEI)" % model)
+        return None
+    keys = _CAMERA_KEYS[model]
+    missing = ["%s.%s" % (sec, k) for sec, k in keys if not isinstance(y.get(sec), dict) or k not in y[sec]]
+    if missing:
+        need(True, "model_type: %s needs %s; the pinhole keys of the file are used instead" % (model, ", ".join(missing)))
+        return None
+    vals = [float(y[sec][k]) for sec, k in keys]
+    return P.camera_kannala_brandt(*vals) if model == "KANNALA_BRANDT" else P.camera_mei(*vals)
+
+
 def config_from_yaml(path_or_text, P=None, strict=True):
     """vio_config from a reference configuration file (parameters.cpp:81-243).  Settings that select code paths outside the
-    built hot path (a camera model other than PINHOLE), or that discard part of the file (``estimate_extrinsic: 2``), raise ValueError when
-    strict; with strict=False they are returned in the second element as a list of notes.  ``estimate_extrinsic: 2`` then gives a mode-2
+    built hot path (SCARAMUZZA, or a KANNALA_BRANDT / MEI file that lacks one of its model's keys), or that discard part of the file
+    (``estimate_extrinsic: 2``), raise ValueError when strict; with strict=False they are returned in the second element as a list of notes.
+    ``model_type`` is matched case-insensitively; a KANNALA_BRANDT or MEI camera is returned as ``extra["camera"]`` (a Camera for
+    VioBatch.set_camera; None for PINHOLE, whose parameters are the config's).  A file without ``model_type`` is PINHOLE here, where
+    camodocal's CameraFactory would default to MEI.  ``estimate_extrinsic: 2`` then gives a mode-2
     configuration with ric = I and tic = 0 (parameters.cpp:181-190: the file's extrinsicRotation / extrinsicTranslation are ignored and the
     rotation is calibrated online, VioBatch.ex_calibration)."""
     if P is None:
@@ -141,7 +169,7 @@ def config_from_yaml(path_or_text, P=None, strict=True):
     for k in ("k1", "k2", "p1", "p2"):
         if k in dp:
             setattr(c, k, float(dp[k]))
-    need(str(g("model_type", "PINHOLE")).upper() != "PINHOLE", "only the PINHOLE camera model is on the hot path")
+    camera = _camera_from_yaml(y, P, need)
     c.estimate_extrinsic = int(g("estimate_extrinsic", 0))
     need(c.estimate_extrinsic == 2, "estimate_extrinsic: 2 (online extrinsic calibration) discards the file's extrinsicRotation / "
                                     "extrinsicTranslation (ric = I, tic = 0); strict=False accepts it")
@@ -176,7 +204,7 @@ def config_from_yaml(path_or_text, P=None, strict=True):
         warnings.warn(notes[-1], stacklevel=2)
     c.equalize = 1 if int(g("equalize", 0)) else 0   # parameters.cpp:110: CLAHE before tracking
     extra = dict(freq=int(g("freq", 0)), frontend_freq=int(g("frontend_freq", 0)), output_path=g("output_path", ""),
-                 max_solver_time=float(g("max_solver_time", 0.0)), fisheye_mask=fisheye_mask, notes=notes)
+                 max_solver_time=float(g("max_solver_time", 0.0)), fisheye_mask=fisheye_mask, notes=notes, camera=camera)
     return c, extra
 
 
@@ -201,7 +229,8 @@ _HANDLE_WIDE_KEYS = (("width", "image_width"), ("height", "image_height"), ("max
 
 def batch_config_from_yamls(paths, P=None, strict=True):
     """One handle for several rigs: returns (shared_cfg, [calibration per file], [extra per file]).  The files may differ in their
-    calibration (intrinsics, distortion, extrinsic, td, tr, IMU noise, gravity); a handle-wide setting on which two files disagree raises
+    calibration (intrinsics, distortion, extrinsic, td, tr, IMU noise, gravity) and camera model (extra["camera"] of each file, for
+    VioBatch.set_camera); a handle-wide setting on which two files disagree raises
     ValueError naming the configuration key.  The extras (freq / frontend_freq, ...) stay per file: replay_many gates every recording on
     its own."""
     if P is None:

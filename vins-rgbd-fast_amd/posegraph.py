@@ -25,6 +25,8 @@ def _lib():
     if not getattr(L, "_pg_bound", False):
         L.vio_pg_describe.argtypes = [C.POINTER(P.Config), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_void_p]
+        L.vio_pg_describe_camera.argtypes = [C.POINTER(P.Config), C.POINTER(P.Camera), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vio_pg_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.vio_pg_find_connection.argtypes = [C.c_int] + [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 5
         L.vio_pg_optimize4dof.argtypes = [C.c_int] + [C.c_void_p] * 8
@@ -77,9 +79,10 @@ def load_brief_pattern(path):
     return np.ascontiguousarray(out)
 
 
-def describe(cfg, gray, window_uv, pattern, fast_threshold=20, cap=8192):
+def describe(cfg, gray, window_uv, pattern, fast_threshold=20, cap=8192, camera=None):
     """computeWindowBRIEFPoint + computeBRIEFPoint: (window descriptors [n][4] u64, keypoints [m][2] f32, their descriptors, their normalised
-    coordinates)"""
+    coordinates).  camera: the sequence's Camera (VioBatch.camera(seq)) to lift the keypoints through (vio_pg_describe_camera); None = the
+    pinhole fields of cfg"""
     P, L = _lib()
     gray = np.ascontiguousarray(gray, np.uint8)
     assert gray.shape == (cfg.height, cfg.width)
@@ -88,12 +91,17 @@ def describe(cfg, gray, window_uv, pattern, fast_threshold=20, cap=8192):
     wd = np.zeros((max(n, 1), 4), np.uint64)
     kxy, kd, kn = np.zeros((cap, 2), np.float32), np.zeros((cap, 4), np.uint64), np.zeros((cap, 2), np.float32)
     pat = np.ascontiguousarray(pattern, np.int32)
-    m = _chk(P, L, L.vio_pg_describe(C.byref(cfg), gray.ctypes.data, n, uv.ctypes.data, pat.ctypes.data, int(fast_threshold), wd.ctypes.data, cap,
-                                     kxy.ctypes.data, kd.ctypes.data, kn.ctypes.data), "vio_pg_describe")
+    if camera is None:
+        m = _chk(P, L, L.vio_pg_describe(C.byref(cfg), gray.ctypes.data, n, uv.ctypes.data, pat.ctypes.data, int(fast_threshold), wd.ctypes.data,
+                                         cap, kxy.ctypes.data, kd.ctypes.data, kn.ctypes.data), "vio_pg_describe")
+    else:
+        m = _chk(P, L, L.vio_pg_describe_camera(C.byref(cfg), C.byref(camera), gray.ctypes.data, n, uv.ctypes.data, pat.ctypes.data,
+                                                int(fast_threshold), wd.ctypes.data, cap, kxy.ctypes.data, kd.ctypes.data, kn.ctypes.data),
+                 "vio_pg_describe_camera")
     if m > cap:
         # cv::FAST has no cap (keyframe.cpp:94-103): the compaction is row-major, a truncated list would lose the bottom of the image -- run
         # again with room for all of them
-        return describe(cfg, gray, window_uv, pattern, fast_threshold, cap=int(m))
+        return describe(cfg, gray, window_uv, pattern, fast_threshold, cap=int(m), camera=camera)
     return wd[:n], kxy[:m], kd[:m], kn[:m]
 
 
@@ -152,7 +160,8 @@ class KeyFrame:
     """KeyFrame (pose_graph/src/keyframe/keyframe.h): the online constructor computes the window descriptors and the FAST keypoints with their
     descriptors (keyframe.cpp:14-43), findConnection verifies a loop candidate chosen by the caller."""
 
-    def __init__(self, cfg, pattern, time_stamp, index, vio_T_w_i, vio_R_w_i, image, point_3d, point_2d_uv, point_2d_norm, point_id, sequence=1):
+    def __init__(self, cfg, pattern, time_stamp, index, vio_T_w_i, vio_R_w_i, image, point_3d, point_2d_uv, point_2d_norm, point_id, sequence=1,
+                 camera=None):
         self.time_stamp, self.index, self.sequence = float(time_stamp), int(index), int(sequence)
         self.vio_T_w_i = np.array(vio_T_w_i, np.float64); self.vio_R_w_i = np.array(vio_R_w_i, np.float64).reshape(3, 3)
         self.T_w_i, self.R_w_i = self.vio_T_w_i.copy(), self.vio_R_w_i.copy()
@@ -163,7 +172,8 @@ class KeyFrame:
         self.point_id = np.array(point_id, np.float64).reshape(-1)
         self.has_loop, self.loop_index, self.loop_info = False, -1, np.zeros(8)
         self.match_points = np.zeros((0, 3))
-        self.window_brief_descriptors, kxy, self.brief_descriptors, kn = describe(cfg, image, self.point_2d_uv, pattern)
+        # m_camera: the sequence's camera model (None = cfg's pinhole)
+        self.window_brief_descriptors, kxy, self.brief_descriptors, kn = describe(cfg, image, self.point_2d_uv, pattern, camera=camera)
         self.keypoints, self.keypoints_norm = kxy, kn
 
     @classmethod
