@@ -222,8 +222,9 @@ int vio_device_download(void *dst_host, const void *src_device, size_t bytes);
  * memory the runtime stages every copy).  NULL on failure. */
 void *vio_host_alloc(size_t bytes);
 void vio_host_free(void *p);
-/* sizeof(vio_config) (what = 0) / sizeof(vio_status) (what = 1) / sizeof(vio_calibration) (what = 2) / sizeof(vio_camera) (what = 3) as
- * compiled into the library: lets a binding check its struct mirrors */
+/* sizeof(vio_config) (what = 0) / sizeof(vio_status) (what = 1) / sizeof(vio_calibration) (what = 2) / sizeof(vio_camera) (what = 3) /
+ * sizeof(vio_snapshot_header) (what = 4) / sizeof(vio_snapshot_shape) (what = 5) as compiled into the library: lets a binding check its
+ * struct mirrors */
 int vio_abi_sizeof(int what);
 /* Contract version of this header: 4 = a vio_feed host image set is free when the next vio_feed has returned; 5 = two uploads in flight (see
  * "Host buffers" above, vio_host_buffers_done); 6 = + vio_get_bound_stats, the inverse-depth bound handled as Ceres does (projected line search);
@@ -233,7 +234,8 @@ int vio_abi_sizeof(int what);
  * vio_stage_spd_inverse16, vio_stage_scan_flags, vio_stage_schur, vio_stage_pinv15, vio_stage_chol blocks = -8 / -9); 10 = + per-sequence
  * calibration (vio_calibration, vio_calibration_from_config, vio_set_calibration, vio_get_calibration, vio_abi_sizeof(2)); 11 = + per-sequence
  * camera models (vio_camera, vio_set_camera, vio_get_camera, vio_stage_camera, vio_stage_host_camera, vio_abi_sizeof(3);
- * vio_synth_render_host_camera / _device_camera in vio_synth.h, vio_pg_describe_camera in vio_posegraph.h). */
+ * vio_synth_render_host_camera / _device_camera in vio_synth.h, vio_pg_describe_camera in vio_posegraph.h); 12 = + sequence snapshots
+ * (vio_snapshot_header, vio_shape_key, vio_snapshot_bytes, vio_save_seqs, vio_load_seqs, vio_snapshot_info, vio_abi_sizeof(4) / (5)). */
 int vio_abi_version(void);
 /* capacities derived from the configuration: out[0] = tracker points per sequence, out[1] = landmark slots, out[2] = IMU ring */
 int vio_get_capacity(vio_batch *h, int32_t *out3);
@@ -366,6 +368,77 @@ int vio_get_calibration(vio_batch *h, int seq, vio_calibration *out);
 int vio_set_camera(vio_batch *h, int seq, const vio_camera *cam);
 /* The camera of seq (PINHOLE: p[] = the calibration's fx..p2). */
 int vio_get_camera(vio_batch *h, int seq, vio_camera *out);
+/* ---- sequence snapshots (ABI 12): take a running sequence out of a slot and put it into another one ----
+ * A snapshot is one self-describing blob in HOST memory (pageable or page-locked) that holds everything the next vio_feed / vio_track /
+ * vio_process* of that sequence reads: tracker and estimator records, the W + 2 pre-integrations, both ping-pong images and pyramids, the
+ * tracker arrays, the packaged observations, the IMU ring (samples pushed for future frames included), the landmark table, the prior, a
+ * pending relocalisation request, the odometry rows, the sticky counters, the mode-2 extrinsic calibration and its pair ring, the slot's
+ * vio_calibration and vio_camera, and the host side (the last IMU stamp; on dynamic_init handles the image-frame mirror of a sequence that is
+ * still INITIAL, which is the variable-length part).  Per-frame scratch is not saved.  A blob restores into ANY slot of ANY handle whose
+ * shape key and tracker lag equal the source's: the batch size, the slot index, the device and the process may all differ, and the restored
+ * sequence continues bit for bit like the original.  NOT in a snapshot, the caller's to set equal on both sides: the fisheye mask
+ * (handle-wide), the VIO_* environment knobs read at vio_create, profiling state, and caller-side state such as a frame gate.
+ *
+ * Layout: vio_snapshot_header | device part (the state arrays of the slot in the order of the layout table, DESIGN.md 6d, every entry on a
+ * 16-byte boundary) | host part.  All padding is zero: equal states give equal bytes. */
+#define VIO_SNAPSHOT_MAGIC 0x0050414E534F4956ULL   /* "VIOSNAP\0", little endian */
+#define VIO_SNAPSHOT_FORMAT 1
+/* Shape key: every configuration value that sizes an array or selects a code path, i.e. vio_config without the fields of
+ * vio_calibration, plus the capacities fixed at vio_create.  Two handles exchange snapshots exactly when their keys are equal. */
+typedef struct vio_snapshot_shape {
+    int32_t width, height, max_cnt, min_dist, grid_rows, grid_cols, window_size, max_landmarks, fix_depth, estimate_extrinsic, estimate_td,
+        max_iterations, ransac_max_iters, lk_max_level, dynamic_init, use_imu, reference_quirks, marg_exact, equalize;
+    int32_t imu_capacity;     /* IMU ring size per sequence as vio_create rounds it (>= 256) */
+    int32_t hist_cap;         /* odometry rows kept per sequence */
+    int32_t pyramid_levels;   /* pyramid levels stored beside level 0 */
+    int32_t reserved[2];      /* 0 */
+    double focal_length, f_threshold, depth_min, depth_max, min_parallax_px, init_depth;
+} vio_snapshot_shape;
+typedef struct vio_snapshot_header {
+    uint64_t magic;             /* VIO_SNAPSHOT_MAGIC */
+    uint32_t format_version;    /* VIO_SNAPSHOT_FORMAT */
+    uint32_t abi_version;       /* vio_abi_version() of the library that wrote the blob */
+    int64_t total_bytes;        /* the whole blob = sizeof(vio_snapshot_header) + device_bytes + host_bytes */
+    int64_t device_bytes;       /* fixed by the shape key */
+    int64_t host_bytes;         /* variable (dynamic_init handles), a multiple of 16 */
+    int64_t frames_processed;   /* informational: vio_status.frames_processed of the sequence */
+    double last_stamp;          /* informational: header stamp of the last processed frame */
+    int32_t tracker_lag;        /* vio_set_tracker_lag of the source handle: must equal the destination's */
+    int32_t solver_flag;        /* informational: 0 INITIAL, 1 NON_LINEAR */
+    vio_snapshot_shape shape;
+} vio_snapshot_header;
+/* The shape key of a handle created with (cfg, imu_capacity).  Host only (no GPU, no handle).  Independent of the batch size and of every
+ * vio_calibration / vio_camera field. */
+int vio_shape_key(const vio_config *cfg, int imu_capacity, vio_snapshot_shape *out);
+/* Validates and describes a blob without a handle and without a GPU: magic, format version, the lengths against `bytes`; never reads beyond
+ * blob + bytes.  VIO_EINVAL (vio_last_error names the field) for NULL, an empty or short buffer, a wrong magic, an unknown format version or
+ * inconsistent lengths. */
+int vio_snapshot_info(const void *blob, int64_t bytes, vio_snapshot_header *out);
+/* Bytes vio_save_seqs would write for seq right now (the fixed device part + the variable host part); < 0 on error.  Synchronises the
+ * handle on dynamic_init handles (the host part depends on the last frame's outcome). */
+int64_t vio_snapshot_bytes(vio_batch *h, int seq);
+/* Saves n sequences: blob i starts at (char *)dst + offsets[i] and may use caps[i] bytes; bytes_out[i] (may be NULL) = bytes written.
+ * Save only READS the handle: it moves the IMU samples still staged on the host into the rings, waits for all work of the handle and picks up
+ * a pending reboot notice, as vio_reset_seq does, then copies; the handle continues exactly as if save had not been called.  The slices of
+ * the slots are gathered by one kernel per stream group into a device staging buffer (allocated at the first save / load of the handle, never
+ * at vio_create) and leave in ONE device-to-host copy when the blobs are packed back to back (offsets[i + 1] = offsets[i] + bytes of blob
+ * i, offsets multiples of 16), in one copy per blob otherwise.  VIO_EINVAL: bad slot, VIO_ECAPACITY: caps[i] too small (nothing written). */
+int vio_save_seqs(vio_batch *h, int n, const int32_t *seqs, void *dst, const int64_t *offsets, const int64_t *caps, int64_t *bytes_out);
+/* Restores n blobs (blob i at (const char *)src + offsets[i], bytes[i] long) into the n DISTINCT slots seqs[i].  Everything is validated
+ * before anything is written: magic, versions, lengths, the shape key and the tracker lag against the handle, the blob's calibration and camera
+ * as vio_set_calibration / vio_set_camera validate theirs; on any mismatch VIO_EINVAL, vio_last_error names the first field that differs,
+ * and every slot is untouched.  On success it synchronises like vio_reset_seq, drops the host-staged IMU of those slots, writes the slots
+ * (one host-to-device copy under the same packing rule, then one scatter kernel per stream group) and updates the handle's host mirrors.
+ * Other slots are not disturbed.  The same blob may be loaded into several slots (a fork). */
+int vio_load_seqs(vio_batch *h, int n, const int32_t *seqs, const void *src, const int64_t *offsets, const int64_t *bytes);
+/* test / measurement helpers: the blob of seq written the naive way, one hipMemcpy per layout-table entry (same bytes as vio_save_seqs;
+ * returns the bytes written or < 0), and what the handle has reserved on the device for snapshots: the staging buffer's bytes plus a
+ * non-zero count for the table and the sequence list; 0 until the first save / load of the handle. */
+int64_t vio_debug_save_seq_naive(vio_batch *h, int seq, void *dst, int64_t cap);
+int64_t vio_debug_snapshot_staging_bytes(vio_batch *h);
+/* The layout table: entry i of the table as (name, kind: 1 state / 0 scratch, bytes per sequence, offset inside the device part or -1);
+ * returns the number of entries (i out of range: that count, nothing written). */
+int vio_debug_snapshot_layout(vio_batch *h, int i, char *name64, int32_t *kind, int64_t *bytes_per_seq, int64_t *blob_offset);
 /* FeatureTracker public vectors after readImage (estimator_nodelet.cpp:337-343): returns count */
 int vio_get_tracks(vio_batch *h, int seq, int cap, int32_t *ids, int32_t *track_cnt, float *cur_pts_xy, float *cur_un_pts_xy,
                    float *pts_velocity_xy);

@@ -6,7 +6,10 @@
 The recording layout is described in vins-rgbd-fast_amd/dataio.py (RgbdImuDirectory).  --gt: ``stamp x y z ...`` ground truth
 (TUM format) for an ATE report.  Repeated --config / --data / --out triples replay several recordings in ONE handle, one slot each, every
 slot with the calibration of its own configuration file (dataio.batch_config_from_yamls: the files must agree on every handle-wide
-setting); --gt then applies to the first recording."""
+setting); --gt then applies to the first recording.
+
+    --save-at FRAME --snapshot FILE   (one recording) write the sequence's snapshot after frame FRAME to FILE, the replay's own state to FILE.json
+    --resume FILE                     (one recording) restore FILE and continue behind the saved frame; --out then holds the rows from there on"""
 import argparse
 import importlib
 import os
@@ -25,11 +28,18 @@ def parse_args(argv=None):
     ap.add_argument("--data", action="append", required=True)
     ap.add_argument("--out", action="append", default=None)
     ap.add_argument("--gt", default=None)
+    ap.add_argument("--save-at", type=int, default=None, help="frame index after which the snapshot is written (with --snapshot)")
+    ap.add_argument("--snapshot", default=None, help="snapshot file to write (its sidecar FILE.json holds the frame gate's state)")
+    ap.add_argument("--resume", default=None, help="snapshot file to restore before replaying the frames behind it")
     ap.add_argument("--lenient", action="store_true", help="warn instead of failing on settings outside the built hot path")
     a = ap.parse_args(argv)
     n = len(a.config)
     if len(a.data) != n:
         ap.error("%d --config but %d --data: give one --data per --config" % (n, len(a.data)))
+    if (a.save_at is None) != (a.snapshot is None):
+        ap.error("--save-at and --snapshot go together")
+    if n > 1 and (a.snapshot or a.resume):
+        ap.error("--snapshot / --resume work on one recording")
     outs = a.out if a.out is not None else (["vins_result.csv"] if n == 1 else ["vins_result_%d.csv" % i for i in range(n)])
     if len(outs) != n:
         ap.error("%d --config but %d --out: give one --out per --config, or none" % (n, len(outs)))
@@ -65,7 +75,8 @@ def main():
         b = P.VioBatch(cfg, 1, imu_capacity=1 << 15)
         if extra["camera"] is not None:   # KANNALA_BRANDT / MEI (dataio.config_from_yaml)
             b.set_camera(0, extra["camera"])
-        rows = io.replay(b, rec, out, freq=extra["freq"], frontend_freq=extra["frontend_freq"])  # freq / frontend_freq: estimator_nodelet.cpp:264-286
+        rows = io.replay(b, rec, out, freq=extra["freq"], frontend_freq=extra["frontend_freq"],
+                         save_at=a.save_at, snapshot=a.snapshot, resume=a.resume)  # freq / frontend_freq: estimator_nodelet.cpp:264-286
         print("%d frames, %d odometry rows -> %s" % (len(rec), len(rows), out))
     if a.gt and len(rows) > 3:
         gt = np.loadtxt(a.gt, comments="#", ndmin=2)

@@ -138,6 +138,42 @@ def stage_host_camera(cam, uv, R=None):
     return _stage_camera(lib().vio_stage_host_camera, cam, uv, R)
 
 
+SNAPSHOT_MAGIC, SNAPSHOT_FORMAT = 0x0050414E534F4956, 1
+
+
+class SnapshotShape(C.Structure):
+    """vio_snapshot_shape (include/vio_abi.h): the shape key of a handle; two handles exchange snapshots exactly when their keys are equal."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "width", "height", "max_cnt", "min_dist", "grid_rows", "grid_cols", "window_size", "max_landmarks", "fix_depth",
+        "estimate_extrinsic", "estimate_td", "max_iterations", "ransac_max_iters", "lk_max_level", "dynamic_init", "use_imu",
+        "reference_quirks", "marg_exact", "equalize", "imu_capacity", "hist_cap", "pyramid_levels")] + [("reserved", C.c_int32 * 2)] + \
+        [(n, C.c_double) for n in ("focal_length", "f_threshold", "depth_min", "depth_max", "min_parallax_px", "init_depth")]
+
+
+class SnapshotHeader(C.Structure):
+    """vio_snapshot_header (include/vio_abi.h): what every snapshot blob starts with."""
+    _fields_ = [("magic", C.c_uint64), ("format_version", C.c_uint32), ("abi_version", C.c_uint32), ("total_bytes", C.c_int64),
+                ("device_bytes", C.c_int64), ("host_bytes", C.c_int64), ("frames_processed", C.c_int64), ("last_stamp", C.c_double),
+                ("tracker_lag", C.c_int32), ("solver_flag", C.c_int32), ("shape", SnapshotShape)]
+
+
+def shape_key(cfg, imu_capacity=8192):
+    """vio_shape_key: the SnapshotShape of a handle created with (cfg, imu_capacity).  Host only: needs no GPU."""
+    k = SnapshotShape()
+    if lib().vio_shape_key(C.byref(cfg), int(imu_capacity), C.byref(k)) != 0:
+        raise VioError("vio_shape_key failed: %s" % lib().vio_last_error().decode())
+    return k
+
+
+def snapshot_info(blob):
+    """vio_snapshot_info: validates a snapshot blob (bytes or a uint8 array) and returns its SnapshotHeader.  Host only: needs no GPU."""
+    a = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, np.uint8).reshape(-1)
+    hd = SnapshotHeader()
+    if lib().vio_snapshot_info(a.ctypes.data if a.size else None, a.size, C.byref(hd)) != 0:
+        raise VioError("vio_snapshot_info failed: %s" % lib().vio_last_error().decode())
+    return hd
+
+
 class SynthConfig(C.Structure):
     """vio_synth_config (include/vio_synth.h)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32)] + \
@@ -230,6 +266,19 @@ def lib():
         L.vio_synth_render_host_camera.argtypes = [C.POINTER(SynthConfig), C.POINTER(Camera), C.c_uint64, C.c_double, C.c_void_p, C.c_void_p]
         L.vio_synth_render_device_camera.argtypes = [C.POINTER(SynthConfig), C.POINTER(Camera), C.c_int, C.c_uint64, C.c_double, C.c_void_p,
                                                      C.c_void_p, C.c_void_p]
+        L.vio_shape_key.argtypes = [C.POINTER(Config), C.c_int, C.POINTER(SnapshotShape)]
+        L.vio_snapshot_info.argtypes = [C.c_void_p, C.c_int64, C.POINTER(SnapshotHeader)]
+        L.vio_snapshot_bytes.restype = C.c_int64
+        L.vio_snapshot_bytes.argtypes = [C.c_void_p, C.c_int]
+        L.vio_save_seqs.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        L.vio_load_seqs.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        L.vio_debug_save_seq_naive.restype = C.c_int64
+        L.vio_debug_save_seq_naive.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
+        L.vio_debug_snapshot_staging_bytes.restype = C.c_int64
+        L.vio_debug_snapshot_staging_bytes.argtypes = [C.c_void_p]
+        L.vio_debug_snapshot_layout.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        if L.vio_abi_sizeof(4) != C.sizeof(SnapshotHeader) or L.vio_abi_sizeof(5) != C.sizeof(SnapshotShape):
+            raise VioError("vio_snapshot_header mirror does not match the library (%d != %d bytes)" % (C.sizeof(SnapshotHeader), L.vio_abi_sizeof(4)))
         if L.vio_abi_sizeof(2) != C.sizeof(Calibration):
             raise VioError("vio_calibration mirror does not match the library (%d != %d bytes)" % (C.sizeof(Calibration), L.vio_abi_sizeof(2)))
         L.vio_get_latest_odometry.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -449,6 +498,65 @@ class VioBatch:
         k = Camera()
         self._chk(self.L.vio_get_camera(self.h, int(seq), C.byref(k)), "vio_get_camera")
         return k
+
+    def snapshot_bytes(self, seq):
+        """vio_snapshot_bytes: bytes save([seq]) would produce for the slot right now"""
+        n = int(self.L.vio_snapshot_bytes(self.h, int(seq)))
+        if n < 0:
+            raise VioError("vio_snapshot_bytes failed (%d): %s" % (n, self.L.vio_last_error().decode()))
+        return n
+
+    def save(self, seqs, out=None):
+        """vio_save_seqs: one snapshot blob (uint8 array) per slot of seqs.  The handle is only read: it continues as if save had not been
+        called.  The blobs are views into ONE buffer, packed back to back, so the device part leaves in a single copy; out = an optional
+        uint8 buffer to pack them into (for instance PinnedArray(...).a), large enough for sum(snapshot_bytes)."""
+        seqs = np.ascontiguousarray(seqs, np.int32).reshape(-1)
+        n = len(seqs)
+        if any(not 0 <= int(s) < self.S for s in seqs):
+            raise VioError("vio_save_seqs failed (%d): seq out of range" % VIO_EINVAL)
+        sizes = np.array([self.snapshot_bytes(int(s)) for s in seqs], np.int64)
+        offs = np.zeros(n, np.int64)
+        offs[1:] = np.cumsum(sizes)[:-1]
+        total = int(sizes.sum())
+        buf = np.empty(total, np.uint8) if out is None else out
+        if buf.dtype != np.uint8 or buf.ndim != 1 or buf.size < total or not buf.flags.c_contiguous:
+            raise ValueError("save: out must be a contiguous uint8 buffer of at least %d bytes" % total)
+        wrote = np.zeros(n, np.int64)
+        self._chk(self.L.vio_save_seqs(self.h, n, seqs.ctypes.data, buf.ctypes.data, offs.ctypes.data, sizes.ctypes.data, wrote.ctypes.data),
+                  "vio_save_seqs")
+        return [buf[int(o):int(o) + int(w)] for o, w in zip(offs, wrote)]
+
+    def load(self, seqs, blobs):
+        """vio_load_seqs: restores blobs[i] (uint8 array or bytes, from save() of any handle with the same shape key and tracker lag) into
+        slot seqs[i]; slots must be distinct.  Refused with VioError (every slot untouched) when a blob does not fit this handle."""
+        seqs = np.ascontiguousarray(seqs, np.int32).reshape(-1)
+        arrs = [np.ascontiguousarray(np.frombuffer(b, np.uint8) if isinstance(b, (bytes, bytearray, memoryview)) else b, np.uint8).reshape(-1)
+                for b in blobs]
+        if len(arrs) != len(seqs):
+            raise ValueError("load: one blob per slot")
+        sizes = np.array([a.size for a in arrs], np.int64)
+        offs = np.zeros(len(arrs), np.int64)
+        offs[1:] = np.cumsum(sizes)[:-1]
+        # blobs that are consecutive views of one buffer (what save() returns) go as they lie; others are packed back to back first
+        base = arrs[0].ctypes.data if arrs else 0
+        if all(a.ctypes.data == base + int(o) for a, o in zip(arrs, offs)):
+            src_ptr, keep = base, arrs
+        else:
+            keep = np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)
+            src_ptr = keep.ctypes.data
+        self._chk(self.L.vio_load_seqs(self.h, len(seqs), seqs.ctypes.data, src_ptr, offs.ctypes.data, sizes.ctypes.data), "vio_load_seqs")
+        for s in seqs:   # config_of() now describes the restored rig (the calibration in effect: ric is a rotation already)
+            self._cal_in[int(s)] = _copy_fields(Calibration(), self.calibration(int(s)))
+
+    def snapshot_layout(self):
+        """The layout table of the handle: [(name, kind: 1 state / 0 scratch / 2 handle-wide, bytes per sequence, offset
+        inside a blob's device part or -1)]"""
+        out, i = [], 0
+        name, kind, nb, off = C.create_string_buffer(64), C.c_int32(), C.c_int64(), C.c_int64()
+        while i < self.L.vio_debug_snapshot_layout(self.h, i, name, C.byref(kind), C.byref(nb), C.byref(off)):
+            out.append((name.value.decode(), int(kind.value), int(nb.value), int(off.value)))
+            i += 1
+        return out
 
     def config_of(self, seq):
         """The handle's configuration with slot seq's calibration merged in: what a one-sequence handle, the oracle or posegraph needs to

@@ -13,6 +13,7 @@
 #include "kernels.h"
 #include "dyninit_host.h"
 #include "camera_model.h"
+#include "snapshot.h"
 
 thread_local std::string g_err;   // last failure of the calling thread (vio_last_error); also set by pg_kernels.hip / posegraph_host.cpp
 
@@ -168,6 +169,17 @@ struct vio_batch {
     std::vector<hipEvent_t> pev;
     int prof_steps = 0, prof_cur = -1;
     bool prof_fe_only = false;        // the profiled steps were vio_track calls: only the front-end events exist
+    // sequence snapshots (vio_save_seqs / vio_load_seqs): the layout table (built at the first use), its device copy, the sequence list of a call
+    // and the staging buffer the pack / unpack kernels work on.  Nothing of this is allocated until the first save or load.
+    struct SnapRow { const char *name; int kind; unsigned char *base; int64_t bytes, blob_off; };   // kind: 1 state, 0 scratch, 2 handle-wide (not per sequence)
+    std::vector<SnapRow> snap_rows;
+    int64_t snap_dev_bytes = 0, snap_chunks = 0;
+    int snap_entries = 0;
+    SnapEntry *d_snap_tab = nullptr;
+    SnapSeq *d_snap_seqs = nullptr;
+    size_t snap_seqs_cap = 0;
+    unsigned char *d_snap_stage = nullptr;
+    size_t snap_stage_cap = 0;
 };
 #define VIO_NK 10  // kernels per vio_feed: fe_begin pyrdown predict lk select fast add | be_ingest solve marg(+finish)
 #define VIO_NEV 12 // events per step: 0..7 bracket the front-end kernels on fe_stream, 8..11 the back-end kernels on stream
@@ -1262,6 +1274,9 @@ void vio_destroy(vio_batch *h) {
     if (h->d_state) (void)hipFree(h->d_state);
     if (h->d_dyn_samples) (void)hipFree(h->d_dyn_samples);
     if (h->d_dyn_offs) (void)hipFree(h->d_dyn_offs);
+    if (h->d_snap_tab) (void)hipFree(h->d_snap_tab);
+    if (h->d_snap_seqs) (void)hipFree(h->d_snap_seqs);
+    if (h->d_snap_stage) (void)hipFree(h->d_snap_stage);
     for (hipEvent_t e : h->pev) (void)hipEventDestroy(e);
     for (auto &g : h->groups) {
         if (g.stream) (void)hipStreamDestroy(g.stream);
@@ -1522,7 +1537,7 @@ int vio_feed_modes(vio_batch *h, const uint8_t *gray, const uint16_t *depth_mm, 
     return VIO_OK;
 }
 
-int vio_abi_version(void) { return 11; }
+int vio_abi_version(void) { return 12; }
 
 // marg_exact = 2 (the literal marginalisation with a CERTIFIED first inverse): out2 = {marginalisations of sequence seq whose certificate failed
 // since vio_create / vio_reset -- those frames used the block inverse WITHOUT the proof that the reference's 1e-8 cut drops nothing --, 1 if the
@@ -1854,7 +1869,7 @@ int vio_device_download(void *dst, const void *src, size_t bytes) { HIPCHK(hipMe
 
 int vio_abi_sizeof(int what) {
     return what == 0 ? (int)sizeof(vio_config) : what == 1 ? (int)sizeof(vio_status) : what == 2 ? (int)sizeof(vio_calibration)
-         : what == 3 ? (int)sizeof(vio_camera) : -1;
+         : what == 3 ? (int)sizeof(vio_camera) : what == 4 ? (int)sizeof(vio_snapshot_header) : what == 5 ? (int)sizeof(vio_snapshot_shape) : -1;
 }
 
 int vio_get_capacity(vio_batch *h, int32_t *out3) {
@@ -2004,25 +2019,20 @@ void vio_calibration_from_config(const vio_config *cfg, vio_calibration *out) {
     if (cfg && out) cal_from_config(*cfg, *out);
 }
 
-int vio_set_calibration(vio_batch *h, int seq, const vio_calibration *cal) {
-    DevGuard dev_guard(h);
-    if (dev_guard.failed) { g_err = "hipSetDevice failed for the handle's device"; return VIO_EDEVICE; }
-    if (!h || !cal) { g_err = "vio_set_calibration: bad arguments"; return VIO_EINVAL; }
-    if (seq < 0 || seq >= h->S) { g_err = "vio_set_calibration: seq out of range"; return VIO_EINVAL; }
-    const vio_calibration &k = *cal;
-    // validation first: the slot is left untouched by a refusal
+// vio_set_calibration's validation: "" when k is usable, else the message naming the offending field (vio_load_seqs applies it to a blob's calibration)
+static std::string calibration_check(const vio_calibration &k) {
     const struct { const char *name; const double *v; int n; } fin[] = {
         {"fx", &k.fx, 1}, {"fy", &k.fy, 1}, {"cx", &k.cx, 1}, {"cy", &k.cy, 1}, {"k1", &k.k1, 1}, {"k2", &k.k2, 1}, {"p1", &k.p1, 1},
         {"p2", &k.p2, 1}, {"ric", k.ric, 9}, {"tic", k.tic, 3}, {"td", &k.td, 1}, {"tr", &k.tr, 1}, {"acc_n", &k.acc_n, 1},
         {"acc_w", &k.acc_w, 1}, {"gyr_n", &k.gyr_n, 1}, {"gyr_w", &k.gyr_w, 1}, {"g_norm", &k.g_norm, 1}};
     for (const auto &f : fin)
         for (int i = 0; i < f.n; i++)
-            if (!std::isfinite(f.v[i])) { g_err = std::string("vio_set_calibration: ") + f.name + " is not finite"; return VIO_EINVAL; }
+            if (!std::isfinite(f.v[i])) return std::string(f.name) + " is not finite";
     const struct { const char *name; double v; } pos[] = {
         {"fx", k.fx}, {"fy", k.fy}, {"acc_n", k.acc_n}, {"acc_w", k.acc_w}, {"gyr_n", k.gyr_n}, {"gyr_w", k.gyr_w}, {"g_norm", k.g_norm}};
     for (const auto &f : pos)
-        if (!(f.v > 0)) { g_err = std::string("vio_set_calibration: ") + f.name + " must be > 0"; return VIO_EINVAL; }
-    if (!(k.tr >= 0)) { g_err = "vio_set_calibration: tr must be >= 0"; return VIO_EINVAL; }
+        if (!(f.v > 0)) return std::string(f.name) + " must be > 0";
+    if (!(k.tr >= 0)) return "tr must be >= 0";
     {
         double err = 0;
         for (int i = 0; i < 3; i++)
@@ -2033,8 +2043,20 @@ int vio_set_calibration(vio_batch *h, int seq, const vio_calibration *cal) {
             }
         const double *R = k.ric;
         const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
-        if (!(err <= 1e-6) || !(det > 0)) { g_err = "vio_set_calibration: ric is not a rotation (orthonormal within 1e-6, determinant +1)"; return VIO_EINVAL; }
+        if (!(err <= 1e-6) || !(det > 0)) return "ric is not a rotation (orthonormal within 1e-6, determinant +1)";
     }
+    return "";
+}
+
+int vio_set_calibration(vio_batch *h, int seq, const vio_calibration *cal) {
+    DevGuard dev_guard(h);
+    if (dev_guard.failed) { g_err = "hipSetDevice failed for the handle's device"; return VIO_EDEVICE; }
+    if (!h || !cal) { g_err = "vio_set_calibration: bad arguments"; return VIO_EINVAL; }
+    if (seq < 0 || seq >= h->S) { g_err = "vio_set_calibration: seq out of range"; return VIO_EINVAL; }
+    const vio_calibration &k = *cal;
+    // validation first: the slot is left untouched by a refusal
+    const std::string why = calibration_check(k);
+    if (!why.empty()) { g_err = "vio_set_calibration: " + why; return VIO_EINVAL; }
     vio_calibration e = k;
     if (h->hc.c.estimate_extrinsic == 2) {   // as build_devcfg: the extrinsic is calibrated online from RIC = I, TIC = 0
         dm::stm(e.ric, dm::eye());
@@ -2113,6 +2135,385 @@ int vio_set_camera(vio_batch *h, int seq, const vio_camera *cam) {
 int vio_get_camera(vio_batch *h, int seq, vio_camera *out) {
     if (!h || !out || seq < 0 || seq >= h->S) { g_err = "vio_get_camera: bad arguments"; return VIO_EINVAL; }
     *out = h->cam[seq].model == VIO_CAMERA_PINHOLE ? pinhole_camera(h->cal[seq]) : h->cam[seq];
+    return VIO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- sequence snapshots
+// THE LAYOUT TABLE (DESIGN.md 6d repeats it): every member of Batch, DevCfg::exc / exh and every per-sequence host vector of vio_batch,
+// classified once.  STATE rows are what a snapshot carries, in this order, each at the next multiple of 16 bytes of the blob's device part;
+// the pack / unpack kernels, the naive reference loop and vio_debug_snapshot_layout all walk this one table.  SCRATCH rows are rewritten by
+// every frame before they are read; HANDLE rows are not per sequence.  When in doubt an array is state.
+static void snapshot_build_layout(vio_batch *h) {
+    if (!h->snap_rows.empty()) return;
+    const DevCfg &C = h->hc;
+    const Batch &B = h->B;
+    const int64_t NP = C.NP, NL = C.NL, W1 = C.W + 1, HW = (int64_t)C.c.width * C.c.height, n = C.NPRIOR, LW = C.LW, nres = C.NRES, npair = W1 * W1, mq = 15 + n;
+    std::vector<vio_batch::SnapRow> &R = h->snap_rows;
+#define ROW(kind, name, ptr, count) R.push_back({name, kind, (unsigned char *)(ptr), (ptr) ? (int64_t)(count) * (int64_t)sizeof(*(ptr)) : 0, -1})
+#define STATE(member, count) ROW(1, #member, B.member, count)
+#define SCRATCH(member, count) ROW(0, #member, B.member, count)
+#define HANDLE(name) R.push_back({name, 2, nullptr, 0, -1})
+    HANDLE("cfg"); HANDLE("S"); HANDLE("s0 ns xcd_nb xcd_n"); HANDLE("tracker_lag (header)"); HANDLE("eval_rpt");
+    STATE(fe, 1); STATE(be, 1);
+    ROW(1, "cal", h->d_cal, 1); ROW(1, "cam (cam_of)", h->d_cam, 1);        // the slot's vio_calibration and vio_camera: host mirrors vio_batch::cal / cam
+    STATE(pre, C.W + 2);
+    STATE(img, 2 * HW); STATE(pyr, 2 * (int64_t)C.pyr_bytes);
+    SCRATCH(clahe_lut, 64 * 256); SCRATCH(clahe_img, HW);
+    HANDLE("fisheye");
+    STATE(cur_pts, NP); STATE(forw_pts, NP); STATE(cur_un_pts, NP); STATE(pts_velocity, NP); STATE(prev_un_pt, NP); STATE(unstable_pts, NP);
+    SCRATCH(tmp_pts, NP);
+    STATE(ids, NP); STATE(track_cnt, NP); STATE(prev_un_id, NP);
+    SCRATCH(tmp_i0, NP); SCRATCH(tmp_i1, NP);
+    STATE(lk_status, NP); STATE(accept_xy, 2 * NP);
+    SCRATCH(cand, (int64_t)C.ncells * VIO_FAST_CAP);
+    STATE(obs_id, NP); STATE(obs, NP * 7);
+    STATE(imu_t, C.NIMU); STATE(imu_acc, (int64_t)C.NIMU * 3); STATE(imu_gyr, (int64_t)C.NIMU * 3);
+    STATE(lm_id, NL); STATE(lm_start, NL); STATE(lm_nobs, NL); STATE(lm_est_flag, NL); STATE(lm_solve_flag, NL); STATE(lm_dyn, NL);
+    STATE(lm_order, NL); STATE(lm_free, NL);
+    SCRATCH(lm_tmp, NL);
+    STATE(lm_pidx, NL); STATE(lm_aidx, NL);
+    STATE(lm_depth, NL); STATE(lm_obs, NL * W1 * VIO_OBS_D);
+    STATE(lm_relo, NL); STATE(relo_xy, NL * 2); STATE(relo_mp, NP * 3);
+    STATE(para_feat, NL);
+    SCRATCH(cand_feat, NL);
+    SCRATCH(prior_J, n * n);                                                  // the factored form, produced on demand by vio_get_prior
+    STATE(prior_r, n); STATE(prior_x0, C.W * 7 + 17); STATE(prior_H, n * n);
+    SCRATCH(prior_rf, n);
+    SCRATCH(H, LW * LW); SCRATCH(Sc, LW * LW); SCRATCH(Hpl, 2 * (NL + 8) * LW); SCRATCH(vec, VEC_SLOTS * LW);
+    SCRATCH(Hll, 2 * (NL + 8)); SCRATCH(gl, 2 * (NL + 8)); SCRATCH(lvec, (NL + 8) * 8);
+    SCRATCH(res, nres * 42); SCRATCH(res_pair, 1); SCRATCH(res_lm, nres); SCRATCH(res_k, nres);
+    SCRATCH(pair_start, npair + 1); SCRATCH(pair_list, nres); SCRATCH(pairblk, npair * 210);
+    SCRATCH(ls_scratch, (int64_t)ps_eval_lds_bytes(C.W)); SCRATCH(pairpart, (int64_t)PS_FUSE_MAXPAIRS * PS_FUSE_MAXBLK * 210);
+    HANDLE("gW gP gLW gNL gNP gNRES gNPRIOR gMX"); HANDLE("gn_ext n_schur form_s fuse fuse_only");
+    SCRATCH(imu_raw, (int64_t)C.W * 15 * 31);
+    SCRATCH(margA, mq * mq); SCRATCH(margB, mq); SCRATCH(margV, n * n); SCRATCH(margW, (n + 16) * (n + 16));
+    SCRATCH(margE, (int64_t)3 * C.MX * C.MX + n * (int64_t)C.MX);
+    STATE(odom, 11); STATE(odom_hist, (int64_t)B.hist_cap * 11); STATE(odom_count, 1);
+    HANDLE("hist_cap (shape key)"); HANDLE("flags");
+    HANDLE("timings");
+    SCRATCH(fe_ticks, 4);
+    STATE(sst, 1);                                                            // idle between frames, but kept: rowbuf and the last solve's diagnostics live here
+    ROW(1, "DevCfg::exc", C.exc, 1); ROW(1, "DevCfg::exh", C.exh, (int64_t)VIO_EXCALIB_CAP * VIO_EXCALIB_PAIR_D);   // estimate_extrinsic = 2 handles only
+    // host vectors of vio_batch: cal / cam mirror the device rows above; the rest travels in the host part of a blob
+    R.push_back({"host: last_imu_t", 1, nullptr, (int64_t)sizeof(double), -1});
+    R.push_back({"host: dyn (DynSeq, variable)", 1, nullptr, 0, -1});
+    R.push_back({"host: p_seq p_t p_acc p_gyr (flushed by save, dropped by load)", 0, nullptr, 0, -1});
+#undef ROW
+#undef STATE
+#undef SCRATCH
+#undef HANDLE
+    int64_t off = 0, chunks = 0;
+    int ne = 0;
+    for (auto &r : R)
+        if (r.kind == 1 && r.base && r.bytes > 0) { r.blob_off = off; off += (r.bytes + 15) & ~(int64_t)15; chunks += (r.bytes + 15) >> 4; ne++; }
+    h->snap_dev_bytes = off; h->snap_chunks = chunks; h->snap_entries = ne;
+}
+static const vio_batch::SnapRow *snapshot_row(const vio_batch *h, const char *name) {
+    for (const auto &r : h->snap_rows) if (!strcmp(r.name, name)) return &r;
+    return nullptr;
+}
+static void snapshot_handle_shape(const vio_batch *h, vio_snapshot_shape *k) {
+    (void)vio_shape_key(&h->hc.c, h->hc.NIMU, k);
+    k->hist_cap = h->B.hist_cap;
+}
+
+// host part of a blob: last_imu_t and, on dynamic_init handles, the image-frame mirror (DynSeq).  Fixed little-endian records, padded with
+// zeros to a multiple of 16.  Of an ImageFrame only what survives between two attempts travels (stamp, ids, points, the linearisation point,
+// the raw samples, bg_lin): everything else is recomputed by vinit::run before it is read.
+struct SnapHostFixed { double last_imu_t; int32_t has_dyn, n_frames; double initial_timestamp; int32_t nonlinear, attempts, failures, last_stage; double pad; };
+struct SnapFrameFixed { double stamp; int32_t n_ids, n_dt; double lin_acc[3], lin_gyr[3], bg_lin[3]; };
+static_assert(sizeof(SnapHostFixed) == 48 && sizeof(SnapFrameFixed) == 88, "snapshot host records");
+static int64_t snapshot_host_bytes(const vio_batch *h, int seq) {
+    int64_t b = sizeof(SnapHostFixed);
+    if (!h->dyn.empty())
+        for (const auto &f : h->dyn[seq].frames)
+            b += (int64_t)sizeof(SnapFrameFixed) + (((int64_t)f.ids.size() + 1) & ~(int64_t)1) * 4 + (int64_t)(f.xy.size() + f.dt.size() + f.acc.size() + f.gyr.size()) * 8;
+    return (b + 15) & ~(int64_t)15;
+}
+static void snapshot_write_host(const vio_batch *h, int seq, unsigned char *p, int64_t bytes) {
+    memset(p, 0, (size_t)bytes);
+    SnapHostFixed hf;
+    memset(&hf, 0, sizeof(hf));
+    hf.last_imu_t = h->last_imu_t[seq];
+    if (!h->dyn.empty()) {
+        const vio_batch::DynSeq &D = h->dyn[seq];
+        hf.has_dyn = 1; hf.n_frames = (int32_t)D.frames.size(); hf.initial_timestamp = D.initial_timestamp;
+        hf.nonlinear = D.nonlinear ? 1 : 0; hf.attempts = D.attempts; hf.failures = D.failures; hf.last_stage = D.last_stage;
+    }
+    memcpy(p, &hf, sizeof(hf)); p += sizeof(hf);
+    if (h->dyn.empty()) return;
+    for (const auto &f : h->dyn[seq].frames) {
+        SnapFrameFixed ff;
+        memset(&ff, 0, sizeof(ff));
+        ff.stamp = f.stamp; ff.n_ids = (int32_t)f.ids.size(); ff.n_dt = (int32_t)f.dt.size();
+        for (int k = 0; k < 3; k++) { ff.lin_acc[k] = f.lin_acc[k]; ff.lin_gyr[k] = f.lin_gyr[k]; ff.bg_lin[k] = f.bg_lin[k]; }
+        memcpy(p, &ff, sizeof(ff)); p += sizeof(ff);
+        if (!f.ids.empty()) memcpy(p, f.ids.data(), f.ids.size() * 4);
+        p += ((f.ids.size() + 1) & ~(size_t)1) * 4;
+        auto put = [&](const std::vector<double> &v) { if (!v.empty()) memcpy(p, v.data(), v.size() * 8); p += v.size() * 8; };
+        put(f.xy); put(f.dt); put(f.acc); put(f.gyr);
+    }
+}
+// parses (and bounds-checks) the host part; D may be NULL (validation only).  "" or the complaint.
+static std::string snapshot_read_host(const unsigned char *p, int64_t bytes, bool want_dyn, int NP, double *last_imu_t, vio_batch::DynSeq *D) {
+    const unsigned char *end = p + bytes;
+    SnapHostFixed hf;
+    if (bytes < (int64_t)sizeof(hf)) return "host_bytes: the host part is shorter than its fixed record";
+    memcpy(&hf, p, sizeof(hf)); p += sizeof(hf);
+    if ((hf.has_dyn != 0) != want_dyn) return "dynamic_init: the host part does not match the handle";
+    if (hf.n_frames < 0 || (!hf.has_dyn && hf.n_frames != 0)) return "host part: bad image-frame count";
+    if (last_imu_t) *last_imu_t = hf.last_imu_t;
+    if (D) { *D = vio_batch::DynSeq(); D->initial_timestamp = hf.initial_timestamp; D->nonlinear = hf.nonlinear != 0; D->attempts = hf.attempts; D->failures = hf.failures; D->last_stage = hf.last_stage; }
+    for (int i = 0; i < hf.n_frames; i++) {
+        SnapFrameFixed ff;
+        if (end - p < (int64_t)sizeof(ff)) return "host_bytes: an image frame runs past the end of the blob";
+        memcpy(&ff, p, sizeof(ff)); p += sizeof(ff);
+        if (ff.n_ids < 0 || ff.n_ids > NP || ff.n_dt < 0 || ff.n_dt > VIO_IMU_SLOT_CAP) return "host part: image frame counts out of range";
+        const int64_t need = (((int64_t)ff.n_ids + 1) & ~(int64_t)1) * 4 + ((int64_t)2 * ff.n_ids + (int64_t)7 * ff.n_dt) * 8;
+        if (end - p < need) return "host_bytes: an image frame runs past the end of the blob";
+        if (D) {
+            vinit::ImageFrame f;
+            f.stamp = ff.stamp;
+            for (int k = 0; k < 3; k++) { f.lin_acc[k] = ff.lin_acc[k]; f.lin_gyr[k] = ff.lin_gyr[k]; f.bg_lin[k] = ff.bg_lin[k]; }
+            const unsigned char *q = p;
+            f.ids.resize(ff.n_ids);
+            if (ff.n_ids) memcpy(f.ids.data(), q, (size_t)ff.n_ids * 4);
+            q += (((size_t)ff.n_ids + 1) & ~(size_t)1) * 4;
+            auto get = [&](std::vector<double> &v, size_t cnt) { v.resize(cnt); if (cnt) memcpy(v.data(), q, cnt * 8); q += cnt * 8; };
+            get(f.xy, (size_t)2 * ff.n_ids); get(f.dt, (size_t)ff.n_dt); get(f.acc, (size_t)3 * ff.n_dt); get(f.gyr, (size_t)3 * ff.n_dt);
+            D->frames.push_back(std::move(f));
+        }
+        p += need;
+    }
+    return "";
+}
+
+// what vio_reset_seq does before it touches a slot (the staged IMU goes INTO the rings here instead of being dropped)
+static int snapshot_quiesce(vio_batch *h, bool flush) {
+    if (flush) { int rc = flush_imu_backend(h); if (rc != VIO_OK) return rc; }
+    { int rc = sync_all(h); if (rc != VIO_OK) return rc; }
+    return refresh_dynamic_state(h);
+}
+// device side of the first save / load: the table, and room for `count` sequences and `stage_bytes` of staging
+static int snapshot_reserve(vio_batch *h, size_t count, size_t stage_bytes) {
+    snapshot_build_layout(h);
+    if (!h->d_snap_tab) {
+        std::vector<SnapEntry> tab;
+        int64_t c0 = 0;
+        for (const auto &r : h->snap_rows)
+            if (r.blob_off >= 0) { tab.push_back({r.base, r.bytes, r.bytes, r.blob_off, c0}); c0 += (r.bytes + 15) >> 4; }
+        HIPCHK(hipMalloc((void **)&h->d_snap_tab, tab.size() * sizeof(SnapEntry)));
+        HIPCHK(hipMemcpy(h->d_snap_tab, tab.data(), tab.size() * sizeof(SnapEntry), hipMemcpyHostToDevice));
+    }
+    if (count > h->snap_seqs_cap) {
+        if (h->d_snap_seqs) { (void)hipFree(h->d_snap_seqs); h->d_snap_seqs = nullptr; h->snap_seqs_cap = 0; }
+        HIPCHK(hipMalloc((void **)&h->d_snap_seqs, count * sizeof(SnapSeq)));
+        h->snap_seqs_cap = count;
+    }
+    if (stage_bytes > h->snap_stage_cap) {
+        if (h->d_snap_stage) { (void)hipFree(h->d_snap_stage); h->d_snap_stage = nullptr; h->snap_stage_cap = 0; }
+        HIPCHK(hipMalloc((void **)&h->d_snap_stage, stage_bytes));
+        h->snap_stage_cap = stage_bytes;
+    }
+    return VIO_OK;
+}
+// Where blob i sits in the staging buffer.  Blobs packed back to back in the caller's buffer keep that arrangement (one copy moves them all);
+// otherwise they are laid out back to back here and move one by one.
+static bool snapshot_place(int n, const int64_t *offsets, const std::vector<int64_t> &bytes, std::vector<int64_t> &pos, int64_t *span) {
+    bool tight = true;
+    for (int i = 0; i + 1 < n; i++) tight = tight && offsets[i + 1] == offsets[i] + bytes[i];
+    for (int i = 0; i < n; i++) tight = tight && (bytes[i] & 15) == 0;
+    pos.resize(n);
+    int64_t at = 0;
+    for (int i = 0; i < n; i++) { pos[i] = at; at += (bytes[i] + 15) & ~(int64_t)15; }
+    *span = at;
+    return tight;
+}
+// one launch per stream group over the sequences it owns, on that group's back-end stream (behind its last kernel), then wait for them
+static int snapshot_launch(vio_batch *h, int n, const int32_t *seqs, const std::vector<int64_t> &pos, bool pack) {
+    std::vector<SnapSeq> list;
+    std::vector<std::pair<int, int>> runs;   // per group: first entry of its run in `list`, count
+    for (auto &g : h->groups) {
+        const int first = (int)list.size();
+        for (int i = 0; i < n; i++)
+            if (seqs[i] >= g.s0 && seqs[i] < g.s0 + g.n) list.push_back({pos[i] + (int64_t)sizeof(vio_snapshot_header), seqs[i], 0});
+        runs.push_back({first, (int)list.size() - first});
+    }
+    HIPCHK(hipMemcpy(h->d_snap_seqs, list.data(), list.size() * sizeof(SnapSeq), hipMemcpyHostToDevice));
+    const unsigned gx = (unsigned)((h->snap_chunks + SNAP_THREADS - 1) / SNAP_THREADS);
+    for (size_t k = 0; k < h->groups.size(); k++) {
+        if (runs[k].second == 0) continue;
+        const dim3 grid(gx, (unsigned)runs[k].second);
+        if (pack) snap_pack_kernel<<<grid, SNAP_THREADS, 0, h->groups[k].stream>>>(h->d_snap_tab, h->snap_entries, h->snap_chunks, h->d_snap_seqs + runs[k].first, h->d_snap_stage);
+        else snap_unpack_kernel<<<grid, SNAP_THREADS, 0, h->groups[k].stream>>>(h->d_snap_tab, h->snap_entries, h->snap_chunks, h->d_snap_seqs + runs[k].first, h->d_snap_stage);
+    }
+    HIPCHK(hipGetLastError());
+    for (size_t k = 0; k < h->groups.size(); k++) if (runs[k].second) HIPCHK(hipStreamSynchronize(h->groups[k].stream));
+    return VIO_OK;
+}
+static void snapshot_fill_header(const vio_batch *h, unsigned char *blob, int64_t host_bytes) {
+    vio_snapshot_header hd;
+    memset(&hd, 0, sizeof(hd));
+    hd.magic = VIO_SNAPSHOT_MAGIC; hd.format_version = VIO_SNAPSHOT_FORMAT; hd.abi_version = (uint32_t)vio_abi_version();
+    hd.device_bytes = h->snap_dev_bytes; hd.host_bytes = host_bytes; hd.total_bytes = (int64_t)sizeof(hd) + hd.device_bytes + hd.host_bytes;
+    static thread_local BeSeq be;
+    memcpy(&be, blob + sizeof(hd) + snapshot_row(h, "be")->blob_off, sizeof(BeSeq));
+    hd.frames_processed = be.frames_processed; hd.last_stamp = be.cur_stamp; hd.solver_flag = be.solver_flag;
+    hd.tracker_lag = h->tracker_lag;
+    snapshot_handle_shape(h, &hd.shape);
+    memcpy(blob, &hd, sizeof(hd));
+}
+
+int64_t vio_snapshot_bytes(vio_batch *h, int seq) {
+    DevGuard dev_guard(h);
+    if (dev_guard.failed) { g_err = "hipSetDevice failed for the handle's device"; return VIO_EDEVICE; }
+    if (!h || seq < 0 || seq >= h->S) { g_err = "vio_snapshot_bytes: seq out of range"; return VIO_EINVAL; }
+    if (!h->dyn.empty()) { int rc = snapshot_quiesce(h, false); if (rc != VIO_OK) return rc; }
+    snapshot_build_layout(h);
+    return (int64_t)sizeof(vio_snapshot_header) + h->snap_dev_bytes + snapshot_host_bytes(h, seq);
+}
+
+int vio_save_seqs(vio_batch *h, int n, const int32_t *seqs, void *dst, const int64_t *offsets, const int64_t *caps, int64_t *bytes_out) {
+    DevGuard dev_guard(h);
+    if (dev_guard.failed) { g_err = "hipSetDevice failed for the handle's device"; return VIO_EDEVICE; }
+    if (!h || n < 0 || (n > 0 && (!seqs || !dst || !offsets || !caps))) { g_err = "vio_save_seqs: bad arguments"; return VIO_EINVAL; }
+    for (int i = 0; i < n; i++)
+        if (seqs[i] < 0 || seqs[i] >= h->S) { g_err = "vio_save_seqs: seqs[" + std::to_string(i) + "] out of range"; return VIO_EINVAL; }
+    if (n == 0) return VIO_OK;
+    { int rc = snapshot_quiesce(h, true); if (rc != VIO_OK) return rc; }
+    snapshot_build_layout(h);
+    std::vector<int64_t> hostb(n), total(n), pos;
+    for (int i = 0; i < n; i++) {
+        hostb[i] = snapshot_host_bytes(h, seqs[i]);
+        total[i] = (int64_t)sizeof(vio_snapshot_header) + h->snap_dev_bytes + hostb[i];
+        if (offsets[i] < 0 || caps[i] < total[i]) { g_err = "vio_save_seqs: caps[" + std::to_string(i) + "] is smaller than vio_snapshot_bytes"; return VIO_ECAPACITY; }
+    }
+    int64_t span = 0;
+    const bool tight = snapshot_place(n, offsets, total, pos, &span);
+    { int rc = snapshot_reserve(h, (size_t)n, (size_t)span); if (rc != VIO_OK) return rc; }
+    { int rc = snapshot_launch(h, n, seqs, pos, true); if (rc != VIO_OK) return rc; }
+    unsigned char *out = (unsigned char *)dst;
+    if (tight) HIPCHK(hipMemcpy(out + offsets[0], h->d_snap_stage, (size_t)span, hipMemcpyDeviceToHost));
+    else
+        for (int i = 0; i < n; i++)
+            HIPCHK(hipMemcpy(out + offsets[i] + sizeof(vio_snapshot_header), h->d_snap_stage + pos[i] + sizeof(vio_snapshot_header), (size_t)h->snap_dev_bytes, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) {
+        unsigned char *blob = out + offsets[i];
+        snapshot_fill_header(h, blob, hostb[i]);
+        snapshot_write_host(h, seqs[i], blob + sizeof(vio_snapshot_header) + h->snap_dev_bytes, hostb[i]);
+        if (bytes_out) bytes_out[i] = total[i];
+    }
+    return VIO_OK;
+}
+
+int64_t vio_debug_save_seq_naive(vio_batch *h, int seq, void *dst, int64_t cap) {
+    DevGuard dev_guard(h);
+    if (dev_guard.failed) { g_err = "hipSetDevice failed for the handle's device"; return VIO_EDEVICE; }
+    if (!h || !dst || seq < 0 || seq >= h->S) { g_err = "vio_debug_save_seq_naive: bad arguments"; return VIO_EINVAL; }
+    { int rc = snapshot_quiesce(h, true); if (rc != VIO_OK) return rc; }
+    snapshot_build_layout(h);
+    const int64_t hostb = snapshot_host_bytes(h, seq), total = (int64_t)sizeof(vio_snapshot_header) + h->snap_dev_bytes + hostb;
+    if (cap < total) { g_err = "vio_debug_save_seq_naive: cap is smaller than vio_snapshot_bytes"; return VIO_ECAPACITY; }
+    unsigned char *blob = (unsigned char *)dst, *dev = blob + sizeof(vio_snapshot_header);
+    memset(dev, 0, (size_t)h->snap_dev_bytes);
+    for (const auto &r : h->snap_rows)   // one copy per table entry: what the pack kernel replaces
+        if (r.blob_off >= 0) HIPCHK(hipMemcpy(dev + r.blob_off, r.base + (int64_t)seq * r.bytes, (size_t)r.bytes, hipMemcpyDeviceToHost));
+    snapshot_fill_header(h, blob, hostb);
+    snapshot_write_host(h, seq, dev + h->snap_dev_bytes, hostb);
+    return total;
+}
+
+int64_t vio_debug_snapshot_staging_bytes(vio_batch *h) { return h ? (int64_t)h->snap_stage_cap + (h->d_snap_tab ? 1 : 0) + (int64_t)h->snap_seqs_cap : VIO_EINVAL; }
+
+int vio_debug_snapshot_layout(vio_batch *h, int i, char *name64, int32_t *kind, int64_t *bytes_per_seq, int64_t *blob_offset) {
+    if (!h) return VIO_EINVAL;
+    snapshot_build_layout(h);
+    const int cnt = (int)h->snap_rows.size();
+    if (i < 0 || i >= cnt) return cnt;
+    const auto &r = h->snap_rows[i];
+    if (name64) { strncpy(name64, r.name, 63); name64[63] = 0; }
+    if (kind) *kind = r.kind;
+    if (bytes_per_seq) *bytes_per_seq = r.bytes;
+    if (blob_offset) *blob_offset = r.blob_off;
+    return cnt;
+}
+
+int vio_load_seqs(vio_batch *h, int n, const int32_t *seqs, const void *src, const int64_t *offsets, const int64_t *bytes) {
+    DevGuard dev_guard(h);
+    if (dev_guard.failed) { g_err = "hipSetDevice failed for the handle's device"; return VIO_EDEVICE; }
+    if (!h || n < 0 || (n > 0 && (!seqs || !src || !offsets || !bytes))) { g_err = "vio_load_seqs: bad arguments"; return VIO_EINVAL; }
+    if (n == 0) return VIO_OK;
+    // ---- validation first: nothing below this block runs after a refusal, so every slot is left untouched
+    for (int i = 0; i < n; i++) {
+        if (seqs[i] < 0 || seqs[i] >= h->S) { g_err = "vio_load_seqs: seqs[" + std::to_string(i) + "] out of range"; return VIO_EINVAL; }
+        for (int j = 0; j < i; j++)
+            if (seqs[j] == seqs[i]) { g_err = "vio_load_seqs: seqs[" + std::to_string(i) + "] is a duplicate slot"; return VIO_EINVAL; }
+    }
+    snapshot_build_layout(h);
+    vio_snapshot_shape mine;
+    snapshot_handle_shape(h, &mine);
+    const unsigned char *in = (const unsigned char *)src;
+    std::vector<int64_t> total(n), pos;
+    std::vector<double> imu_t(n);
+    std::vector<vio_batch::DynSeq> dyn(h->dyn.empty() ? 0 : n);
+    std::vector<vio_calibration> cals(n);
+    std::vector<vio_camera> cams(n);
+    bool relo_pending = false;
+    for (int i = 0; i < n; i++) {
+        const std::string at = "vio_load_seqs: blob " + std::to_string(i) + ": ";
+        if (offsets[i] < 0) { g_err = at + "negative offset"; return VIO_EINVAL; }
+        const unsigned char *blob = in + offsets[i];
+        vio_snapshot_header hd;
+        if (vio_snapshot_info(blob, bytes[i], &hd) != VIO_OK) { g_err = at + g_err; return VIO_EINVAL; }
+        if ((int)hd.abi_version > vio_abi_version()) { g_err = at + "abi_version " + std::to_string(hd.abi_version) + " is newer than this library"; return VIO_EINVAL; }
+        if (const char *f = snap_shape_diff(hd.shape, mine)) { g_err = at + "shape key differs from the handle's in " + f; return VIO_EINVAL; }
+        if (hd.tracker_lag != h->tracker_lag) { g_err = at + "tracker_lag " + std::to_string(hd.tracker_lag) + " differs from the handle's " + std::to_string(h->tracker_lag); return VIO_EINVAL; }
+        if (hd.device_bytes != h->snap_dev_bytes) { g_err = at + "device_bytes does not match the handle's layout"; return VIO_EINVAL; }
+        const unsigned char *dev = blob + sizeof(hd);
+        memcpy(&cals[i], dev + snapshot_row(h, "cal")->blob_off, sizeof(vio_calibration));
+        memcpy(&cams[i], dev + snapshot_row(h, "cam (cam_of)")->blob_off, sizeof(vio_camera));
+        std::string why = calibration_check(cals[i]);
+        if (!why.empty()) { g_err = at + "calibration: " + why; return VIO_EINVAL; }
+        why = camera_check(cams[i], h->hc.c.width, h->hc.c.height);
+        if (!why.empty()) { g_err = at + "camera: " + why; return VIO_EINVAL; }
+        why = snapshot_read_host(dev + hd.device_bytes, hd.host_bytes, !h->dyn.empty(), h->hc.NP, &imu_t[i], dyn.empty() ? nullptr : &dyn[i]);
+        if (!why.empty()) { g_err = at + why; return VIO_EINVAL; }
+        static thread_local BeSeq be;
+        memcpy(&be, dev + snapshot_row(h, "be")->blob_off, sizeof(BeSeq));
+        relo_pending = relo_pending || be.relo_info != 0;
+        total[i] = hd.total_bytes;
+    }
+    // ---- write: synchronise like vio_reset_seq, drop what is staged on the host for these slots, scatter
+    { int rc = snapshot_quiesce(h, false); if (rc != VIO_OK) return rc; }
+    int64_t span = 0;
+    const bool tight = snapshot_place(n, offsets, total, pos, &span);
+    { int rc = snapshot_reserve(h, (size_t)n, (size_t)span); if (rc != VIO_OK) return rc; }
+    if (tight) HIPCHK(hipMemcpy(h->d_snap_stage, in + offsets[0], (size_t)span, hipMemcpyHostToDevice));
+    else
+        for (int i = 0; i < n; i++)
+            HIPCHK(hipMemcpy(h->d_snap_stage + pos[i] + sizeof(vio_snapshot_header), in + offsets[i] + sizeof(vio_snapshot_header), (size_t)h->snap_dev_bytes, hipMemcpyHostToDevice));
+    { int rc = snapshot_launch(h, n, seqs, pos, false); if (rc != VIO_OK) return rc; }
+    {
+        std::lock_guard<std::mutex> lk(h->imu_mu);
+        auto loaded = [&](int s) { for (int i = 0; i < n; i++) if (seqs[i] == s) return true; return false; };
+        size_t w = 0;
+        for (size_t i = 0; i < h->p_seq.size(); i++) {
+            if (loaded(h->p_seq[i])) continue;
+            h->p_seq[w] = h->p_seq[i]; h->p_t[w] = h->p_t[i];
+            for (int k = 0; k < 3; k++) { h->p_acc[3 * w + k] = h->p_acc[3 * i + k]; h->p_gyr[3 * w + k] = h->p_gyr[3 * i + k]; }
+            w++;
+        }
+        h->p_seq.resize(w); h->p_t.resize(w); h->p_acc.resize(3 * w); h->p_gyr.resize(3 * w);
+        for (int i = 0; i < n; i++) h->last_imu_t[seqs[i]] = imu_t[i];
+    }
+    for (int i = 0; i < n; i++) { h->cal[seqs[i]] = cals[i]; h->cam[seqs[i]] = cams[i]; }
+    if (!h->dyn.empty()) {
+        for (int i = 0; i < n; i++) h->dyn[seqs[i]] = std::move(dyn[i]);
+        bool any = false;
+        for (int s = 0; s < h->S; s++) any = any || !h->dyn[s].nonlinear;
+        h->dyn_active = any;
+    }
+    if (relo_pending) h->relo_frames = 1 << 30;   // as vio_set_relo_frame: the pending request needs the two-kernel solver path launched
     return VIO_OK;
 }
 

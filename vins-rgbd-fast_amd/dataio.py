@@ -12,6 +12,7 @@
   * ``ate_rmse``           absolute trajectory error after yaw + translation alignment (gravity-aligned 4-DoF).
 
 Host-side plumbing only: every frame still ends in ``libvio_hip.so``."""
+import json
 import os
 import re
 
@@ -477,19 +478,53 @@ class FrameGate:
         self.first_image_time = float(t)
         self.pub_count = self.input_count = 0
 
+    STATE = ("first_image_flag", "first_image_time", "last_image_time", "pub_count", "input_count")
 
-def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_freq=0):
+    def state(self):
+        """the gate's state as a plain dict (it lives on the Python side: a snapshot's sidecar carries it, not the blob)"""
+        return {n: getattr(self, n) for n in self.STATE}
+
+    def set_state(self, d):
+        self.first_image_flag = bool(d["first_image_flag"])
+        self.first_image_time, self.last_image_time = float(d["first_image_time"]), float(d["last_image_time"])
+        self.pub_count, self.input_count = int(d["pub_count"]), int(d["input_count"])
+
+
+def snapshot_sidecar(path):
+    """the file beside a snapshot blob that holds the caller-side state of replay(): frame index, IMU position, FrameGate state"""
+    return path + ".json"
+
+
+def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_freq=0, save_at=None, snapshot=None, resume=None):
     """Feed a recording through a single-sequence slot of a VioBatch the way the nodelet does: push IMU through the frame stamp
     (one sample beyond, so that IMUAvailable holds), run the frame gate (``freq`` / ``frontend_freq`` of the configuration file;
     frontend_freq == 0 disables the gate: every frame is published), feed the pair with the gate's mode, append a CSV row whenever
     the estimator is NON_LINEAR.  A stream discontinuity restarts the estimator of the sequence (vio_reset_seq; the tracker keeps its state).  Returns the rows
-    [stamp, P, Q(wxyz), V]."""
-    rows, k = [], 0
+    [stamp, P, Q(wxyz), V].
+    save_at = FRAME with snapshot = FILE: after frame FRAME (index into rec) the slot's snapshot (VioBatch.save) is written to FILE and the
+    caller-side state -- frame index, position in the IMU stream, FrameGate state, the init_pub / init_feature mirror -- to FILE.json.
+    resume = FILE: the slot is restored from FILE (VioBatch.load: the handle must have the shape key of the one that saved) and the replay
+    starts behind the saved frame: IMU from the sample after the last one pushed, images from the next frame; the rows it returns and writes
+    are those of the frames it feeds."""
+    rows, k, f0 = [], 0, 0
     wr = OdometryCsvWriter(csv_path, append=False) if csv_path else None
     S = batch.S
     gate = FrameGate(freq, frontend_freq) if int(frontend_freq) > 0 else None
     init_pub = init_feature = False   # host mirror of estimator_nodelet.cpp:365-377, only to recognise an EMPTY published map
-    for f in range(len(rec)):
+    if (save_at is None) != (snapshot is None):
+        raise ValueError("replay: save_at and snapshot go together")
+    if resume is not None:
+        with open(snapshot_sidecar(resume)) as fd:
+            side = json.load(fd)
+        if (side["gate"] is None) != (gate is None):
+            raise ValueError("replay: the snapshot was taken %s a frame gate, this replay runs %s one" %
+                             (("without", "with") if gate is not None else ("with", "without")))
+        batch.load([seq], [np.fromfile(resume, np.uint8)])
+        f0, k = int(side["frame"]) + 1, int(side["imu_next"])
+        init_pub, init_feature = bool(side["init_pub"]), bool(side["init_feature"])
+        if gate is not None:
+            gate.set_state(side["gate"])
+    for f in range(f0, len(rec)):
         t, gray, depth = rec.frame(f)
         k2 = k
         while k2 < len(rec.imu_t) and rec.imu_t[k2] <= t + 1e-9:
@@ -529,6 +564,11 @@ def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_fre
                 wr.write(row[0], row[1:4], row[4:8], row[8:11])
         if on_frame:
             on_frame(f, st)
+        if save_at is not None and f == int(save_at):
+            batch.save([seq])[0].tofile(snapshot)
+            with open(snapshot_sidecar(snapshot), "w") as fd:
+                json.dump(dict(frame=f, stamp=float(t), imu_next=int(k), init_pub=init_pub, init_feature=init_feature,
+                               gate=None if gate is None else gate.state()), fd)
     if wr:
         wr.close()
     return np.array(rows).reshape(-1, 11)
