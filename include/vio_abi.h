@@ -471,7 +471,12 @@ int vio_stage_pyr_down(const uint8_t *src, int w, int h, uint8_t *dst);
 int vio_stage_clahe(const uint8_t *src, int w, int h, uint8_t *dst);
 /* FastFeatureDetector::detect on a ROI, before the mask filter (feature_tracker.cpp:109-110): returns count, out = x,y,score */
 int vio_stage_fast_roi(const uint8_t *img, int W, int H, int rx, int ry, int rw, int rh, int cap, float *out_xys);
-/* cv::calcOpticalFlowPyrLK(21x21, maxLevel, {COUNT+EPS,30,0.01}, OPTFLOW_USE_INITIAL_FLOW) */
+/* cv::calcOpticalFlowPyrLK(21x21, maxLevel, {COUNT+EPS,30,0.01}, OPTFLOW_USE_INITIAL_FLOW).  As in OpenCV (buildOpticalFlowPyramid),
+   the pyramid stops before the first level that is 21 px or less in width or height: the depth used is
+   vio_lk_effective_level(w, h, max_level) = min(max_level, deepest l such that every level 1..l is at least 22 x 22; a level is
+   (n + 1) / 2 of the one above).  A call with a larger max_level returns exactly what the call with the effective level returns.
+   The batch pipeline applies the same rule to vio_config.lk_max_level (the configuration reads back as it was set). */
+int vio_lk_effective_level(int width, int height, int lk_max_level);
 int vio_stage_lk(const uint8_t *prev, const uint8_t *next, int w, int h, int max_level, int n, const float *prev_pts,
                  float *next_pts_inout, uint8_t *status);
 /* cv::findFundamentalMat(FM_RANSAC, F_THRESHOLD, 0.99) on virtual-pinhole points (feature_tracker.cpp:462) */

@@ -293,6 +293,7 @@ void ovio_circle_hw(int radius, int *hw) {
 }
 void ovio_lk(const uint8_t *prev, const uint8_t *next, int w, int h, int maxLevel, int n, const float *prevPts, float *nextPts,
              uint8_t *status, int useInitial) {
+    maxLevel = lk_effective_level(w, h, maxLevel);
     std::vector<Image> P(maxLevel + 1), N(maxLevel + 1);
     P[0].w = N[0].w = w; P[0].h = N[0].h = h;
     P[0].d.assign(prev, prev + (size_t)w * h);
@@ -304,6 +305,7 @@ void ovio_lk(const uint8_t *prev, const uint8_t *next, int w, int h, int maxLeve
     lk_track(P, N, pp, np, st, maxLevel, useInitial != 0);
     for (int i = 0; i < n; i++) { nextPts[2 * i] = np[i].x; nextPts[2 * i + 1] = np[i].y; status[i] = st[i]; }
 }
+int ovio_lk_effective_level(int w, int h, int maxLevel) { return lk_effective_level(w, h, maxLevel); }
 // 7 correspondences (normalised coordinates) -> up to 3 fundamental matrices (row-major 9 each); returns their number
 int ovio_seven_point(const double *x1, const double *y1, const double *x2, const double *y2, double *F27) {
     double F[3][9];

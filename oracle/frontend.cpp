@@ -208,6 +208,22 @@ static inline void scharr_at(const Image &im, int x, int y, int &ix, int &iy) {
 }
 static inline int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 
+// cv::buildOpticalFlowPyramid, which calcOpticalFlowPyrLK calls for both images (OpenCV modules/video/src/lkpyramid.cpp: the level
+// loop ends with `sz = Size((sz.width + 1) / 2, (sz.height + 1) / 2); if (sz.width <= winSize.width || sz.height <= winSize.height)
+// return level;` and the caller continues with that return value as maxLevel): the pyramid stops before the first level that does not
+// exceed the 21 x 21 window, so every level >= 1 is at least 22 px both ways -- exactly what one BORDER_REFLECT_101 reflection of the
+// window needs (-21 -> 21, w + 20 -> w - 22).
+int lk_effective_level(int w, int h, int maxLevel) {
+    const int WIN = 21;
+    int level = 0;
+    while (level < maxLevel) {
+        w = (w + 1) / 2; h = (h + 1) / 2;
+        if (w <= WIN || h <= WIN) break;
+        level++;
+    }
+    return level;
+}
+
 void lk_track(const std::vector<Image> &prev, const std::vector<Image> &next, const std::vector<P2f> &prevPts,
               std::vector<P2f> &nextPts, std::vector<uint8_t> &status, int maxLevel, bool useInitialFlow) {
     const int WIN = 21;
@@ -215,6 +231,7 @@ void lk_track(const std::vector<Image> &prev, const std::vector<Image> &next, co
     const float FLT_SCALE = 1.f / (1 << 20);
     const float minEigThreshold = 1e-4f;
     size_t n = prevPts.size();
+    maxLevel = lk_effective_level(prev[0].w, prev[0].h, maxLevel);
     status.assign(n, 1);
     if (!useInitialFlow) nextPts = prevPts;
     std::vector<short> Ibuf(WIN * WIN), dIx(WIN * WIN), dIy(WIN * WIN);
@@ -666,7 +683,7 @@ void Tracker::undistortedPoints() {  // :542-593
 
 void Tracker::readImage(const uint8_t *img, double t, const double R[9], bool publish) {  // :263-439
     cur_time = t;
-    int maxLevel = cfg.lk_max_level;
+    int maxLevel = lk_effective_level(cfg.width, cfg.height, cfg.lk_max_level);
     std::vector<Image> pyr(maxLevel + 1);
     pyr[0].w = cfg.width; pyr[0].h = cfg.height;
     if (cfg.equalize) {   // :269-275

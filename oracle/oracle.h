@@ -72,6 +72,8 @@ void clahe_apply(const uint8_t *src, int W, int H, uint8_t *dst, double clip = 3
 void fast_detect_roi(const uint8_t *img, int W, int H, int rx, int ry, int rw, int rh, std::vector<KeyPt> &out, int thr = 10);
 int fast_corner_score(const uint8_t *p, int stride, int thr);  // returns 0 if not a corner
 void circle_halfwidths(int radius, std::vector<int> &hw);      // cv::circle(filled) raster shape
+// pyramid depth calcOpticalFlowPyrLK really uses: min(maxLevel, deepest l with every level 1..l >= 22 px both ways); lk_track applies it
+int lk_effective_level(int w, int h, int maxLevel);
 void lk_track(const std::vector<Image> &prev, const std::vector<Image> &next, const std::vector<P2f> &prevPts,
               std::vector<P2f> &nextPts, std::vector<uint8_t> &status, int maxLevel, bool useInitialFlow);
 int seven_point_models(const double *x1, const double *y1, const double *x2, const double *y2, double F[3][9]);

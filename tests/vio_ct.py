@@ -82,6 +82,7 @@ def oracle(path=None):
             "ovio_fast_roi": [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p],
             "ovio_circle_hw": [C.c_int, C.c_void_p],
             "ovio_lk": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+            "ovio_lk_effective_level": [C.c_int, C.c_int, C.c_int],
             "ovio_ransac": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
             "ovio_eval_projection": [C.c_void_p] * 4 + [C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
             "ovio_preint_create": [C.c_void_p] * 5, "ovio_preint_destroy": [C.c_void_p],

@@ -298,6 +298,7 @@ def lib():
         L.vio_stage_pyr_down.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.vio_stage_clahe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.vio_stage_fast_roi.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
+        L.vio_lk_effective_level.argtypes = [C.c_int, C.c_int, C.c_int]
         L.vio_stage_lk.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vio_stage_ransac.argtypes = [C.POINTER(Config), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vio_stage_relative_r.argtypes = [C.c_int, C.c_void_p, C.c_void_p]

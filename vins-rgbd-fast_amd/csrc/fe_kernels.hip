@@ -833,7 +833,7 @@ __global__ __launch_bounds__(64, LK_WAVES) void fe_lk_kernel(Batch B) {
             im.prev[0] = B.img + ((size_t)s * 2 + cur) * hw;
             im.next[0] = B.img + ((size_t)s * 2 + forw) * hw;
             im.w[0] = C.c.width; im.h[0] = C.c.height;
-        } else if (l <= C.c.lk_max_level) {
+        } else if (l <= C.lk_level) {
             im.prev[l] = B.pyr + ((size_t)s * 2 + cur) * C.pyr_bytes + C.lvl_off[l];
             im.next[l] = B.pyr + ((size_t)s * 2 + forw) * C.pyr_bytes + C.lvl_off[l];
             im.w[l] = C.lvl_w[l]; im.h[l] = C.lvl_h[l];
@@ -845,7 +845,7 @@ __global__ __launch_bounds__(64, LK_WAVES) void fe_lk_kernel(Batch B) {
     for (int i = blk0; i < fe.n_pts; i += nblk) {
         float2 np = B.forw_pts[(size_t)s * C.NP + i];
         uint8_t st;
-        lk_one_point(im, C.c.lk_max_level, B.cur_pts[(size_t)s * C.NP + i], np, st, win, der, jw, (s == 0 && blk0 == 0) ? B.timings + 92 : nullptr);
+        lk_one_point(im, C.lk_level, B.cur_pts[(size_t)s * C.NP + i], np, st, win, der, jw, (s == 0 && blk0 == 0) ? B.timings + 92 : nullptr);
         if (threadIdx.x == 0) {
             B.forw_pts[(size_t)s * C.NP + i] = np;
             B.lk_status[(size_t)s * C.NP + i] = st;

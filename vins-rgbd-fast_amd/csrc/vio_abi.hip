@@ -520,7 +520,7 @@ int launch_frontend(vio_batch *h, vio_batch::Group &g, const uint8_t *d_gray, in
     // pyramid: level 1 from the new frame (+ level-0 copy), further levels from the previous one
     {
         int sw = Wd, sh = Ht;
-        for (int l = 1; l <= C.c.lk_max_level; l++) {
+        for (int l = 1; l <= C.lk_level; l++) {
             int dw = (sw + 1) / 2, dh = (sh + 1) / 2;
             dim3 grid((dw + 63) / 64, (dh + 15) / 16, S);
             fe_pyrdown_kernel<<<grid, 256, 0, st>>>(Bg, l == 1 ? d_gray : nullptr, (size_t)Wd * Ht, sw, sh, l, l == 1 ? 1 : 0);
@@ -879,6 +879,19 @@ static void ortho_ric(const double *in, double *out) {
     dm::stm(out, Rc);
 }
 
+// cv::buildOpticalFlowPyramid (called by calcOpticalFlowPyrLK) stops before the first level that does not exceed the 21 x 21 window
+// and LK continues with the depth reached: every level >= 1 in use is at least 22 px both ways, which is also the smallest size at
+// which the single BORDER_REFLECT_101 reflection of the staging code covers the window (-21 -> 21, w + 20 -> w - 22)
+int vio_lk_effective_level(int width, int height, int lk_max_level) {
+    int level = 0;
+    while (level < lk_max_level) {
+        width = (width + 1) / 2; height = (height + 1) / 2;
+        if (width <= VIO_WIN || height <= VIO_WIN) break;
+        level++;
+    }
+    return level;
+}
+
 static int build_devcfg(const vio_config *cfg, int imu_capacity, DevCfg &C) {
     memset(&C, 0, sizeof(C));
     C.c = *cfg;
@@ -943,6 +956,7 @@ static int build_devcfg(const vio_config *cfg, int imu_capacity, DevCfg &C) {
         off += (sw * sh + 63) & ~63;
     }
     C.pyr_bytes = off;
+    C.lk_level = vio_lk_effective_level(c.width, c.height, c.lk_max_level);
     if (c.marg_exact < 0 || c.marg_exact > 2) { g_err = "marg_exact must be 0, 1 or 2"; return VIO_EINVAL; }
     if (c.equalize < 0 || c.equalize > 1) { g_err = "equalize must be 0 or 1"; return VIO_EINVAL; }
     // marg_exact 1: scratch for the full marginalised block (a landmark that starts in frame 0 was packaged by the tracker in that frame: at most NP
@@ -2777,6 +2791,7 @@ int vio_stage_lk(const uint8_t *prev, const uint8_t *next, int w, int h, int max
                  uint8_t *status) {
     int rc = VIO_OK;
     if (max_level < 0 || max_level > 3 || n < 0) return VIO_EINVAL;
+    max_level = vio_lk_effective_level(w, h, max_level);
     uint8_t *dp[4] = {0, 0, 0, 0}, *dn[4] = {0, 0, 0, 0}, *dst = nullptr;
     float2 *dpp = nullptr, *dnp = nullptr;
     LkImages im;

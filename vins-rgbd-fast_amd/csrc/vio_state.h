@@ -60,6 +60,7 @@ struct DevCfg {
     int LW;             // dense row stride of the landmark coupling matrix (= P rounded up to 16)
     int lvl_w[4], lvl_h[4], lvl_off[4];  // pyramid levels >= 1 packed in one buffer
     int pyr_bytes;
+    int lk_level;       // pyramid depth LK really uses (vio_lk_effective_level of c.lk_max_level): the levels built and tracked
     int MX;             // marg_exact: largest marginalised block (15 + landmarks starting in frame 0) the scratch margE is sized for (0 = off)
     int MXL;            // marg_exact: largest block whose eigen-decomposition runs LDS-resident (Householder + implicit QL); larger ones use the HBM Jacobi
     int eig_jacobi;     // VIO_MARG_EIG_JACOBI: the eigen-decompositions of the literal marginalisation that do not fit LDS by cyclic Jacobi sweeps over HBM (rounds 3 - 5) instead of sym_eig_hbm
