@@ -4,7 +4,9 @@ original.  Every comparison is bitwise and is made after EVERY frame: window, tr
 latest odometry (the dictionary of tests/test_gpu_seq_calibration.py, re-stated here) plus the packaged feature map, the relocalisation
 outputs, the mode-2 extrinsic calibration with its pair history, the bound statistics and the slot's calibration and camera."""
 import ctypes as C
+import hashlib
 import importlib
+import json
 import os
 import sys
 
@@ -500,3 +502,47 @@ def test_nothing_is_allocated_until_the_first_save(P):
     assert b.snapshot_bytes(0) > 0 and b.snapshot_layout() and stage() == 0     # sizes and the table cost no device memory
     blob = b.save([0])[0]
     assert stage() >= blob.size
+
+
+# ------------------------------------------------------------------------------------------------ 9. the layout table is pinned
+GOLDEN_LAYOUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "snapshot_layout_abi12.json")
+# every conditional array (clahe_*, margE, exc / exh, pairpart present and absent at W = 20) and both ps_serial variants
+LAYOUT_CONFIGS = [dict(), dict(dynamic_init=1), dict(estimate_extrinsic=2), dict(equalize=1), dict(marg_exact=1), dict(window_size=20),
+                  dict(use_imu=0)]
+
+
+def _layout_key(kw):
+    return ",".join("%s=%d" % kv for kv in sorted(kw.items())) or "default"
+
+
+def _layout_rows(P, kw):
+    return [list(row) for row in P.VioBatch(P.canonical_config(**kw), 2).snapshot_layout()]
+
+
+def _blob_sha256(P, flavour):
+    """slot 1 of a two-sequence handle, driven as test_canonical_bytes drives its handle"""
+    kw, n = (dict(), 26) if flavour == "default" else (dict(dynamic_init=1), 13)
+    cfg = P.canonical_config(**kw)
+    A = P.VioBatch(cfg, 2)
+    sd = Side(A, [_scene(P, cfg, SEQ_OTHER, N), _scene(P, cfg, SEQ_MOVED, N)])
+    for f in range(n):
+        sd.push_imu(f, False)
+        A.feed(sd.gray(f), sd.depth(f), sd.stamps(f))
+    sd.push_imu(n, False)
+    return hashlib.sha256(A.save([1])[0].tobytes()).hexdigest()
+
+
+def test_layout_matches_the_recorded_table(P):
+    """The handle's array table (csrc/vio_handle.h) gives, row for row, the names, kinds, sizes and blob offsets that the library had
+    before the table existed, and a blob has the bytes it had.  tests/golden/snapshot_layout_abi12.json was written by
+    tools/record_snapshot_layout.py (which calls _layout_rows and _blob_sha256 above) with the library of the commit its header names."""
+    gold = json.load(open(GOLDEN_LAYOUT))
+    assert gold["abi_version"] == P.lib().vio_abi_version() == 12 and gold["format_version"] == P.SNAPSHOT_FORMAT == 1
+    assert sorted(gold["layouts"]) == sorted(_layout_key(kw) for kw in LAYOUT_CONFIGS)
+    for kw in LAYOUT_CONFIGS:
+        want, got = gold["layouts"][_layout_key(kw)], _layout_rows(P, kw)
+        assert len(got) == len(want), (kw, len(got), len(want))
+        for i, (w, g) in enumerate(zip(want, got)):
+            assert g == w, (kw, i, g, w)
+    for flavour, sha in gold["blob_sha256"].items():
+        assert _blob_sha256(P, flavour) == sha, flavour

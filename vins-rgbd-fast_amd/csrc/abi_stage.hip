@@ -1,0 +1,254 @@
+// Stage entry points of the C ABI (include/vio_abi.h vio_stage_*): one front-end or back-end building block on caller-supplied data, for the
+// parity tests.  No handle: every call allocates what it needs for its own duration (DevBuf, stage_util.h).
+#include "vio_handle.h"
+
+extern "C" {
+
+int vio_stage_host_camera(const vio_camera *cam, int n, const double *uv, const double *R9, double *ray_out, double *un_out, double *uv_out) {
+    if (!cam || n < 0 || (n > 0 && !uv)) return VIO_EINVAL;
+    const double I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    const double *R = R9 ? R9 : I9;
+    for (int i = 0; i < n; i++) {
+        double x, y, z, X, Y, Z;
+        vcam::lift(*cam, uv[2 * i], uv[2 * i + 1], x, y, z);
+        if (ray_out) { ray_out[3 * i] = x; ray_out[3 * i + 1] = y; ray_out[3 * i + 2] = z; }
+        if (un_out) vcam::lift_plane(*cam, uv[2 * i], uv[2 * i + 1], un_out[2 * i], un_out[2 * i + 1]);
+        X = R[0] * x + R[1] * y + R[2] * z; Y = R[3] * x + R[4] * y + R[5] * z; Z = R[6] * x + R[7] * y + R[8] * z;
+        if (uv_out) vcam::project(*cam, X, Y, Z, uv_out[2 * i], uv_out[2 * i + 1]);
+    }
+    return VIO_OK;
+}
+
+int vio_stage_pyr_down(const uint8_t *src, int w, int h, uint8_t *dst) {
+    const int dw = (w + 1) / 2, dh = (h + 1) / 2;
+    DevBuf<uint8_t> ds, dd;
+    HIPCHK(ds.alloc((size_t)w * h));
+    HIPCHK(dd.alloc((size_t)dw * dh));
+    HIPCHK(ds.upload(src, (size_t)w * h));
+    fe_pyrdown_stage_kernel<<<dim3((dw + 63) / 64, (dh + 15) / 16), 256>>>(ds, w, h, dd);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dd.download(dst, (size_t)dw * dh));
+    return VIO_OK;
+}
+
+int vio_stage_clahe(const uint8_t *src, int w, int h, uint8_t *dst) {
+    DevBuf<uint8_t> ds, dd, dl;
+    if (!src || !dst || w < 8 || h < 8) return VIO_EINVAL;
+    HIPCHK(ds.alloc((size_t)w * h));
+    HIPCHK(dd.alloc((size_t)w * h));
+    HIPCHK(dl.alloc(64 * 256));
+    HIPCHK(ds.upload(src, (size_t)w * h));
+    fe_clahe_lut_stage_kernel<<<64, 256>>>(ds, w, h, dl);
+    fe_clahe_apply_stage_kernel<<<dim3((w + 1023) / 1024, h), 256>>>(ds, w, h, dl, dd);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dd.download(dst, (size_t)w * h));
+    return VIO_OK;
+}
+
+int vio_stage_fast_roi(const uint8_t *img, int W, int H, int rx, int ry, int rw, int rh, int cap, float *out) {
+    int count = 0;
+    DevBuf<uint8_t> di;
+    DevBuf<uint32_t> dout;
+    DevBuf<int> dcnt;
+    std::vector<uint32_t> hv;
+    GridRect r{rx, ry, rw, rh};
+    if (rw < 7 || rh < 7) return 0;
+    size_t lds = fast_lds_bytes(rw, rh);
+    HIPCHK(di.alloc((size_t)W * H));
+    HIPCHK(dout.alloc((size_t)cap));
+    HIPCHK(dcnt.alloc(1));
+    HIPCHK(di.upload(img, (size_t)W * H));
+    (void)raise_lds_limit((const void *)fe_fast_stage_kernel, (size_t)(lds));
+    fe_fast_stage_kernel<<<1, 256, lds>>>(di, W, r, dout, cap, dcnt);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dcnt.download(&count, 1));
+    hv.resize(cap);
+    HIPCHK(dout.download(hv.data(), (size_t)cap));
+    for (int i = 0; i < count && i < cap; i++) { out[3 * i] = (float)(hv[i] & 0xFFF); out[3 * i + 1] = (float)((hv[i] >> 12) & 0xFFF); out[3 * i + 2] = (float)(hv[i] >> 24); }
+    return count;
+}
+
+int vio_stage_lk(const uint8_t *prev, const uint8_t *next, int w, int h, int max_level, int n, const float *prev_pts, float *next_pts,
+                 uint8_t *status) {
+    if (max_level < 0 || max_level > 3 || n < 0) return VIO_EINVAL;
+    max_level = vio_lk_effective_level(w, h, max_level);
+    DevBuf<uint8_t> dp[4], dn[4], dst;
+    DevBuf<float2> dpp, dnp;
+    LkImages im;
+    memset(&im, 0, sizeof(im));
+    int lw = w, lh = h;
+    for (int l = 0; l <= max_level; l++) {
+        HIPCHK(dp[l].alloc((size_t)lw * lh));
+        HIPCHK(dn[l].alloc((size_t)lw * lh));
+        im.prev[l] = dp[l]; im.next[l] = dn[l]; im.w[l] = lw; im.h[l] = lh;
+        if (l == 0) {
+            HIPCHK(dp[0].upload(prev, (size_t)w * h));
+            HIPCHK(dn[0].upload(next, (size_t)w * h));
+        } else {
+            int pw = im.w[l - 1], ph = im.h[l - 1];
+            fe_pyrdown_stage_kernel<<<dim3((lw + 63) / 64, (lh + 15) / 16), 256>>>(dp[l - 1], pw, ph, dp[l]);
+            fe_pyrdown_stage_kernel<<<dim3((lw + 63) / 64, (lh + 15) / 16), 256>>>(dn[l - 1], pw, ph, dn[l]);
+        }
+        lw = (lw + 1) / 2; lh = (lh + 1) / 2;
+    }
+    HIPCHK(dpp.alloc((size_t)n + 1));
+    HIPCHK(dnp.alloc((size_t)n + 1));
+    HIPCHK(dst.alloc((size_t)n + 1));
+    HIPCHK(dpp.upload((const float2 *)prev_pts, n));
+    HIPCHK(dnp.upload((const float2 *)next_pts, n));
+    if (n > 0) fe_lk_stage_kernel<<<n, 64>>>(im, max_level, n, dpp, dnp, dst);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dnp.download((float2 *)next_pts, n));
+    HIPCHK(dst.download(status, n));
+    return VIO_OK;
+}
+
+int vio_stage_ransac(const vio_config *cfg, int n, const float *p1, const float *p2, uint8_t *status) {
+    DevBuf<float2> d1, d2;
+    DevBuf<uint8_t> ds;
+    size_t lds = (size_t)n * 36 + 64;
+    HIPCHK(d1.alloc((size_t)n + 1));
+    HIPCHK(d2.alloc((size_t)n + 1));
+    HIPCHK(ds.alloc((size_t)n + 1));
+    HIPCHK(d1.upload((const float2 *)p1, n));
+    HIPCHK(d2.upload((const float2 *)p2, n));
+    (void)raise_lds_limit((const void *)fe_ransac_stage_kernel, (size_t)(lds));
+    fe_ransac_stage_kernel<<<1, 256, lds>>>(*cfg, n, d1, d2, ds);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(ds.download(status, n));
+    return VIO_OK;
+}
+
+int vio_stage_camera(const vio_camera *cam, int n, const double *uv, const double *R9, double *ray_out, double *un_out, double *uv_out) {
+    if (!cam || n < 0 || (n > 0 && !uv)) return VIO_EINVAL;
+    DevBuf<double> d;
+    const double I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    const size_t m = (size_t)n + 1;   // uv(2) ray(3) un(2) uv_out(2) per point, R9
+    HIPCHK(d.alloc(9 * m + 9));
+    HIPCHK(d.upload(uv, (size_t)2 * n));
+    HIPCHK(d.upload(R9 ? R9 : I9, 9, 9 * m));
+    if (n > 0) fe_camera_stage_kernel<<<(n + 255) / 256, 256>>>(*cam, n, d, d + 9 * m, d + 2 * m, d + 5 * m, d + 7 * m);
+    HIPCHK(hipDeviceSynchronize());
+    if (ray_out) HIPCHK(d.download(ray_out, (size_t)3 * n, 2 * m));
+    if (un_out) HIPCHK(d.download(un_out, (size_t)2 * n, 5 * m));
+    if (uv_out) HIPCHK(d.download(uv_out, (size_t)2 * n, 7 * m));
+    return VIO_OK;
+}
+
+int vio_stage_relative_r(int n, const double *corres6, double *R9) {
+    if (n < 0 || (n > 0 && !corres6) || !R9) return VIO_EINVAL;
+    DevBuf<double> dc, dR;
+    const size_t lds = (size_t)n * 40 + 64;   // four coordinate arrays + the RANSAC status flags
+    HIPCHK(dc.alloc((size_t)6 * (n + 1)));
+    HIPCHK(dR.alloc(9));
+    if (n > 0) HIPCHK(dc.upload(corres6, (size_t)6 * n));
+    (void)raise_lds_limit((const void *)be_stage_relative_r_kernel, lds);
+    if (!lds_fits((const void *)be_stage_relative_r_kernel, lds, "be_stage_relative_r")) return VIO_ECAPACITY;
+    be_stage_relative_r_kernel<<<1, 256, lds>>>(n, dc, dR);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dR.download(R9, 9));
+    return VIO_OK;
+}
+
+static int stage_imu_impl(const vio_config *cfg, int n, const double *dt, const double *acc, const double *gyr, const double *acc0,
+                          const double *gyr0, const double *ba, const double *bg, const double *pose_i, const double *sb_i,
+                          const double *pose_j, const double *sb_j, double *preint_out, double *r15, double *J480, double *G961) {
+    DevBuf<double> dG, dbuf;
+    DevBuf<PreInt> dp;
+    std::vector<PreInt> hpv(1);
+    PreInt *hp = hpv.data();
+    std::vector<double> hb;
+    memset(hp, 0, sizeof(PreInt));
+    {
+        using namespace dm;
+        // IntegrationBase constructor on the host side of the test harness (plain state initialisation)
+        for (int k = 0; k < 3; k++) { hp->lin_acc[k] = acc0[k]; hp->lin_gyr[k] = gyr0[k]; hp->lin_ba[k] = ba[k]; hp->lin_bg[k] = bg[k]; hp->acc0[k] = acc0[k]; hp->gyr0[k] = gyr0[k]; }
+        hp->dq[0] = 1;
+        for (int i = 0; i < 15; i++) hp->jac[i * 16] = 1;
+        hp->valid = 1;
+    }
+    size_t nd = (size_t)n * 7 + 32 + 461 + 15 + 480;
+    hb.assign(nd, 0.0);
+    for (int i = 0; i < n; i++) { hb[i] = dt[i]; for (int k = 0; k < 3; k++) { hb[n + 3 * i + k] = acc[3 * i + k]; hb[4 * n + 3 * i + k] = gyr[3 * i + k]; } }
+    for (int k = 0; k < 7; k++) { hb[7 * n + k] = pose_i[k]; hb[7 * n + 16 + k] = pose_j[k]; }
+    for (int k = 0; k < 9; k++) { hb[7 * n + 7 + k] = sb_i[k]; hb[7 * n + 23 + k] = sb_j[k]; }
+    HIPCHK(dp.alloc(1));
+    HIPCHK(dbuf.alloc(nd));
+    HIPCHK(dp.upload(hp, 1));
+    HIPCHK(dbuf.upload(hb.data(), nd));
+    be_stage_imu_kernel<<<1, 256>>>(*cfg, dp, n, dbuf, dbuf + n, dbuf + 4 * n, dbuf + 7 * n, cfg->g_norm, dbuf + 7 * n + 32, dbuf + 7 * n + 32 + 461,
+                                    dbuf + 7 * n + 32 + 461 + 15);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dbuf.download(hb.data(), nd));
+    if (preint_out) memcpy(preint_out, &hb[7 * n + 32], 461 * sizeof(double));
+    if (r15) memcpy(r15, &hb[7 * n + 32 + 461], 15 * sizeof(double));
+    if (J480) memcpy(J480, &hb[7 * n + 32 + 461 + 15], 480 * sizeof(double));
+    if (G961) {
+        HIPCHK(dG.alloc(961));
+        HIPCHK(hipMemset(dG, 0, 961 * sizeof(double)));
+        be_stage_imu_block_kernel<<<1, 64>>>(dp, dbuf + 7 * n, cfg->g_norm, dG);
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(dG.download(G961, 961));
+    }
+    return VIO_OK;
+}
+
+int vio_stage_imu_factor(const vio_config *cfg, int n, const double *dt, const double *acc, const double *gyr, const double *acc0,
+                         const double *gyr0, const double *ba, const double *bg, const double *pose_i, const double *sb_i,
+                         const double *pose_j, const double *sb_j, double *preint_out, double *r15, double *J480) {
+    return stage_imu_impl(cfg, n, dt, acc, gyr, acc0, gyr0, ba, bg, pose_i, sb_i, pose_j, sb_j, preint_out, r15, J480, nullptr);
+}
+int vio_stage_imu_block(const vio_config *cfg, int n, const double *dt, const double *acc, const double *gyr, const double *acc0,
+                        const double *gyr0, const double *ba, const double *bg, const double *pose_i, const double *sb_i,
+                        const double *pose_j, const double *sb_j, double *G961) {
+    return stage_imu_impl(cfg, n, dt, acc, gyr, acc0, gyr0, ba, bg, pose_i, sb_i, pose_j, sb_j, nullptr, nullptr, nullptr, G961);
+}
+
+static int stage_projection_impl(const vio_config *cfg, const double *pose_i, const double *pose_j, const double *ex, double inv_dep, double td,
+                                 const double *obs_i, const double *obs_j, int use_td, int form, double *r2, double *J46) {
+    double hb[41 + 2 + 46];
+    DevBuf<double> db;
+    memcpy(hb, pose_i, 56); memcpy(hb + 7, pose_j, 56); memcpy(hb + 14, ex, 56);
+    hb[21] = inv_dep; hb[22] = td;
+    memcpy(hb + 23, obs_i, 72); memcpy(hb + 32, obs_j, 72);
+    HIPCHK(db.alloc(41 + 2 + 46));
+    HIPCHK(db.upload(hb, 41 + 2 + 46));
+    be_stage_projection_kernel<<<1, 64>>>(*cfg, db, use_td, form, db + 41, db + 43);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(db.download(hb, 41 + 2 + 46));
+    memcpy(r2, hb + 41, 16);
+    memcpy(J46, hb + 43, 46 * 8);
+    return VIO_OK;
+}
+// cv::solvePnP(SOLVEPNP_ITERATIVE, useExtrinsicGuess = 1) with K = I as FeatureManager::solvePoseByPnP calls it (feature_manager.cpp:571):
+// obj[n][3], img[n][2] (both rounded to float like cv::Point3f / Point2f), rvec / tvec in and out
+int vio_stage_pnp(int n, const double *obj, const double *img, double *rvec3, double *tvec3) {
+    if (n < 4) return VIO_EINVAL;
+    std::vector<double> pts((size_t)n * 5), par(6);
+    for (int i = 0; i < n; i++) {
+        for (int k = 0; k < 3; k++) pts[5 * i + k] = (double)(float)obj[3 * i + k];
+        for (int k = 0; k < 2; k++) pts[5 * i + 3 + k] = (double)(float)img[2 * i + k];
+    }
+    for (int k = 0; k < 3; k++) { par[k] = rvec3[k]; par[3 + k] = tvec3[k]; }
+    DevBuf<double> dp, dq;
+    HIPCHK(dp.alloc(pts.size()));
+    HIPCHK(dq.alloc(6));
+    HIPCHK(dp.upload(pts.data(), pts.size()));
+    HIPCHK(dq.upload(par.data(), 6));
+    be_stage_pnp_kernel<<<1, 256>>>(dp, n, dq);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dq.download(par.data(), 6));
+    for (int k = 0; k < 3; k++) { rvec3[k] = par[k]; tvec3[k] = par[3 + k]; }
+    return VIO_OK;
+}
+
+int vio_stage_projection(const vio_config *cfg, const double *pose_i, const double *pose_j, const double *ex, double inv_dep, double td,
+                         const double *obs_i, const double *obs_j, int use_td, double *r2, double *J46) {
+    return stage_projection_impl(cfg, pose_i, pose_j, ex, inv_dep, td, obs_i, obs_j, use_td, 0, r2, J46);
+}
+int vio_stage_projection_residual(const vio_config *cfg, const double *pose_i, const double *pose_j, const double *ex, double inv_dep, double td,
+                                  const double *obs_i, const double *obs_j, int use_td, double *r2, double *J46) {
+    return stage_projection_impl(cfg, pose_i, pose_j, ex, inv_dep, td, obs_i, obs_j, use_td, 1, r2, J46);
+}
+
+}  // extern "C"

@@ -27,7 +27,7 @@ __device__ __forceinline__ unsigned ps_colmask(int W1, int LW, bool vext) {
 
 // The landmark rows (Hpl, Hll, gl) are double-buffered: the fused evaluate + assemble kernel builds the rows of the point it evaluates -- a
 // candidate that may still be rejected -- into the half that is NOT current (st.rowbuf ^ 1), ps_accept flips st.rowbuf when the point is taken.
-// Second half = the same arrays one handle-size further (vio_abi.hip allocates them twice).  Everything else uses half 0 / st.rowbuf.
+// Second half = the same arrays one handle-size further (the array table of vio_handle.h allocates them twice).  Everything else uses half 0 / st.rowbuf.
 __device__ __forceinline__ int fis_early(const SolveSt &st, int chunk, int pslot) { return st.fi[chunk][pslot]; }
 __device__ __forceinline__ void ps_sel_rows(const Batch &B, Ctx &c, int buf) {
     if (!buf) return;

@@ -6,7 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-#include "../../include/vio_abi.h"
+#include "stage_util.h"
 #include "be_linalg.h"
 
 namespace {
@@ -173,31 +173,32 @@ __global__ __launch_bounds__(512) void be_stage_chol_stream_kernel(int nb, int r
 
 }  // namespace
 
-#define ST_CHK(x) do { if ((x) != hipSuccess) { rc = VIO_EDEVICE; goto done; } } while (0)
+// wall-clock ticks of a stage kernel in microseconds
+static void stage_ticks_to_usec(const float *ticks, int count, double *usec) {
+    int rate_khz = 100000, dev = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || rate_khz <= 0) rate_khz = 100000;
+    if (usec) for (int k = 0; k < count; k++) usec[k] = ticks[k] / (rate_khz * 1e-3);
+}
 
 // the streaming path (ps_serial_big): tiles in HBM, one block column in LDS; blocks = -7 forces it for nb <= 11 (bit-for-bit against the LDS path)
 static int stage_chol_stream(int nb, int reps, int blocks, const double *S, const double *rhs, double *L_out, double *x_out, double *usec2) {
-    int rc = VIO_OK;
     const size_t n = 16 * (size_t)nb, ntile = (size_t)nb * (nb + 1) / 2, lds = (((size_t)2 * nb + 1) * 256 + 2 * n) * sizeof(double);
     const int nblk = blocks < 0 ? 1 : blocks;
-    double *dS = nullptr, *dr = nullptr, *dL = nullptr, *dx = nullptr, *dT = nullptr;
-    float *dt = nullptr, ht[5] = {0, 0, 0, 0, 0};
-    int rate_khz = 100000, dev = 0;
-    ST_CHK(hipFuncSetAttribute((const void *)be_stage_chol_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ST_CHK(hipMalloc((void **)&dS, n * n * 8)); ST_CHK(hipMalloc((void **)&dr, n * 8)); ST_CHK(hipMalloc((void **)&dL, n * n * 8));
-    ST_CHK(hipMalloc((void **)&dx, n * 8)); ST_CHK(hipMalloc((void **)&dt, 32)); ST_CHK(hipMalloc((void **)&dT, (size_t)nblk * ntile * 256 * 8));
-    ST_CHK(hipMemcpy(dS, S, n * n * 8, hipMemcpyHostToDevice)); ST_CHK(hipMemcpy(dr, rhs, n * 8, hipMemcpyHostToDevice));
-    ST_CHK(hipMemcpy(dL, L_out, n * n * 8, hipMemcpyHostToDevice));
+    DevBuf<double> dS, dr, dL, dx, dT;
+    DevBuf<float> dt;
+    float ht[5] = {0, 0, 0, 0, 0};
+    HIPCHK(hipFuncSetAttribute((const void *)be_stage_chol_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(dS.alloc(n * n)); HIPCHK(dr.alloc(n)); HIPCHK(dL.alloc(n * n));
+    HIPCHK(dx.alloc(n)); HIPCHK(dt.alloc(8)); HIPCHK(dT.alloc((size_t)nblk * ntile * 256));
+    HIPCHK(dS.upload(S, n * n)); HIPCHK(dr.upload(rhs, n));
+    HIPCHK(dL.upload(L_out, n * n));
     be_stage_chol_stream_kernel<<<nblk, 512, lds>>>(nb, reps, dS, dr, dT, dL, dx, dt, getenv("VIO_STAGE_BACKWARD_BLOCK") ? 1 : 0);
-    ST_CHK(hipDeviceSynchronize());
-    ST_CHK(hipMemcpy(L_out, dL, n * n * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(x_out, dx, n * 8, hipMemcpyDeviceToHost));
-    ST_CHK(hipMemcpy(ht, dt, 20, hipMemcpyDeviceToHost));
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || rate_khz <= 0) rate_khz = 100000;
-    if (usec2) for (int k = 0; k < 5; k++) usec2[k] = ht[k] / (rate_khz * 1e-3);
-done:
-    if (dS) (void)hipFree(dS); if (dr) (void)hipFree(dr); if (dL) (void)hipFree(dL); if (dx) (void)hipFree(dx); if (dt) (void)hipFree(dt); if (dT) (void)hipFree(dT);
-    return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dL.download(L_out, n * n)); HIPCHK(dx.download(x_out, n));
+    HIPCHK(dt.download(ht, 5));
+    stage_ticks_to_usec(ht, 5, usec2);
+    return VIO_OK;
 }
 
 // Harness of sym_eig_hbm (be_linalg.h): one workgroup decomposes the symmetric n x n matrix A (row-major, n <= 512) in place in HBM.  evals[n] (unsorted),
@@ -215,23 +216,18 @@ __global__ __launch_bounds__(512) void be_stage_sym_eig_kernel(double *A, int n,
 }  // namespace
 extern "C" int vio_stage_sym_eig(int n, const double *A, double *evals, double *evecs, double *usec) {   // usec[4]: total, tridiagonalisation, accumulation, QL
     if (n < 2 || n > SYM_EIG_HBM_MAX || !A || !evals || !evecs) return VIO_EINVAL;
-    int rc = VIO_OK;
     const size_t lds = (size_t)SYM_EIG_HBM_LDS_DOUBLES * sizeof(double);
-    double *dA = nullptr, *dv = nullptr;
-    float *dt = nullptr, ht[4] = {0, 0, 0, 0};
-    int rate_khz = 100000, dev = 0;
-    ST_CHK(hipMalloc((void **)&dA, (size_t)n * n * 8)); ST_CHK(hipMalloc((void **)&dv, (size_t)n * 8)); ST_CHK(hipMalloc((void **)&dt, 16));
-    ST_CHK(hipMemcpy(dA, A, (size_t)n * n * 8, hipMemcpyHostToDevice));
+    DevBuf<double> dA, dv;
+    DevBuf<float> dt;
+    float ht[4] = {0, 0, 0, 0};
+    HIPCHK(dA.alloc((size_t)n * n)); HIPCHK(dv.alloc((size_t)n)); HIPCHK(dt.alloc(4));
+    HIPCHK(dA.upload(A, (size_t)n * n));
     be_stage_sym_eig_kernel<<<1, 512, lds>>>(dA, n, dv, dt);
-    ST_CHK(hipDeviceSynchronize());
-    ST_CHK(hipMemcpy(evecs, dA, (size_t)n * n * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(evals, dv, (size_t)n * 8, hipMemcpyDeviceToHost));
-    ST_CHK(hipMemcpy(ht, dt, 16, hipMemcpyDeviceToHost));
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || rate_khz <= 0) rate_khz = 100000;
-    if (usec) for (int k = 0; k < 4; k++) usec[k] = ht[k] / (rate_khz * 1e-3);
-done:
-    if (dA) (void)hipFree(dA); if (dv) (void)hipFree(dv); if (dt) (void)hipFree(dt);
-    return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dA.download(evecs, (size_t)n * n)); HIPCHK(dv.download(evals, (size_t)n));
+    HIPCHK(dt.download(ht, 4));
+    stage_ticks_to_usec(ht, 4, usec);
+    return VIO_OK;
 }
 
 static int stage_chol_blocked(int nb, int nt, const double *S, const double *rhs, double *L_out, double *x_out);
@@ -245,27 +241,22 @@ extern "C" int vio_stage_chol(int nb, int reps, int blocks, const double *S, con
     if (nb < 1 || nb > 24 || reps < 1 || blocks == 0 || blocks < -9 || !S || !rhs || !L_out || !x_out) return VIO_EINVAL;
     if (blocks <= -8) return nb <= 21 ? stage_chol_blocked(nb, blocks == -8 ? 1024 : 512, S, rhs, L_out, x_out) : VIO_EINVAL;
     if (nb > 11 && blocks < 0 && blocks != -7) return VIO_EINVAL;
-    int rc = VIO_OK;
     if (nb > 11 || blocks == -7) return stage_chol_stream(nb, reps, blocks, S, rhs, L_out, x_out, usec5);
     const size_t n = 16 * (size_t)nb, ntile = (size_t)nb * (nb + 1) / 2, lds = (ntile * 256 + 2 * n) * sizeof(double);
-    double *dS = nullptr, *dr = nullptr, *dL = nullptr, *dx = nullptr;
-    float *dt = nullptr, ht[5] = {0, 0, 0, 0, 0};
-    int rate_khz = 100000, dev = 0;
-    ST_CHK(hipFuncSetAttribute((const void *)be_stage_chol_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ST_CHK(hipMalloc((void **)&dS, n * n * 8)); ST_CHK(hipMalloc((void **)&dr, n * 8)); ST_CHK(hipMalloc((void **)&dL, n * n * 8));
-    ST_CHK(hipMalloc((void **)&dx, n * 8)); ST_CHK(hipMalloc((void **)&dt, 32));
-    ST_CHK(hipMemcpy(dS, S, n * n * 8, hipMemcpyHostToDevice)); ST_CHK(hipMemcpy(dr, rhs, n * 8, hipMemcpyHostToDevice));
-    ST_CHK(hipMemcpy(dL, L_out, n * n * 8, hipMemcpyHostToDevice));
+    DevBuf<double> dS, dr, dL, dx;
+    DevBuf<float> dt;
+    float ht[5] = {0, 0, 0, 0, 0};
+    HIPCHK(hipFuncSetAttribute((const void *)be_stage_chol_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(dS.alloc(n * n)); HIPCHK(dr.alloc(n)); HIPCHK(dL.alloc(n * n));
+    HIPCHK(dx.alloc(n)); HIPCHK(dt.alloc(8));
+    HIPCHK(dS.upload(S, n * n)); HIPCHK(dr.upload(rhs, n));
+    HIPCHK(dL.upload(L_out, n * n));
     be_stage_chol_kernel<<<blocks < 0 ? 1 : blocks, 512, lds>>>(nb, reps, blocks < 0 ? -blocks : 0, dS, dr, dL, dx, dt);
-    ST_CHK(hipDeviceSynchronize());
-    ST_CHK(hipMemcpy(L_out, dL, n * n * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(x_out, dx, n * 8, hipMemcpyDeviceToHost));
-    ST_CHK(hipMemcpy(ht, dt, 20, hipMemcpyDeviceToHost));
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || rate_khz <= 0) rate_khz = 100000;
-    if (usec2) for (int k = 0; k < 5; k++) usec2[k] = ht[k] / (rate_khz * 1e-3);
-done:
-    if (dS) (void)hipFree(dS); if (dr) (void)hipFree(dr); if (dL) (void)hipFree(dL); if (dx) (void)hipFree(dx); if (dt) (void)hipFree(dt);
-    return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dL.download(L_out, n * n)); HIPCHK(dx.download(x_out, n));
+    HIPCHK(dt.download(ht, 5));
+    stage_ticks_to_usec(ht, 5, usec2);
+    return VIO_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- ABI 9: the remaining primitives
@@ -392,97 +383,84 @@ extern "C" int vio_stage_jacobi(int mode, int n, int nt, const double *A, double
     if ((mode == 0 || mode == 2) && n > 16) return VIO_EINVAL;
     if (n > JAC_HBM_MAX) return VIO_EINVAL;
     const bool hbm = mode == 3 || (mode == 1 && n > JAC_LDS_MAX);
-    int rc = VIO_OK, hs = 0;
+    int hs = 0;
     const size_t nn = (size_t)n * n, lds = hbm ? 0 : 2 * nn * sizeof(double);
-    double *dA = nullptr, *dV = nullptr;
-    int *ds = nullptr;
+    DevBuf<double> dA, dV;
+    DevBuf<int> ds;
     std::vector<double> hA(nn);
     if ((long)lds > (long)stage_lds_cap((const void *)be_stage_jacobi_kernel)) return VIO_EINVAL;
-    ST_CHK(hipMalloc((void **)&dA, nn * 8)); ST_CHK(hipMalloc((void **)&dV, nn * 8)); ST_CHK(hipMalloc((void **)&ds, 4));
-    ST_CHK(hipMemcpy(dA, A, nn * 8, hipMemcpyHostToDevice));
-    if (lds) ST_CHK(hipFuncSetAttribute((const void *)be_stage_jacobi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(dA.alloc(nn)); HIPCHK(dV.alloc(nn)); HIPCHK(ds.alloc(1));
+    HIPCHK(dA.upload(A, nn));
+    if (lds) HIPCHK(hipFuncSetAttribute((const void *)be_stage_jacobi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     be_stage_jacobi_kernel<<<1, nt, lds>>>(mode, n, dA, dV, ds);
-    ST_CHK(hipDeviceSynchronize());
-    ST_CHK(hipMemcpy(hA.data(), dA, nn * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(evecs, dV, nn * 8, hipMemcpyDeviceToHost));
-    ST_CHK(hipMemcpy(&hs, ds, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dA.download(hA.data(), nn)); HIPCHK(dV.download(evecs, nn));
+    HIPCHK(ds.download(&hs, 1));
     for (int k = 0; k < n; k++) evals[k] = hA[(size_t)k * n + k];
     if (sweeps_out) *sweeps_out = mode == 0 ? 0 : hs;
-done:
-    if (dA) (void)hipFree(dA); if (dV) (void)hipFree(dV); if (ds) (void)hipFree(ds);
-    return rc;
+    return VIO_OK;
 }
 
 extern "C" int vio_stage_sym_eig_lds(int n, int one_wave, int in_hbm, const double *A, double *evals, double *evecs) {
     if (n < 1 || n > 128 || !A || !evals || !evecs) return VIO_EINVAL;
-    int rc = VIO_OK;
     const size_t nn = (size_t)n * n, lds = in_hbm ? 0 : (size_t)n * (n | 1) * sizeof(double);
-    double *dA = nullptr, *dG = nullptr, *dw = nullptr, *dV = nullptr;
-    ST_CHK(hipMalloc((void **)&dA, nn * 8)); ST_CHK(hipMalloc((void **)&dG, nn * 8)); ST_CHK(hipMalloc((void **)&dw, (size_t)n * 8));
-    ST_CHK(hipMalloc((void **)&dV, nn * 8));
-    ST_CHK(hipMemcpy(dA, A, nn * 8, hipMemcpyHostToDevice));
-    if (lds) ST_CHK(hipFuncSetAttribute((const void *)be_stage_sym_eig_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DevBuf<double> dA, dG, dw, dV;
+    HIPCHK(dA.alloc(nn)); HIPCHK(dG.alloc(nn)); HIPCHK(dw.alloc((size_t)n));
+    HIPCHK(dV.alloc(nn));
+    HIPCHK(dA.upload(A, nn));
+    if (lds) HIPCHK(hipFuncSetAttribute((const void *)be_stage_sym_eig_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     be_stage_sym_eig_lds_kernel<<<1, 512, lds>>>(n, one_wave ? 1 : 0, in_hbm ? 1 : 0, dA, dG, dw, dV);
-    ST_CHK(hipDeviceSynchronize());
-    ST_CHK(hipMemcpy(evals, dw, (size_t)n * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(evecs, dV, nn * 8, hipMemcpyDeviceToHost));
-done:
-    if (dA) (void)hipFree(dA); if (dG) (void)hipFree(dG); if (dw) (void)hipFree(dw); if (dV) (void)hipFree(dV);
-    return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dw.download(evals, (size_t)n)); HIPCHK(dV.download(evecs, nn));
+    return VIO_OK;
 }
 
 extern "C" int vio_stage_spd_inverse16(int n, double floor, const double *A, double *Ainv, int *ok_out) {
     if (n < 1 || n > 16 || !A || !Ainv || !ok_out) return VIO_EINVAL;
-    int rc = VIO_OK;
     const size_t nn = (size_t)n * n;
-    double *dA = nullptr, *dI = nullptr;
-    int *dok = nullptr;
-    ST_CHK(hipMalloc((void **)&dA, nn * 8)); ST_CHK(hipMalloc((void **)&dI, nn * 8)); ST_CHK(hipMalloc((void **)&dok, 4));
-    ST_CHK(hipMemcpy(dA, A, nn * 8, hipMemcpyHostToDevice));
+    DevBuf<double> dA, dI;
+    DevBuf<int> dok;
+    HIPCHK(dA.alloc(nn)); HIPCHK(dI.alloc(nn)); HIPCHK(dok.alloc(1));
+    HIPCHK(dA.upload(A, nn));
     be_stage_spd_inv_kernel<<<1, 512>>>(n, floor, dA, dI, dok);
-    ST_CHK(hipDeviceSynchronize());
-    ST_CHK(hipMemcpy(Ainv, dI, nn * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(ok_out, dok, 4, hipMemcpyDeviceToHost));
-done:
-    if (dA) (void)hipFree(dA); if (dI) (void)hipFree(dI); if (dok) (void)hipFree(dok);
-    return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dI.download(Ainv, nn)); HIPCHK(dok.download(ok_out, 1));
+    return VIO_OK;
 }
 
 extern "C" int vio_stage_scan_flags(int n, int nt, int skew, const int *flags, int *offs, int *total_out) {
     if (n < 0 || n > (1 << 20) || nt < 64 || nt > 1024 || (nt & 63) || skew < 0 || skew > 15 || (n > 0 && (!flags || !offs)) || !total_out) return VIO_EINVAL;
-    int rc = VIO_OK;
-    const size_t nb = (size_t)(n > 0 ? n : 1) * 4;
+    const size_t nb = (size_t)(n > 0 ? n : 1);
     const int nout = (skew & 8) ? 2 : 1;
-    int *dsrc = nullptr, *dfl = nullptr, *doffs = nullptr, *dtot = nullptr, htot[3] = {0, 0, 0};
-    ST_CHK(hipMalloc((void **)&dsrc, nb)); ST_CHK(hipMalloc((void **)&dfl, nb)); ST_CHK(hipMalloc((void **)&doffs, nb * nout));
-    ST_CHK(hipMalloc((void **)&dtot, 12));
+    DevBuf<int> dsrc, dfl, doffs, dtot;
+    int htot[3] = {0, 0, 0};
+    HIPCHK(dsrc.alloc(nb)); HIPCHK(dfl.alloc(nb)); HIPCHK(doffs.alloc(nb * nout));
+    HIPCHK(dtot.alloc(3));
     if (n > 0) {
-        ST_CHK(hipMemcpy(dsrc, flags, (size_t)n * 4, hipMemcpyHostToDevice));
-        if (skew & 4) ST_CHK(hipMemset(dfl, 0xff, (size_t)n * 4));   // (whatever the flags held before the writers ran)
-        else ST_CHK(hipMemcpy(dfl, flags, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIPCHK(dsrc.upload(flags, (size_t)n));
+        if (skew & 4) HIPCHK(hipMemset(dfl, 0xff, (size_t)n * 4));   // (whatever the flags held before the writers ran)
+        else HIPCHK(dfl.upload(flags, (size_t)n));
     }
     be_stage_scan_kernel<<<1, nt>>>(n, skew, dsrc, dfl, doffs, dtot, dtot + 2);
-    ST_CHK(hipDeviceSynchronize());
-    if (n > 0) ST_CHK(hipMemcpy(offs, doffs, (size_t)n * 4 * nout, hipMemcpyDeviceToHost));
-    ST_CHK(hipMemcpy(htot, dtot, 12, hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    if (n > 0) HIPCHK(doffs.download(offs, (size_t)n * nout));
+    HIPCHK(dtot.download(htot, 3));
     total_out[0] = htot[0]; total_out[1] = htot[1]; total_out[2] = htot[2];
-done:
-    if (dsrc) (void)hipFree(dsrc); if (dfl) (void)hipFree(dfl); if (doffs) (void)hipFree(doffs); if (dtot) (void)hipFree(dtot);
-    return rc;
+    return VIO_OK;
 }
 
 // blocks = -8 / -9 of vio_stage_chol: chol_blocked + chol_solve_blocked at be_solve_kernel's 1024 / be_solve_kernel_512's 512 threads
 static int stage_chol_blocked(int nb, int nt, const double *S, const double *rhs, double *L_out, double *x_out) {
-    int rc = VIO_OK;
     const size_t n = 16 * (size_t)nb;
-    double *dA = nullptr, *dr = nullptr, *dx = nullptr;
+    DevBuf<double> dA, dr, dx;
     std::vector<double> hA(n * n);
-    ST_CHK(hipMalloc((void **)&dA, n * n * 8)); ST_CHK(hipMalloc((void **)&dr, n * 8)); ST_CHK(hipMalloc((void **)&dx, n * 8));
-    ST_CHK(hipMemcpy(dA, S, n * n * 8, hipMemcpyHostToDevice)); ST_CHK(hipMemcpy(dr, rhs, n * 8, hipMemcpyHostToDevice));
+    HIPCHK(dA.alloc(n * n)); HIPCHK(dr.alloc(n)); HIPCHK(dx.alloc(n));
+    HIPCHK(dA.upload(S, n * n)); HIPCHK(dr.upload(rhs, n));
     be_stage_chol_blocked_kernel<<<1, nt, n * sizeof(double)>>>((int)n, dA, dr, dx);
-    ST_CHK(hipDeviceSynchronize());
-    ST_CHK(hipMemcpy(hA.data(), dA, n * n * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(x_out, dx, n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dA.download(hA.data(), n * n)); HIPCHK(dx.download(x_out, n));
     for (size_t i = 0; i < n; i++) for (size_t j = 0; j <= i; j++) L_out[i * n + j] = hA[i * n + j];
-done:
-    if (dA) (void)hipFree(dA); if (dr) (void)hipFree(dr); if (dx) (void)hipFree(dx);
-    return rc;
+    return VIO_OK;
 }
 
 // ---- the landmark Schur complement (be_solve, solve_mode 0) and be_marg's truncated pseudo-inverse
@@ -538,39 +516,33 @@ extern "C" int vio_stage_schur(int variant, int nb, int nt, int Kpad, unsigned c
     const int n = 16 * nb, ntile = nb * (nb + 1) / 2;
     if (variant >= 1 && ntile * 256 > 16896) return VIO_EINVAL;                  // be_solve's tiles_in_lds
     if (variant == 2 && !schur_staged_ok(n, nt)) return VIO_EINVAL;
-    int rc = VIO_OK, hg = 0;
+    int hg = 0;
     const size_t nn = (size_t)n * n, kw = (size_t)(Kpad > 0 ? Kpad : 1) * n, lds = variant ? ((size_t)ntile * 256 + SCHUR_GUARDS) * sizeof(double) : 0;
-    double *dH = nullptr, *dW = nullptr, *di = nullptr, *dd = nullptr, *ds = nullptr, *dS = nullptr;
-    int *dg = nullptr;
-    ST_CHK(hipMalloc((void **)&dH, nn * 8)); ST_CHK(hipMalloc((void **)&dW, kw * 8)); ST_CHK(hipMalloc((void **)&di, (size_t)(Kpad + 1) * 8));
-    ST_CHK(hipMalloc((void **)&dd, (size_t)n * 8)); ST_CHK(hipMalloc((void **)&ds, (size_t)n * 8)); ST_CHK(hipMalloc((void **)&dS, nn * 8));
-    ST_CHK(hipMalloc((void **)&dg, 4));
-    ST_CHK(hipMemcpy(dH, H, nn * 8, hipMemcpyHostToDevice)); ST_CHK(hipMemcpy(dS, S_out, nn * 8, hipMemcpyHostToDevice));
-    if (Kpad > 0) { ST_CHK(hipMemcpy(dW, Ws, (size_t)Kpad * n * 8, hipMemcpyHostToDevice)); ST_CHK(hipMemcpy(di, inv, (size_t)Kpad * 8, hipMemcpyHostToDevice)); }
-    ST_CHK(hipMemcpy(dd, dgp, (size_t)n * 8, hipMemcpyHostToDevice)); ST_CHK(hipMemcpy(ds, sp, (size_t)n * 8, hipMemcpyHostToDevice));
-    if (lds) ST_CHK(hipFuncSetAttribute((const void *)be_stage_schur_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DevBuf<double> dH, dW, di, dd, ds, dS;
+    DevBuf<int> dg;
+    HIPCHK(dH.alloc(nn)); HIPCHK(dW.alloc(kw)); HIPCHK(di.alloc((size_t)Kpad + 1));
+    HIPCHK(dd.alloc((size_t)n)); HIPCHK(ds.alloc((size_t)n)); HIPCHK(dS.alloc(nn));
+    HIPCHK(dg.alloc(1));
+    HIPCHK(dH.upload(H, nn)); HIPCHK(dS.upload(S_out, nn));
+    if (Kpad > 0) { HIPCHK(dW.upload(Ws, (size_t)Kpad * n)); HIPCHK(di.upload(inv, (size_t)Kpad)); }
+    HIPCHK(dd.upload(dgp, (size_t)n)); HIPCHK(ds.upload(sp, (size_t)n));
+    if (lds) HIPCHK(hipFuncSetAttribute((const void *)be_stage_schur_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     be_stage_schur_kernel<<<1, nt, lds>>>(variant, n, Kpad, colmask, dH, dW, di, dd, ds, mu, dS, dg);
-    ST_CHK(hipDeviceSynchronize());
-    ST_CHK(hipMemcpy(S_out, dS, nn * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(&hg, dg, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dS.download(S_out, nn)); HIPCHK(dg.download(&hg, 1));
     *guard_ok = hg;
-done:
-    if (dH) (void)hipFree(dH); if (dW) (void)hipFree(dW); if (di) (void)hipFree(di); if (dd) (void)hipFree(dd); if (ds) (void)hipFree(ds);
-    if (dS) (void)hipFree(dS); if (dg) (void)hipFree(dg);
-    return rc;
+    return VIO_OK;
 }
 
 extern "C" int vio_stage_pinv15(int n, const double *A, double *Pinv, int *path_out) {
     if (n < 1 || n > 15 || !A || !Pinv || !path_out) return VIO_EINVAL;
-    int rc = VIO_OK;
     const size_t nn = (size_t)n * n;
-    double *dA = nullptr, *dP = nullptr;
-    int *dp = nullptr;
-    ST_CHK(hipMalloc((void **)&dA, nn * 8)); ST_CHK(hipMalloc((void **)&dP, nn * 8)); ST_CHK(hipMalloc((void **)&dp, 4));
-    ST_CHK(hipMemcpy(dA, A, nn * 8, hipMemcpyHostToDevice));
+    DevBuf<double> dA, dP;
+    DevBuf<int> dp;
+    HIPCHK(dA.alloc(nn)); HIPCHK(dP.alloc(nn)); HIPCHK(dp.alloc(1));
+    HIPCHK(dA.upload(A, nn));
     be_stage_pinv15_kernel<<<1, 512>>>(n, dA, dP, dp);
-    ST_CHK(hipDeviceSynchronize());
-    ST_CHK(hipMemcpy(Pinv, dP, nn * 8, hipMemcpyDeviceToHost)); ST_CHK(hipMemcpy(path_out, dp, 4, hipMemcpyDeviceToHost));
-done:
-    if (dA) (void)hipFree(dA); if (dP) (void)hipFree(dP); if (dp) (void)hipFree(dp);
-    return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dP.download(Pinv, nn)); HIPCHK(dp.download(path_out, 1));
+    return VIO_OK;
 }
