@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import vio_ct
+from posegraph_cases import blur_def
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -79,14 +80,9 @@ def test_blur_is_the_fixed_point_gaussian():
     img = rng.integers(0, 256, (60, 80), dtype=np.uint8)
     out = np.zeros_like(img)
     L.ovio_pg_blur(img.ctypes.data, 80, 60, out.ctypes.data)
-    # definition: exp(-x^2 / (2 sigma^2)) normalised, 8 fractional bits per pass, REFLECT_101, one rounding at the end
-    k = np.exp(-np.arange(-4, 5) ** 2 / 8.0)
-    ki = np.rint(k / k.sum() * 256).astype(np.int64)
-    assert ki.sum() == 256 and list(ki) == [7, 17, 32, 46, 52, 46, 32, 17, 7]
-    pad = np.pad(img.astype(np.int64), 4, mode="reflect")
-    h = sum(ki[i] * pad[:, i:i + 80] for i in range(9))
-    v = sum(ki[i] * h[i:i + 60, :] for i in range(9))
-    assert np.array_equal(out, ((v + (1 << 15)) >> 16).astype(np.uint8))
+    # definition (posegraph_cases.blur_def, which asserts the taps 7 17 32 46 52 46 32 17 7 and their sum 256): exp(-x^2 / (2 sigma^2))
+    # normalised, 8 fractional bits per pass, REFLECT_101, one rounding at the end
+    assert np.array_equal(out, blur_def(img))
     flat = np.full((40, 40), 93, np.uint8); o2 = np.zeros_like(flat)
     L.ovio_pg_blur(flat.ctypes.data, 40, 40, o2.ctypes.data)
     assert np.all(o2 == 93)
