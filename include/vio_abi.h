@@ -324,6 +324,21 @@ int vio_set_tracker_lag(vio_batch *h, int lag);
  * updateLatestStates :1768-1788): the newest window state propagated through every IMU sample pushed after it.
  * out11 = t, P(3), Q(w, x, y, z), V(3).  INITIAL sequences and VO mode return the window state unchanged. */
 int vio_get_latest_odometry(vio_batch *h, int seq, double *out11);
+/* vio_get_latest_odometry for every sequence in one launch and one copy: out[S][11], the same bits per row.  on_device != 0: out is an
+ * HBM address on the handle's device and nothing but the launch crosses the bus. */
+int vio_get_latest_odometry_all(vio_batch *h, double *out, int on_device);
+/* The IMU-rate stream itself: pubLatestOdometry publishes one pose per IMU sample, and this returns, for every sequence, the row
+ * t, P(3), Q(w, x, y, z), V(3) after EVERY sample newer than the window state (row k is what vio_get_latest_odometry returned when the
+ * k-th of them had just been pushed, bit for bit).  One launch and one copy for the whole batch.
+ *   since   [S] host doubles or NULL: only rows with t > since[s] are counted and returned, so a poller passes the last stamp it has
+ *           received and gets the new rows only.  The propagation still starts at the window state: an optimisation in between
+ *           re-anchors the rows, as it does upstream.  NULL: every applied sample.
+ *   n_rows  [S] host: the number of such rows, which may exceed cap
+ *   out     [S][cap][11]: the first min(n_rows[s], cap) rows of sequence s in time order; rows beyond them are left untouched.
+ *           on_device != 0: an HBM address on the handle's device (only n_rows comes back to the host).  cap == 0 (out may be NULL) only counts.
+ * The bytes copied back grow with S * cap, whatever n_rows turns out to be: a poller sets cap near the rows it expects per poll.
+ * INITIAL sequences and VO mode apply no sample: n_rows[s] = 0.  Samples the ring has overwritten (imu_capacity) are not applied. */
+int vio_get_imu_rate_odometry(vio_batch *h, const double *since, int cap, int32_t *n_rows, double *out, int on_device);
 /* Estimator::setReloFrame(frame_stamp, frame_index, match_points, relo_t, relo_r) (estimator.h:48-49, estimator.cpp:1728-1747) for
  * sequence seq: the window frame stamped frame_stamp has been matched with an old keyframe (pose relo_t / relo_r in the loop-closed
  * world, relo_r row-major); match_points[n][3] = (x, y) normalised point of the old keyframe and the feature id it matched (z), in

@@ -9,7 +9,8 @@ slot with the calibration of its own configuration file (dataio.batch_config_fro
 setting); --gt then applies to the first recording.
 
     --save-at FRAME --snapshot FILE   (one recording) write the sequence's snapshot after frame FRAME to FILE, the replay's own state to FILE.json
-    --resume FILE                     (one recording) restore FILE and continue behind the saved frame; --out then holds the rows from there on"""
+    --resume FILE                     (one recording) restore FILE and continue behind the saved frame; --out then holds the rows from there on
+    --imu-rate-out FILE               (one recording) the IMU-rate poses (pubLatestOdometry: one row per IMU sample, the layout of --out)"""
 import argparse
 import importlib
 import os
@@ -31,6 +32,7 @@ def parse_args(argv=None):
     ap.add_argument("--save-at", type=int, default=None, help="frame index after which the snapshot is written (with --snapshot)")
     ap.add_argument("--snapshot", default=None, help="snapshot file to write (its sidecar FILE.json holds the frame gate's state)")
     ap.add_argument("--resume", default=None, help="snapshot file to restore before replaying the frames behind it")
+    ap.add_argument("--imu-rate-out", default=None, help="file for the IMU-rate poses: one row per IMU sample, the layout of --out")
     ap.add_argument("--lenient", action="store_true", help="warn instead of failing on settings outside the built hot path")
     a = ap.parse_args(argv)
     n = len(a.config)
@@ -38,16 +40,16 @@ def parse_args(argv=None):
         ap.error("%d --config but %d --data: give one --data per --config" % (n, len(a.data)))
     if (a.save_at is None) != (a.snapshot is None):
         ap.error("--save-at and --snapshot go together")
-    if n > 1 and (a.snapshot or a.resume):
-        ap.error("--snapshot / --resume work on one recording")
+    if n > 1 and (a.snapshot or a.resume or a.imu_rate_out):
+        ap.error("--snapshot / --resume / --imu-rate-out work on one recording")
     outs = a.out if a.out is not None else (["vins_result.csv"] if n == 1 else ["vins_result_%d.csv" % i for i in range(n)])
     if len(outs) != n:
         ap.error("%d --config but %d --out: give one --out per --config, or none" % (n, len(outs)))
     return a, list(zip(a.config, a.data, outs))
 
 
-def main():
-    a, triples = parse_args()
+def main(argv=None):
+    a, triples = parse_args(argv)
     P = importlib.import_module("vins-rgbd-fast_amd")
     io = importlib.import_module("vins-rgbd-fast_amd.dataio")
     if len(triples) > 1:
@@ -76,8 +78,11 @@ def main():
         if extra["camera"] is not None:   # KANNALA_BRANDT / MEI (dataio.config_from_yaml)
             b.set_camera(0, extra["camera"])
         rows = io.replay(b, rec, out, freq=extra["freq"], frontend_freq=extra["frontend_freq"],
-                         save_at=a.save_at, snapshot=a.snapshot, resume=a.resume)  # freq / frontend_freq: estimator_nodelet.cpp:264-286
+                         save_at=a.save_at, snapshot=a.snapshot, resume=a.resume,  # freq / frontend_freq: estimator_nodelet.cpp:264-286
+                         imu_rate=a.imu_rate_out)
         print("%d frames, %d odometry rows -> %s" % (len(rec), len(rows), out))
+        if a.imu_rate_out:
+            print("IMU-rate poses -> %s" % a.imu_rate_out)
     if a.gt and len(rows) > 3:
         gt = np.loadtxt(a.gt, comments="#", ndmin=2)
         gp = np.array([gt[np.argmin(np.abs(gt[:, 0] - t)), 1:4] for t in rows[:, 0]])

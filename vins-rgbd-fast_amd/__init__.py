@@ -282,6 +282,8 @@ def lib():
         if L.vio_abi_sizeof(2) != C.sizeof(Calibration):
             raise VioError("vio_calibration mirror does not match the library (%d != %d bytes)" % (C.sizeof(Calibration), L.vio_abi_sizeof(2)))
         L.vio_get_latest_odometry.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.vio_get_latest_odometry_all.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.vio_get_imu_rate_odometry.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.vio_set_tracker_lag.argtypes = [C.c_void_p, C.c_int]
         L.vio_set_fisheye_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.vio_get_status_all.argtypes = [C.c_void_p, C.c_void_p]
@@ -763,6 +765,33 @@ class VioBatch:
         o = np.zeros(11)
         self._chk(self.L.vio_get_latest_odometry(self.h, seq, o.ctypes.data), "vio_get_latest_odometry")
         return o
+
+    def latest_odometry_all(self, out=None):
+        """latest_odometry of every sequence in one launch and one copy: [S, 11].  out = a device address (DeviceBuffer.ptr, a torch tensor)
+        that receives the rows instead; nothing is returned then."""
+        if out is not None:
+            self._chk(self.L.vio_get_latest_odometry_all(self.h, _ptr(out), 1), "vio_get_latest_odometry_all")
+            return None
+        o = np.zeros((self.S, 11))
+        self._chk(self.L.vio_get_latest_odometry_all(self.h, o.ctypes.data, 0), "vio_get_latest_odometry_all")
+        return o
+
+    def imu_rate_odometry(self, since=None, cap=256, out=None):
+        """The pose after every IMU sample newer than the window state, for every sequence (what pubLatestOdometry publishes, one row per
+        sample): (n_rows [S], rows [S, cap, 11]).  rows[s, :min(n_rows[s], cap)] are t, P(3), Q(wxyz), V(3) in time order, the rest is
+        zero; n_rows may exceed cap.  since = [S] stamps: only rows with t > since[s] (a poller passes the last stamp it received).
+        out = a device address that receives [S][cap][11] instead: only n_rows is returned then.  cap = 0 only counts."""
+        cap = int(cap)
+        n = np.zeros(self.S, np.int32)
+        sn = None if since is None else np.ascontiguousarray(since, np.float64).reshape(self.S)
+        sp = None if sn is None else sn.ctypes.data
+        if out is not None:
+            self._chk(self.L.vio_get_imu_rate_odometry(self.h, sp, cap, n.ctypes.data, _ptr(out), 1), "vio_get_imu_rate_odometry")
+            return n
+        rows = np.zeros((self.S, max(cap, 0), 11))
+        self._chk(self.L.vio_get_imu_rate_odometry(self.h, sp, cap, n.ctypes.data, rows.ctypes.data if cap > 0 else None, 0),
+                  "vio_get_imu_rate_odometry")
+        return n, rows
 
     def set_relo_frame(self, seq, stamp, index, match_points, relo_t, relo_r):
         """Estimator::setReloFrame (estimator.cpp:1728-1747): match_points[n][3] = (x, y, feature id) ascending in id"""

@@ -158,6 +158,66 @@ int vio_get_latest_odometry(vio_batch *h, int seq, double *out11) {
     return VIO_OK;
 }
 
+// staging of the two batched getters below: at least `dev` doubles in HBM and `host` doubles of page-locked memory (nothing of the handle
+// is in flight when they are regrown: the callers have synchronised)
+static int odo_stage(vio_batch *h, size_t dev, size_t host) {
+    if (dev > h->odo_cap) {
+        dev_release(h, h->d_odo);
+        h->odo_cap = 0;
+        VIO_TRY(dev_alloc(h, &h->d_odo, dev, false));
+        h->odo_cap = dev;
+    }
+    if (host > h->h_odo_cap) {
+        pinned_release(h, h->h_odo);
+        h->h_odo_cap = 0;
+        VIO_TRY(pinned_alloc(h, &h->h_odo, host));
+        h->h_odo_cap = host;
+    }
+    return VIO_OK;
+}
+
+int vio_get_latest_odometry_all(vio_batch *h, double *out, int on_device) {
+    VIO_ENTER(h, VIO_NO_SEQ, false);
+    if (!out) return VIO_EINVAL;
+    VIO_TRY(flush_imu_backend(h));   // samples pushed so far must be in the ring
+    VIO_TRY(sync_all(h));
+    const size_t S = (size_t)h->S, o_last = (S + 1) / 2;   // n_rows [S] (int32), then last [S][11]
+    VIO_TRY(odo_stage(h, o_last + (on_device ? 0 : S * 11), 0));
+    double *last = on_device ? out : h->d_odo + o_last;
+    be_imu_rate_odometry_kernel<<<h->S, 64, 0, h->stream>>>(h->B, nullptr, 0, (int *)h->d_odo, nullptr, last);
+    HIPCHK(hipGetLastError());
+    if (!on_device) HIPCHK(hipMemcpyAsync(out, last, S * 11 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return VIO_OK;
+}
+
+int vio_get_imu_rate_odometry(vio_batch *h, const double *since, int cap, int32_t *n_rows, double *out, int on_device) {
+    VIO_ENTER(h, VIO_NO_SEQ, false);
+    if (cap < 0 || !n_rows || (cap > 0 && !out)) return VIO_EINVAL;
+    VIO_TRY(flush_imu_backend(h));   // samples pushed so far must be in the ring
+    VIO_TRY(sync_all(h));
+    // staging, in doubles: since [S], n_rows [S] (int32), rows [S][cap][11] (host output only); the host image holds n_rows and the rows
+    const size_t S = (size_t)h->S, o_n = S, o_rows = o_n + (S + 1) / 2, n_row_doubles = on_device ? 0 : S * (size_t)cap * 11;
+    VIO_TRY(odo_stage(h, o_rows + n_row_doubles, o_rows + n_row_doubles));
+    double *d = h->d_odo, *hb = h->h_odo;
+    if (since) {
+        memcpy(hb, since, S * sizeof(double));
+        HIPCHK(hipMemcpyAsync(d, hb, S * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    be_imu_rate_odometry_kernel<<<h->S, 64, 0, h->stream>>>(h->B, since ? d : nullptr, cap, (int *)(d + o_n), on_device ? out : d + o_rows, nullptr);
+    HIPCHK(hipGetLastError());
+    // one copy back: the counts and, for a host output, the rows behind them
+    HIPCHK(hipMemcpyAsync(hb + o_n, d + o_n, (o_rows - o_n + n_row_doubles) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int32_t *cnt = (const int32_t *)(hb + o_n);
+    for (size_t s = 0; s < S; s++) {
+        n_rows[s] = cnt[s];
+        const size_t m = (size_t)std::min(cnt[s], cap);
+        if (!on_device && m > 0) memcpy(out + s * (size_t)cap * 11, hb + o_rows + s * (size_t)cap * 11, m * 11 * sizeof(double));
+    }
+    return VIO_OK;
+}
+
 int vio_get_packaged(vio_batch *h, int seq, int cap, int32_t *ids, double *obs) {
     VIO_ENTER(h, seq, true);
     static thread_local FeSeq fe;

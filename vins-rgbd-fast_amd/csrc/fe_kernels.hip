@@ -296,6 +296,119 @@ __global__ void be_latest_odometry_kernel(Batch B, int seq, double *out11) {
     out11[0] = latest_time; out11[1] = P.x; out11[2] = P.y; out11[3] = P.z;
     out11[4] = q.w; out11[5] = q.x; out11[6] = q.y; out11[7] = q.z; out11[8] = V.x; out11[9] = V.y; out11[10] = V.z;
 }
+// The same propagation for EVERY sequence in one launch, with the pose at every applied sample (what pubLatestOdometry publishes, one
+// message per IMU sample), by one wavefront per sequence in the way of predict_motion_wave: 64 ring entries are read at once, the first
+// sample newer than the window state is found with a ballot (vio_push_imu keeps only ascending stamps, so the applied samples are a
+// suffix of the ring), every lane forms dt, un_gyr and the rotation increment of its own sample (the sample before it comes through a
+// lane shift, or from the carry of the previous chunk / be.acc_0, be.gyr_0 and the window time for lane 0), the ordered product
+// R <- R * dR runs sequentially on broadcast matrices and lane q keeps R before and after its own step, every lane forms its un_acc, and
+// the (P, V) recurrence runs sequentially on broadcast (dt, un_acc) with lane q keeping its own (P, V).  The same expressions on the same
+// operands as be_latest_odometry_kernel above, hence the same bits in every row (no contraction in this build).
+//   since    [S] or NULL: only rows with t > since[s] count and are stored (NULL: every applied sample)
+//   n_rows   [S] number of such rows (may exceed cap)
+//   rows     [S][cap][11]: the first min(n_rows[s], cap) of them in time order; nothing else is written.  Not read when cap == 0
+//   last     [S][11] or NULL: the final state, i.e. what be_latest_odometry_kernel writes for the sequence
+// grid S, 64 threads.  Output only: no field of be / fe and no ring entry is written.
+__global__ __launch_bounds__(64) void be_imu_rate_odometry_kernel(Batch B, const double *since, int cap, int *n_rows, double *rows, double *last) {
+    const int s = blockIdx.x;
+    if (s >= B.S) return;
+    const int lane = threadIdx.x & 63;
+    const DevCfg &C = *B.cfg;
+    const BeSeq &be = B.be[s];
+    const int fc = be.frame_count;
+    double latest_time = be.Headers[fc] + be.td;
+    dm::v3 P = dm::ld3(be.Ps[fc]), V = dm::ld3(be.Vs[fc]);
+    const dm::v3 Ba = dm::ld3(be.Bas[fc]), Bg = dm::ld3(be.Bgs[fc]), g = dm::ld3(be.g);
+    dm::m3 R = dm::ldm(be.Rs[fc]);
+    const dm::v3 acc_0 = dm::ld3(be.acc_0), gyr_0 = dm::ld3(be.gyr_0);
+    const double *it = B.imu_t + (size_t)s * C.NIMU, *ia = B.imu_acc + (size_t)s * C.NIMU * 3, *ig = B.imu_gyr + (size_t)s * C.NIMU * 3;
+    const int imu_count = be.imu_count;
+    int k = be.imu_head;
+    if (imu_count - k > C.NIMU) k = imu_count - C.NIMU;  // ring bookkeeping: samples that were overwritten
+    const bool front = (C.c.reference_quirks & VIO_QUIRK_LATEST_FRONT) != 0;
+    const int idx_front = k % C.NIMU;
+    const int n_front = be.imu_count_ingest;
+    const bool all = since == nullptr;
+    const double since_s = all ? 0.0 : since[s];
+    double *out = rows + (size_t)s * (size_t)cap * 11;
+    int nq = 0;   // rows with t > since[s] so far
+    if (be.solver_flag == 1 && C.c.use_imu) {
+        // first sample with t > latest_time
+        while (k < imu_count) {
+            const int j = k + lane;
+            const bool le = j < imu_count && !(it[j % C.NIMU] > latest_time);
+            const unsigned long long bal = __ballot(le);
+            if (bal == ~0ULL) { k += 64; continue; }
+            k += __builtin_ctzll(~bal);   // stamps ascend: the lanes with t <= latest_time are a prefix
+            break;
+        }
+        // the sample before the chunk's first one: the window state's time and processIMU's acc_0 / gyr_0, then the previous chunk's last
+        double prev_t = latest_time;
+        dm::v3 prev_a = acc_0, prev_w = gyr_0;
+        while (k < imu_count) {
+            const int j = k + lane;
+            const int nv = imu_count - k < 64 ? imu_count - k : 64;   // every remaining sample is applied
+            const bool in = lane < nv;
+            const int idx = in ? j % C.NIMU : idx_front;
+            const double tk = it[idx];
+            // quirk mode: front values only for the samples that were in the ring when the frame was taken (be_latest_odometry_kernel)
+            const int iv = (front && j < n_front) ? idx_front : idx;
+            const dm::v3 a1 = dm::ld3(ia + (size_t)iv * 3), w1 = dm::ld3(ig + (size_t)iv * 3);
+            double pt = __shfl_up(tk, 1, 64);
+            dm::v3 pa = dm::mk(__shfl_up(a1.x, 1, 64), __shfl_up(a1.y, 1, 64), __shfl_up(a1.z, 1, 64));
+            dm::v3 pw = dm::mk(__shfl_up(w1.x, 1, 64), __shfl_up(w1.y, 1, 64), __shfl_up(w1.z, 1, 64));
+            if (lane == 0) { pt = prev_t; pa = prev_a; pw = prev_w; }
+            if (front) { pa = acc_0; pw = gyr_0; }   // predict() never advances acc_0 / gyr_0
+            const double dt = tk - pt;
+            const dm::v3 un_gyr = dm::sub(dm::scl(0.5, dm::add(pw, w1)), Bg);
+            const dm::m3 dR = dm::q2R(dm::deltaQ(dm::scl(dt, un_gyr)));
+            dm::m3 Rb = R, Ra = R;   // R before and after my step
+            for (int q = 0; q < nv; q++) {
+                dm::m3 Mq;
+#pragma unroll
+                for (int e = 0; e < 9; e++) Mq.a[e] = lane_bcast(dR.a[e], q);
+                const dm::m3 Rn = dm::mul(R, Mq);
+                if (lane == q) { Rb = R; Ra = Rn; }
+                R = Rn;
+            }
+            const dm::v3 un_acc_0 = dm::sub(dm::mul(Rb, dm::sub(pa, Ba)), g);
+            const dm::v3 un_acc_1 = dm::sub(dm::mul(Ra, dm::sub(a1, Ba)), g);
+            const dm::v3 un_acc = dm::scl(0.5, dm::add(un_acc_0, un_acc_1));
+            dm::v3 Pm = P, Vm = V;   // (P, V) after my step
+            for (int q = 0; q < nv; q++) {
+                const double dq = lane_bcast(dt, q);
+                const dm::v3 uq = dm::mk(lane_bcast(un_acc.x, q), lane_bcast(un_acc.y, q), lane_bcast(un_acc.z, q));
+                P = dm::add(dm::add(P, dm::scl(dq, V)), dm::scl(0.5 * dq * dq, uq));
+                V = dm::add(V, dm::scl(dq, uq));
+                if (lane == q) { Pm = P; Vm = V; }
+            }
+            const bool mine = in && (all || tk > since_s);
+            const unsigned long long bal = __ballot(mine);
+            const int r = nq + __popcll(bal & ((1ULL << lane) - 1ULL));
+            if (mine && r < cap) {
+                const dm::quat qm = dm::R2q(Ra);
+                double *o = out + (size_t)r * 11;
+                o[0] = tk; o[1] = Pm.x; o[2] = Pm.y; o[3] = Pm.z;
+                o[4] = qm.w; o[5] = qm.x; o[6] = qm.y; o[7] = qm.z; o[8] = Vm.x; o[9] = Vm.y; o[10] = Vm.z;
+            }
+            nq += __popcll(bal);
+            prev_t = lane_bcast(tk, nv - 1);
+            prev_a = dm::mk(lane_bcast(a1.x, nv - 1), lane_bcast(a1.y, nv - 1), lane_bcast(a1.z, nv - 1));
+            prev_w = dm::mk(lane_bcast(w1.x, nv - 1), lane_bcast(w1.y, nv - 1), lane_bcast(w1.z, nv - 1));
+            latest_time = prev_t;
+            k += 64;
+        }
+    }
+    if (lane == 0) {
+        n_rows[s] = nq;
+        if (last) {
+            const dm::quat q = dm::R2q(R);
+            double *o = last + (size_t)s * 11;
+            o[0] = latest_time; o[1] = P.x; o[2] = P.y; o[3] = P.z;
+            o[4] = q.w; o[5] = q.x; o[6] = q.y; o[7] = q.z; o[8] = V.x; o[9] = V.y; o[10] = V.z;
+        }
+    }
+}
 
 // vio_predict_motion: one sequence, result to out9 (row-major)
 __global__ void fe_predict_motion_kernel(Batch B, int seq, double t0, double t1, double *out9) {

@@ -279,6 +279,29 @@ class OdometryCsvWriter:
         self.f.close()
 
 
+class ImuRateCsvWriter(OdometryCsvWriter):
+    """The IMU-rate stream of one slot (pubLatestOdometry: one pose per IMU sample) in the layout of the odometry file.  poll() appends the
+    rows of VioBatch.imu_rate_odometry that are newer than the last one written, so the stamps in the file ascend strictly."""
+
+    def __init__(self, path, append=False, cap=64):
+        OdometryCsvWriter.__init__(self, path, append)
+        self.last, self.last_row, self.n, self.cap = -np.inf, None, 0, int(cap)
+
+    def poll(self, batch, seq=0):
+        """one launch and one copy for the whole handle; the other slots are asked for nothing (since = +inf).  Returns the new rows."""
+        since = np.full(batch.S, np.inf)
+        since[seq] = self.last
+        n, rows = batch.imu_rate_odometry(since, self.cap)
+        if n[seq] > self.cap:   # more new samples than a poll expected: once more with room for all of them
+            self.cap = int(n[seq])
+            n, rows = batch.imu_rate_odometry(since, self.cap)
+        new = rows[seq, :n[seq]]
+        if len(new):
+            self.write_rows(new)
+            self.last, self.last_row, self.n = float(new[-1, 0]), new[-1].copy(), self.n + len(new)
+        return new
+
+
 def read_odometry_csv(path):
     rows = []
     for line in open(path):
@@ -495,7 +518,8 @@ def snapshot_sidecar(path):
     return path + ".json"
 
 
-def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_freq=0, save_at=None, snapshot=None, resume=None):
+def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_freq=0, save_at=None, snapshot=None, resume=None,
+           imu_rate=None, before_feed=None):
     """Feed a recording through a single-sequence slot of a VioBatch the way the nodelet does: push IMU through the frame stamp
     (one sample beyond, so that IMUAvailable holds), run the frame gate (``freq`` / ``frontend_freq`` of the configuration file;
     frontend_freq == 0 disables the gate: every frame is published), feed the pair with the gate's mode, append a CSV row whenever
@@ -505,8 +529,13 @@ def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_fre
     caller-side state -- frame index, position in the IMU stream, FrameGate state, the init_pub / init_feature mirror -- to FILE.json.
     resume = FILE: the slot is restored from FILE (VioBatch.load: the handle must have the shape key of the one that saved) and the replay
     starts behind the saved frame: IMU from the sample after the last one pushed, images from the next frame; the rows it returns and writes
-    are those of the frames it feeds."""
+    are those of the frames it feeds.
+    imu_rate = FILE (or an ImuRateCsvWriter): the IMU-rate poses of the slot.  Once the IMU of a frame interval has been pushed, and once
+    more after the last frame, the file gets the pose at every sample newer than the last one written, each propagated from the newest
+    window state of that moment: what a subscriber of pubLatestOdometry receives.  before_feed(f, batch) is called after that, right before
+    frame f is handed to the gate."""
     rows, k, f0 = [], 0, 0
+    ir = ImuRateCsvWriter(imu_rate) if isinstance(imu_rate, str) else imu_rate
     wr = OdometryCsvWriter(csv_path, append=False) if csv_path else None
     S = batch.S
     gate = FrameGate(freq, frontend_freq) if int(frontend_freq) > 0 else None
@@ -533,6 +562,10 @@ def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_fre
         if k2 > k:
             batch.push_imu(seq, rec.imu_t[k:k2], rec.imu_acc[k:k2], rec.imu_gyr[k:k2])
             k = k2
+        if ir is not None:
+            ir.poll(batch, seq)
+        if before_feed:
+            before_feed(f, batch)
         mode = FrameGate.PUBLISH
         if gate is not None:
             d = gate.step(t)
@@ -571,6 +604,10 @@ def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_fre
                                gate=None if gate is None else gate.state()), fd)
     if wr:
         wr.close()
+    if ir is not None:
+        ir.poll(batch, seq)
+        if isinstance(imu_rate, str):
+            ir.close()
     return np.array(rows).reshape(-1, 11)
 
 
