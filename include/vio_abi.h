@@ -203,10 +203,20 @@ int vio_predict_motion(vio_batch *h, int seq, double t0, double t1, double *R9);
  * feature map for sequence seq: n entries in ascending feature id (std::map order), xyz_uv_vel[n][7] = (x, y, z = 1, u, v, vx, vy)
  * exactly as estimator_nodelet.cpp:336-363 packs them, depth_mm = the CV_16UC1 depth image of THAT frame (host memory), stamp =
  * header stamp.  This is what the process thread pops from feature_buf (estimator_nodelet.cpp:380-384, 539), so the tracker may
- * run ahead of the estimator by any number of frames.  n <= the tracker capacity (max_cnt + grid slack, see vio_get_capacity). */
+ * run ahead of the estimator by any number of frames.  n <= the tracker capacity (max_cnt + grid slack, see vio_get_capacity).
+ * Feature ids are NON-NEGATIVE, as the reference's are (its tracker counts them up from 0): -1 is the empty key of the back end's
+ * id -> slot table.  A map with a negative id is refused with VIO_EINVAL (text in vio_last_error) before anything is uploaded or
+ * launched; the sequence is untouched.  The order of the entries is free: the landmarks a map introduces are appended in the map's order
+ * (ascending ids reproduce the reference's list order).
+ * IMU: the samples of one frame interval are kept per window slot (64 of them) for as long as the sequence runs, because a non-keyframe's
+ * samples are re-propagated into the previous slot (MARGIN_SECOND_NEW).  A frame interval with more than 64 samples, i.e. an IMU rate above
+ * 64 x the rate of processed frames, raises overflow flag 2 and that merge then misses the samples beyond the 64th. */
 int vio_process_obs(vio_batch *h, int seq, int n, const int32_t *ids, const double *xyz_uv_vel, const uint16_t *depth_mm, double stamp);
 /* The same for the whole batch: n_obs[S] (a negative count skips the sequence), ids[S][cap], xyz_uv_vel[S][cap][7], depth_mm
- * [S][height][width], stamps[S]; the feature arrays are host memory, depth_mm is HBM when on_device != 0. */
+ * [S][height][width], stamps[S]; the feature arrays are host memory, depth_mm is HBM when on_device != 0.  A negative id in any sequence's
+ * map refuses the whole call with VIO_EINVAL, as above.  (The maps that reach the back end from device memory -- vio_process, vio_feed: what
+ * the handle's own tracker packaged -- cannot be checked by the host; their ids are non-negative by construction, and a caller that writes
+ * such device buffers itself must keep that precondition.) */
 int vio_process_obs_batch(vio_batch *h, const int32_t *n_obs, const int32_t *ids, const double *xyz_uv_vel, int cap,
                           const uint16_t *depth_mm, const double *stamps, int on_device);
 /* The feature map packaged by the last vio_track / vio_feed for sequence seq (what the nodelet would push to feature_buf):
@@ -280,7 +290,7 @@ typedef struct vio_status {
     int32_t n_in_problem, n_residuals, n_var_landmarks, has_prior;
     int32_t reboot_count, frames_processed;
     double initial_cost, final_cost, td;
-    int32_t overflow_flags;       /* capacity flags of the last frame: 1 landmark table, 2 IMU slot (> 64 samples per frame interval),
+    int32_t overflow_flags;       /* capacity flags of the last frame: 1 landmark table, 2 IMU slot (> 64 samples per frame interval: IMU rate / frame rate must be <= 64, see vio_process_obs),
                                      4 FAST candidates of a cell, 8 residual list, 16 IMU ring overwritten, 32 solver iteration slots
                                      exhausted before the trust-region loop finished, 64 relocalisation request dropped (vio_set_relo_frame),
                                      128 extrinsic-calibration history full: its oldest pair was dropped (estimate_extrinsic = 2, see

@@ -1357,6 +1357,11 @@ int vio_process_obs_batch(vio_batch *h, const int32_t *n_obs, const int32_t *ids
     const int NP = h->hc.NP;
     for (int s = 0; s < h->S; s++)
         if (n_obs[s] > cap || n_obs[s] > NP) { g_err = "feature map larger than the tracker capacity (vio_get_capacity)"; return VIO_ECAPACITY; }
+    // feature ids are non-negative (the reference's tracker counts them up from 0) and -1 is the empty key of be_ingest's id -> slot table:
+    // checked here, before anything is uploaded or launched
+    for (int s = 0; s < h->S; s++)
+        for (int j = 0; j < n_obs[s]; j++)
+            if (ids[(size_t)s * cap + j] < 0) { g_err = "negative feature id in a caller-supplied feature map"; return VIO_EINVAL; }
     VIO_TRY(wait_host_uploads(h));
     VIO_TRY(refresh_dynamic_state(h));
     VIO_TRY(flush_imu_backend(h));
@@ -1387,6 +1392,8 @@ int vio_process_obs(vio_batch *h, int seq, int n, const int32_t *ids, const doub
     const DevCfg &C = h->hc;
     const int NP = C.NP;
     if (n > NP) { g_err = "feature map larger than the tracker capacity (vio_get_capacity)"; return VIO_ECAPACITY; }
+    for (int j = 0; j < n; j++)   // (as in vio_process_obs_batch: before any upload or launch)
+        if (ids[j] < 0) { g_err = "negative feature id in a caller-supplied feature map"; return VIO_EINVAL; }
     VIO_TRY(wait_host_uploads(h));
     VIO_TRY(flush_imu_backend(h));
     vio_batch::Group *gp = &h->groups[0];

@@ -20,7 +20,10 @@
 #include "dmath.h"
 
 #define VIO_MAXW 20
-#define VIO_IMU_SLOT_CAP 64  // IMU samples kept per window slot for repropagate() (only read until initialisation)
+// IMU samples kept per window slot.  Read by repropagate() until initialisation AND, for as long as the sequence runs, by the
+// MARGIN_SECOND_NEW merge of be_finish, which re-propagates slot W's samples into slot W - 1 on every non-keyframe: a frame interval
+// with more samples (IMU rate / frame rate > 64) is flagged (overflow bit 2) and loses the rest in that merge.
+#define VIO_IMU_SLOT_CAP 64
 #define VIO_OBS_D 9          // x y z u v vx vy cur_td depth  (FeaturePerFrame)
 #define VIO_MAX_CELLS 64
 #define VIO_FAST_CAP 1024    // NMS survivors kept per grid cell (before mask filter)
