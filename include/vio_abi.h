@@ -550,6 +550,35 @@ int vio_stage_host_sfm_window(int window_size, int nf, const int32_t *start, con
 int vio_stage_imu_block(const vio_config *cfg, int n, const double *dt, const double *acc, const double *gyr, const double *acc0,
                         const double *gyr0, const double *ba, const double *bg, const double *pose_i, const double *sb_i,
                         const double *pose_j, const double *sb_j, double *G961);
+/* Harnesses of the factor code alone (be_factors.h and the propagation routines of be_kernels.hip), for tests against the definitions.
+ * vio_stage_preint: IntegrationBase(acc0, gyr0, ba, bg) followed by n x propagate (integration_base.h:56-162) through mode 0 = preint_propagate step
+ * by step, 1 = preint_propagate_many(append = false), 2 = preint_propagate_many(append = true), the merge of MARGIN_SECOND_NEW, which also files
+ * the samples (push_back).  dt[n], acc[n][3], gyr[n][3]; the noise densities are cfg's.  out686 = delta_p(3) delta_q(wxyz) delta_v(3) sum_dt
+ * jacobian(225) covariance(225), as vio_stage_imu_factor's preint_out, then the whitening matrix M = chol(cov)^-1 (225, row-major lower triangular,
+ * all zero when the covariance has no Cholesky factor).  n_buf_out (may be NULL) = samples filed: min(n, 64) in mode 2, 0 otherwise; buf_out (may be
+ * NULL; 64 x 7 doubles) = the sample buffer, (dt, acc[3], gyr[3]) per slot, zero where nothing was filed. */
+int vio_stage_preint(const vio_config *cfg, int mode, int n, const double *dt, const double *acc, const double *gyr, const double *acc0,
+                     const double *gyr0, const double *ba, const double *bg, double *out686, int *n_buf_out, double *buf_out);
+/* IntegrationBase::evaluate (integration_base.h:164-195) and the Jacobian blocks of IMUFactor::Evaluate (imu_factor.h:92-201) BEFORE the
+ * multiplication by sqrt_info, on a caller-supplied pre-integration: pre461 as above (the covariance is not read), ba / bg = its linearisation
+ * biases, gravity (0, 0, cfg->g_norm).  r15 = raw residual; J450 = imu_raw_jacobian, 15 x 30 row-major in tangent coordinates, columns pose_i(6)
+ * speedbias_i(9) pose_j(6) speedbias_j(9); Jp465 (in and out) = a 15 x 31 row-major buffer into which four lanes write the four
+ * imu_raw_jacobian_part column groups as the solver does: columns 0 .. 29 are overwritten, column 30 (the residual's) is returned as passed in. */
+int vio_stage_imu_raw(const vio_config *cfg, const double *pre461, const double *ba, const double *bg, const double *pose_i, const double *sb_i,
+                      const double *pose_j, const double *sb_j, double *r15, double *J450, double *Jp465);
+/* eval_projection_pair, the frame-pair form of ProjectionFactor / ProjectionTdFactor::Evaluate, as the solver calls it: cauchy != 0 multiplies the
+ * Jacobian rows by the CauchyLoss(1) weight sqrt(1 / (1 + |r|^2)) and stores it in *wgt (r2 stays unweighted; without cauchy *wgt is returned as
+ * passed in); rs = 20: rows [pose_i(6) pose_j(6) ex(6) td inv_depth], of which ext = 0 writes only columns 0 .. 12 (inverse depth at 12); rs = 14
+ * (ext must be 0): compact rows [pose_i(6) pose_j(6) inv_depth -].  J (in and out, nJ doubles, 2 rs <= nJ <= 4096): the two rows are written at J[0] and
+ * J[rs]; every element the routine does not own -- slot 13 of a compact row, everything from 2 rs on -- is returned as passed in.  The readout
+ * time is cfg->tr.  VIO_EINVAL for any other (rs, ext) and for an nJ outside that range; nothing is written then. */
+int vio_stage_projection_pair(const vio_config *cfg, const double *pose_i, const double *pose_j, const double *ex, double inv_dep, double td,
+                              const double *obs_i, const double *obs_j, int use_td, int cauchy, int rs, int ext, double *r2, double *wgt,
+                              double *J, int nJ);
+/* PoseLocalParameterization::Plus (pose_local_parameterization.cpp:3-20) and the pose delta of MarginalizationFactor::Evaluate
+ * (marginalization_factor.cpp:374-393), one thread per input: plus7[i] = Plus(x7[i], d6[i]); dx6[i] = (x - x0, 2 vec(q0^-1 q), negated unless
+ * the scalar part of q0^-1 q is >= 0) for x = x7[i], x0 = x07[i].  Poses are (x y z qx qy qz qw). */
+int vio_stage_pose_ops(int n, const double *x7, const double *d6, const double *x07, double *plus7, double *dx6);
 /* The dense solve at the bottom of every trust-region step (Ceres DENSE_SCHUR on the reduced camera system, estimator.cpp:1251-1263;
  * Eigen LLT underneath) through the LDS-tile Cholesky of the solve kernels: S [16 nb][16 nb] row-major symmetric positive definite
  * (nb <= 11; 12 <= nb <= 24 or blocks = -7: the streaming factorisation of windows beyond 10 keyframes, tiles in HBM -- usec5 is then

@@ -168,21 +168,13 @@ static void Qright(const Q &q, double M[4][4]) {  // utility.h:56-64
 }
 static M3 br33(const double M[4][4]) { M3 B; for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) B(i, j) = M[1 + i][1 + j]; return B; }
 
-// IMUFactor::Evaluate imu_factor.h:20-205
-void eval_imu(const Integration &pre, const V3 &G, const double *pi, const double *sbi, const double *pj, const double *sbj,
-              double r[15], double *J_pi, double *J_sbi, double *J_pj, double *J_sbj) {
-    V3 Pi(pi[0], pi[1], pi[2]); Q Qi(pi[6], pi[3], pi[4], pi[5]);
-    V3 Vi(sbi[0], sbi[1], sbi[2]), Bai(sbi[3], sbi[4], sbi[5]), Bgi(sbi[6], sbi[7], sbi[8]);
-    V3 Pj(pj[0], pj[1], pj[2]); Q Qj(pj[6], pj[3], pj[4], pj[5]);
-    V3 Vj(sbj[0], sbj[1], sbj[2]), Baj(sbj[3], sbj[4], sbj[5]), Bgj(sbj[6], sbj[7], sbj[8]);
-    double raw[15];
-    pre.evaluate(G, Pi, Qi, Vi, Bai, Bgi, Pj, Qj, Vj, Baj, Bgj, raw);
+// the whitening matrix of IMUFactor::Evaluate (imu_factor.h:66-69); all zero when a factorisation fails
+void imu_sqrt_info(const Integration &pre, double sqrt_info[15][15]) {
     // sqrt_info = LLT(cov^-1).matrixL().transpose()
     Mat C(15, 15);
     for (int i = 0; i < 15; i++) for (int j = 0; j < 15; j++) C(i, j) = 0.5 * (pre.covariance[i][j] + pre.covariance[j][i]);
     Mat Lc = C;
-    double sqrt_info[15][15];
-    std::memset(sqrt_info, 0, sizeof(sqrt_info));
+    std::memset(sqrt_info, 0, 225 * sizeof(double));
     if (chol(Lc)) {
         // cov^-1 = Lc^-T Lc^-1
         Mat Li(15, 15);
@@ -209,6 +201,19 @@ void eval_imu(const Integration &pre, const V3 &G, const double *pi, const doubl
         } else if (chol(Ci))
             for (int i = 0; i < 15; i++) for (int j = i; j < 15; j++) sqrt_info[i][j] = Ci(j, i);  // L^T
     }
+}
+
+// IMUFactor::Evaluate imu_factor.h:20-205
+void eval_imu(const Integration &pre, const V3 &G, const double *pi, const double *sbi, const double *pj, const double *sbj,
+              double r[15], double *J_pi, double *J_sbi, double *J_pj, double *J_sbj) {
+    V3 Pi(pi[0], pi[1], pi[2]); Q Qi(pi[6], pi[3], pi[4], pi[5]);
+    V3 Vi(sbi[0], sbi[1], sbi[2]), Bai(sbi[3], sbi[4], sbi[5]), Bgi(sbi[6], sbi[7], sbi[8]);
+    V3 Pj(pj[0], pj[1], pj[2]); Q Qj(pj[6], pj[3], pj[4], pj[5]);
+    V3 Vj(sbj[0], sbj[1], sbj[2]), Baj(sbj[3], sbj[4], sbj[5]), Bgj(sbj[6], sbj[7], sbj[8]);
+    double raw[15];
+    pre.evaluate(G, Pi, Qi, Vi, Bai, Bgi, Pj, Qj, Vj, Baj, Bgj, raw);
+    double sqrt_info[15][15];
+    imu_sqrt_info(pre, sqrt_info);
     for (int i = 0; i < 15; i++) {
         double s = 0;
         for (int k = 0; k < 15; k++) s += sqrt_info[i][k] * raw[k];
@@ -874,7 +879,13 @@ struct NormalEq {
 };
 }  // namespace
 
-static void pose_dx(const double *x, const double *x0, double *dx) {  // marginalization_factor.cpp:374-393
+void pose_plus(double *x, const double *d) {  // PoseLocalParameterization::Plus
+    x[0] += d[0]; x[1] += d[1]; x[2] += d[2];
+    Q q(x[6], x[3], x[4], x[5]);
+    Q r = normalized(q * deltaQ(V3(d[3], d[4], d[5])));
+    x[3] = r.x; x[4] = r.y; x[5] = r.z; x[6] = r.w;
+}
+void pose_dx(const double *x, const double *x0, double *dx) {  // marginalization_factor.cpp:374-393
     for (int k = 0; k < 3; k++) dx[k] = x[k] - x0[k];
     Q q0(x0[6], x0[3], x0[4], x0[5]), q(x[6], x[3], x[4], x[5]);
     Q d = inverse(q0) * q;
@@ -1137,12 +1148,7 @@ void Estimator::solve() {
     std::vector<double> feat = para_Feature;
     double relo[7], crelo[7];
     std::memcpy(relo, relo_Pose, sizeof(relo));
-    auto plus_pose = [](double *x, const double *d) {  // PoseLocalParameterization::Plus
-        x[0] += d[0]; x[1] += d[1]; x[2] += d[2];
-        Q q(x[6], x[3], x[4], x[5]);
-        Q r = normalized(q * deltaQ(V3(d[3], d[4], d[5])));
-        x[3] = r.x; x[4] = r.y; x[5] = r.z; x[6] = r.w;
-    };
+    auto plus_pose = [](double *x, const double *d) { pose_plus(x, d); };
     if (constrained) {
         // TrustRegionMinimizer::IterationZero on a bounds-constrained program: x <- Plus(x, 0), i.e. every non-constant block goes through its
         // local parameterisation once (the quaternions are re-normalised) and is PROJECTED onto the box (ParameterBlock::Plus) before the

@@ -346,10 +346,46 @@ void ovio_preint_get(void *h, double *out) {
     out[10] = p->sum_dt;
     for (int i = 0; i < 15; i++) for (int j = 0; j < 15; j++) { out[11 + i * 15 + j] = p->jacobian[i][j]; out[11 + 225 + i * 15 + j] = p->covariance[i][j]; }
 }
+// overwrite the integrated state with the 461 values of ovio_preint_get's layout (the linearisation biases and the sample buffers stay): lets a test
+// evaluate the factor on a pre-integration that came from elsewhere
+void ovio_preint_set(void *h, const double *in) {
+    Integration *p = (Integration *)h;
+    p->delta_p = V3(in[0], in[1], in[2]);
+    p->delta_q.w = in[3]; p->delta_q.x = in[4]; p->delta_q.y = in[5]; p->delta_q.z = in[6];
+    p->delta_v = V3(in[7], in[8], in[9]);
+    p->sum_dt = in[10];
+    for (int i = 0; i < 15; i++) for (int j = 0; j < 15; j++) { p->jacobian[i][j] = in[11 + i * 15 + j]; p->covariance[i][j] = in[11 + 225 + i * 15 + j]; }
+}
 // r(15), J: Ji(105) Jsi(135) Jj(105) Jsj(135)
 void ovio_eval_imu(void *h, double g_norm, const double *pi, const double *sbi, const double *pj, const double *sbj, double *r, double *J) {
     eval_imu(*(Integration *)h, V3(0, 0, g_norm), pi, sbi, pj, sbj, r, J ? J : nullptr, J ? J + 105 : nullptr, J ? J + 240 : nullptr,
              J ? J + 345 : nullptr);
+}
+// the same factor before the multiplication by sqrt_info: r(15), J = 15 x 30 row-major in tangent coordinates (pose_i(6) speedbias_i(9) pose_j(6)
+// speedbias_j(9)).  eval_imu under an identity whitening matrix: its covariance is replaced by the identity for the call.
+void ovio_eval_imu_raw(void *h, double g_norm, const double *pi, const double *sbi, const double *pj, const double *sbj, double *r, double *J) {
+    Integration tmp = *(Integration *)h;
+    for (int i = 0; i < 15; i++) for (int j = 0; j < 15; j++) tmp.covariance[i][j] = i == j ? 1.0 : 0.0;
+    double Ji[105], Jsi[135], Jj[105], Jsj[135];
+    eval_imu(tmp, V3(0, 0, g_norm), pi, sbi, pj, sbj, r, Ji, Jsi, Jj, Jsj);
+    for (int i = 0; i < 15; i++) {
+        for (int c = 0; c < 6; c++) { J[i * 30 + c] = Ji[i * 7 + c]; J[i * 30 + 15 + c] = Jj[i * 7 + c]; }
+        for (int c = 0; c < 9; c++) { J[i * 30 + 6 + c] = Jsi[i * 9 + c]; J[i * 30 + 21 + c] = Jsj[i * 9 + c]; }
+    }
+}
+// sqrt_info of the factor as eval_imu forms it, 15 x 15 row-major
+void ovio_imu_sqrt_info(void *h, double *out225) {
+    double S[15][15];
+    imu_sqrt_info(*(Integration *)h, S);
+    for (int i = 0; i < 15; i++) for (int j = 0; j < 15; j++) out225[i * 15 + j] = S[i][j];
+}
+// PoseLocalParameterization::Plus and the prior's pose delta (marginalization_factor.cpp:374-393) on n inputs
+void ovio_pose_ops(int n, const double *x7, const double *d6, const double *x07, double *plus7, double *dx6) {
+    for (int i = 0; i < n; i++) {
+        for (int k = 0; k < 7; k++) plus7[7 * i + k] = x7[7 * i + k];
+        pose_plus(plus7 + 7 * i, d6 + 6 * i);
+        pose_dx(x7 + 7 * i, x07 + 7 * i, dx6 + 6 * i);
+    }
 }
 // symmetric eigen (for tests of the stand-in solver)
 void ovio_sym_eig(int n, const double *A, double *w, double *V) {

@@ -331,7 +331,11 @@ extern int oracle_deviations;   // the mask of the most recently constructed Est
 void eval_projection(const Config &c, const double *pose_i, const double *pose_j, const double *ex, double inv_dep, double td,
                      const Obs &oi, const Obs &oj, bool use_td, double r[2], double *J_i, double *J_j, double *J_ex,
                      double *J_l, double *J_td);
+// PoseLocalParameterization::Plus in place, and the pose delta of MarginalizationFactor::Evaluate (marginalization_factor.cpp:374-393)
+void pose_plus(double *x7, const double *d6);
+void pose_dx(const double *x7, const double *x0_7, double *dx6);
 // IMUFactor::Evaluate factor/imu_factor.h:20-205; Jacobians row-major 15×7, 15×9, 15×7, 15×9
+void imu_sqrt_info(const Integration &pre, double sqrt_info[15][15]);
 void eval_imu(const Integration &pre, const om::V3 &G, const double *pose_i, const double *sb_i, const double *pose_j,
               const double *sb_j, double r[15], double *J_pi, double *J_sbi, double *J_pj, double *J_sbj);
 

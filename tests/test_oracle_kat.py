@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import factor_ref
 import vio_ct
 
 RING = [(0, -3), (1, -3), (2, -2), (3, -1), (3, 0), (3, 1), (2, 2), (1, 3), (0, 3), (-1, 3), (-2, 2), (-3, 1), (-3, 0), (-3, -1), (-2, -2),
@@ -376,20 +377,9 @@ def test_imu_factor_residual_definition_and_jacobians(P, orc):
 
 # ------------------------------------------------------------------ projection factors
 def _proj_def(cfg, pi, pj, ex, inv_dep, td, oi, oj, use_td):
-    """projection_factor.cpp:22-47 / projection_td_factor.cpp:34-62 from the definition."""
-    pts_i, pts_j = oi[:3].copy(), oj[:3].copy()
-    if use_td:
-        pts_i = pts_i - (td - oi[7]) * np.r_[oi[5:7], 0] + 0  # TR / ROW * row - ... with global shutter TR = 0 handled below
-        pts_j = pts_j - (td - oj[7]) * np.r_[oj[5:7], 0]
-        if cfg.tr != 0:
-            pts_i = oi[:3] - (td - oi[7] + cfg.tr / cfg.height * oi[4] - 0 * cfg.tr / 2) * np.r_[oi[5:7], 0]
-            pts_j = oj[:3] - (td - oj[7] + cfg.tr / cfg.height * oj[4] - 0 * cfg.tr / 2) * np.r_[oj[5:7], 0]
-    pc_i = pts_i / inv_dep
-    p_imu_i = qrot(ex[3:], pc_i) + ex[:3]
-    p_w = qrot(pi[3:], p_imu_i) + pi[:3]
-    p_imu_j = qrot(qinv(pj[3:]), p_w - pj[:3])
-    pc_j = qrot(qinv(ex[3:]), p_imu_j - ex[:3])
-    return (cfg.focal_length / 1.5) * (pc_j[:2] / pc_j[2] - pts_j[:2])
+    """projection_factor.cpp:22-47 / projection_td_factor.cpp:34-62 from the definition: the extended-precision reference, which carries the
+    rolling-shutter row term td - cur_td + TR / ROW * (v - ROW / 2)."""
+    return factor_ref.proj_residual(factor_ref.proj_consts(cfg), pi, pj, ex, inv_dep, td, oi, oj, use_td)[0]
 
 
 def _proj_eval(orc, cfg, pi, pj, ex, inv_dep, td, oi, oj, use_td, jac=True):
@@ -402,9 +392,9 @@ def _proj_eval(orc, cfg, pi, pj, ex, inv_dep, td, oi, oj, use_td, jac=True):
 
 @pytest.mark.parametrize("use_td", [0, 1])
 def test_projection_factor_definition_and_jacobians(P, orc, use_td):
-    cfg = P.default_config(tr=0.0)
     rng = np.random.default_rng(40 + use_td)
-    for _ in range(6):
+    for draw in range(12):
+        cfg = P.default_config(tr=0.0 if draw < 6 else 0.02)      # global shutter, then a rolling shutter of 20 ms readout
         pi = _rand_pose(rng, 0.5)
         pj = pose_plus(pi, np.r_[rng.normal(0, 0.1, 3), rng.normal(0, 0.03, 3)])
         ex = np.r_[np.array(cfg.tic[:]), 0.5, -0.5, 0.5, -0.5]

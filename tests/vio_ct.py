@@ -89,6 +89,9 @@ def oracle(path=None):
             "ovio_preint_push": [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],
             "ovio_preint_repropagate": [C.c_void_p, C.c_void_p, C.c_void_p], "ovio_preint_get": [C.c_void_p, C.c_void_p],
             "ovio_eval_imu": [C.c_void_p, C.c_double] + [C.c_void_p] * 6,
+            "ovio_eval_imu_raw": [C.c_void_p, C.c_double] + [C.c_void_p] * 6,
+            "ovio_pose_ops": [C.c_int] + [C.c_void_p] * 5, "ovio_imu_sqrt_info": [C.c_void_p, C.c_void_p],
+            "ovio_preint_set": [C.c_void_p, C.c_void_p],
             "ovio_sym_eig": [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
             "ovio_get_prior": [C.c_void_p] * 5,
             "ovio_marg_finish": [C.c_int, C.c_int] + [C.c_void_p] * 4,

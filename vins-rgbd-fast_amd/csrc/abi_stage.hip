@@ -204,6 +204,113 @@ int vio_stage_imu_block(const vio_config *cfg, int n, const double *dt, const do
     return stage_imu_impl(cfg, n, dt, acc, gyr, acc0, gyr0, ba, bg, pose_i, sb_i, pose_j, sb_j, nullptr, nullptr, nullptr, G961);
 }
 
+// IntegrationBase constructor on the host side of the test harnesses (plain state initialisation)
+static void stage_preint_init(PreInt *hp, const double *acc0, const double *gyr0, const double *ba, const double *bg) {
+    memset(hp, 0, sizeof(PreInt));
+    for (int k = 0; k < 3; k++) { hp->lin_acc[k] = acc0[k]; hp->lin_gyr[k] = gyr0[k]; hp->lin_ba[k] = ba[k]; hp->lin_bg[k] = bg[k]; hp->acc0[k] = acc0[k]; hp->gyr0[k] = gyr0[k]; }
+    hp->dq[0] = 1;
+    for (int i = 0; i < 15; i++) hp->jac[i * 16] = 1;
+    hp->valid = 1;
+}
+
+int vio_stage_preint(const vio_config *cfg, int mode, int n, const double *dt, const double *acc, const double *gyr, const double *acc0,
+                     const double *gyr0, const double *ba, const double *bg, double *out686, int *n_buf_out, double *buf_out) {
+    if (!cfg || mode < 0 || mode > 2 || n < 0 || (n > 0 && (!dt || !acc || !gyr)) || !acc0 || !gyr0 || !ba || !bg || !out686) return VIO_EINVAL;
+    DevBuf<double> dbuf;
+    DevBuf<PreInt> dp;
+    std::vector<PreInt> hpv(1);
+    PreInt *hp = hpv.data();
+    stage_preint_init(hp, acc0, gyr0, ba, bg);
+    const size_t nd = (size_t)n * 7 + 686;
+    std::vector<double> hb(nd, 0.0);
+    for (int i = 0; i < n; i++) { hb[i] = dt[i]; for (int k = 0; k < 3; k++) { hb[n + 3 * i + k] = acc[3 * i + k]; hb[4 * n + 3 * i + k] = gyr[3 * i + k]; } }
+    HIPCHK(dp.alloc(1));
+    HIPCHK(dbuf.alloc(nd));
+    HIPCHK(dp.upload(hp, 1));
+    HIPCHK(dbuf.upload(hb.data(), nd));
+    be_stage_preint_kernel<<<1, 256>>>(*cfg, dp, n, dbuf, dbuf + n, dbuf + 4 * n, mode, dbuf + 7 * n);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dbuf.download(hb.data(), nd));
+    HIPCHK(dp.download(hp, 1));
+    memcpy(out686, &hb[7 * (size_t)n], 686 * sizeof(double));
+    if (n_buf_out) *n_buf_out = hp->n_buf;
+    if (buf_out)
+        for (int q = 0; q < VIO_IMU_SLOT_CAP; q++) {
+            buf_out[7 * q] = hp->dt_buf[q];
+            for (int k = 0; k < 3; k++) { buf_out[7 * q + 1 + k] = hp->acc_buf[q][k]; buf_out[7 * q + 4 + k] = hp->gyr_buf[q][k]; }
+        }
+    return VIO_OK;
+}
+
+int vio_stage_imu_raw(const vio_config *cfg, const double *pre461, const double *ba, const double *bg, const double *pose_i, const double *sb_i,
+                      const double *pose_j, const double *sb_j, double *r15, double *J450, double *Jp465) {
+    if (!cfg || !pre461 || !ba || !bg || !pose_i || !sb_i || !pose_j || !sb_j || !r15 || !J450 || !Jp465) return VIO_EINVAL;
+    DevBuf<double> db;
+    DevBuf<PreInt> dp;
+    std::vector<PreInt> hpv(1);
+    PreInt *hp = hpv.data();
+    const double z3[3] = {0, 0, 0};
+    stage_preint_init(hp, z3, z3, ba, bg);
+    for (int k = 0; k < 3; k++) { hp->dp[k] = pre461[k]; hp->dv[k] = pre461[7 + k]; }
+    for (int k = 0; k < 4; k++) hp->dq[k] = pre461[3 + k];
+    hp->sum_dt = pre461[10];
+    for (int k = 0; k < 225; k++) { hp->jac[k] = pre461[11 + k]; hp->cov[k] = pre461[236 + k]; }
+    double hb[32 + 15 + 450 + 465];
+    memset(hb, 0, sizeof(hb));
+    memcpy(hb, pose_i, 56); memcpy(hb + 7, sb_i, 72); memcpy(hb + 16, pose_j, 56); memcpy(hb + 23, sb_j, 72);
+    memcpy(hb + 32 + 15 + 450, Jp465, 465 * sizeof(double));
+    HIPCHK(dp.alloc(1));
+    HIPCHK(db.alloc(32 + 15 + 450 + 465));
+    HIPCHK(dp.upload(hp, 1));
+    HIPCHK(db.upload(hb, 32 + 15 + 450 + 465));
+    be_stage_imu_raw_kernel<<<1, 64>>>(dp, db, cfg->g_norm, db + 32, db + 47, db + 497);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(db.download(hb, 32 + 15 + 450 + 465));
+    memcpy(r15, hb + 32, 15 * sizeof(double));
+    memcpy(J450, hb + 47, 450 * sizeof(double));
+    memcpy(Jp465, hb + 497, 465 * sizeof(double));
+    return VIO_OK;
+}
+
+int vio_stage_projection_pair(const vio_config *cfg, const double *pose_i, const double *pose_j, const double *ex, double inv_dep, double td,
+                              const double *obs_i, const double *obs_j, int use_td, int cauchy, int rs, int ext, double *r2, double *wgt,
+                              double *J, int nJ) {
+    if (!cfg || !pose_i || !pose_j || !ex || !obs_i || !obs_j || !r2 || !wgt || !J) return VIO_EINVAL;
+    if (!((rs == 20) || (rs == 14 && !ext)) || nJ < 2 * rs || nJ > 4096) return VIO_EINVAL;   // ext writes columns 12 .. 19 of both rows
+    std::vector<double> hb((size_t)41 + 3 + nJ);
+    DevBuf<double> db;
+    memcpy(&hb[0], pose_i, 56); memcpy(&hb[7], pose_j, 56); memcpy(&hb[14], ex, 56);
+    hb[21] = inv_dep; hb[22] = td;
+    memcpy(&hb[23], obs_i, 72); memcpy(&hb[32], obs_j, 72);
+    hb[41] = r2[0]; hb[42] = r2[1]; hb[43] = *wgt;
+    memcpy(&hb[44], J, (size_t)nJ * sizeof(double));
+    HIPCHK(db.alloc(hb.size()));
+    HIPCHK(db.upload(hb.data(), hb.size()));
+    be_stage_projection_pair_kernel<<<1, 64>>>(*cfg, db, use_td, cauchy, rs, ext, db + 41, db + 43, db + 44);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(db.download(hb.data(), hb.size()));
+    r2[0] = hb[41]; r2[1] = hb[42]; *wgt = hb[43];
+    memcpy(J, &hb[44], (size_t)nJ * sizeof(double));
+    return VIO_OK;
+}
+
+int vio_stage_pose_ops(int n, const double *x7, const double *d6, const double *x07, double *plus7, double *dx6) {
+    if (n < 0 || (n > 0 && (!x7 || !d6 || !x07 || !plus7 || !dx6))) return VIO_EINVAL;
+    if (n == 0) return VIO_OK;
+    DevBuf<double> db;
+    const size_t m = (size_t)n;   // x7 d6 x07 plus7 dx6
+    std::vector<double> hb(33 * m, 0.0);
+    memcpy(&hb[0], x7, 7 * m * sizeof(double)); memcpy(&hb[7 * m], d6, 6 * m * sizeof(double)); memcpy(&hb[13 * m], x07, 7 * m * sizeof(double));
+    HIPCHK(db.alloc(33 * m));
+    HIPCHK(db.upload(hb.data(), 33 * m));
+    be_stage_pose_ops_kernel<<<(n + 63) / 64, 64>>>(n, db, db + 7 * m, db + 13 * m, db + 20 * m, db + 27 * m);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(db.download(hb.data(), 33 * m));
+    memcpy(plus7, &hb[20 * m], 7 * m * sizeof(double));
+    memcpy(dx6, &hb[27 * m], 6 * m * sizeof(double));
+    return VIO_OK;
+}
+
 static int stage_projection_impl(const vio_config *cfg, const double *pose_i, const double *pose_j, const double *ex, double inv_dep, double td,
                                  const double *obs_i, const double *obs_j, int use_td, int form, double *r2, double *J46) {
     double hb[41 + 2 + 46];

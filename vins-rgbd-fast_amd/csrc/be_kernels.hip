@@ -3416,3 +3416,69 @@ __global__ __launch_bounds__(64) void be_stage_imu_block_kernel(const PreInt *P,
         }
     }
 }
+
+// The two propagation routines of the pipeline on one sample list, for comparison with each other and with the definition: mode 0 = n calls
+// of preint_propagate (be_dyn_finalize, be_marg's repropagation), 1 = preint_propagate_many(append = false), 2 = the same with append = true
+// (the MARGIN_SECOND_NEW merge: the samples are also filed into P's buffers, n_buf saturating at VIO_IMU_SLOT_CAP).  preint_store refreshes
+// sqrt_info as everywhere.  out686 = delta_p(3) delta_q(wxyz) delta_v(3) sum_dt jacobian(225) covariance(225) sqrt_info(225).
+__global__ __launch_bounds__(256) void be_stage_preint_kernel(vio_config cfg, PreInt *P, int n, const double *dt, const double *acc,
+                                                               const double *gyr, int mode, double *out686) {
+    __shared__ PreWork pw;
+    __shared__ double lds_fv[PREINT_MANY_LDS_DOUBLES];
+    const int t = threadIdx.x;
+    preint_load(*P, pw);
+    if (mode == 0)
+        for (int q = 0; q < n; q++) preint_propagate(*P, pw, cfg, dt[q], ld3(acc + 3 * q), ld3(gyr + 3 * q));
+    else
+        preint_propagate_many(*P, pw, cfg, n, dt, (const double (*)[3])acc, (const double (*)[3])gyr, mode == 2, lds_fv);
+    preint_store(*P, pw);
+    const PreInt &p = *P;
+    if (t == 0) {
+        out686[0] = p.dp[0]; out686[1] = p.dp[1]; out686[2] = p.dp[2];
+        for (int k = 0; k < 4; k++) out686[3 + k] = p.dq[k];
+        out686[7] = p.dv[0]; out686[8] = p.dv[1]; out686[9] = p.dv[2];
+        out686[10] = p.sum_dt;
+    }
+    for (int k = t; k < 225; k += blockDim.x) { out686[11 + k] = p.jac[k]; out686[236 + k] = p.cov[k]; out686[461 + k] = p.sqrt_info[k]; }
+}
+// IntegrationBase::evaluate and the raw (un-whitened) Jacobian of IMUFactor::Evaluate on a caller-supplied pre-integration (P: delta state,
+// jacobian, linearisation biases).  Lane 0: imu_raw_residual and imu_raw_jacobian (r15, J450 = 15 x 30 row-major, columns pose_i(6)
+// speedbias_i(9) pose_j(6) speedbias_j(9)); lanes 1-4: the four imu_raw_jacobian_part calls into a 15 x 31 buffer as be_stage_imu_block_kernel
+// and the solver lay it out (Jp465: column 30, which the parts do not own, keeps the value it came in with).
+__global__ __launch_bounds__(64) void be_stage_imu_raw_kernel(const PreInt *P, const double *par /*pi7 sbi9 pj7 sbj9*/, double g_norm, double *r15,
+                                                               double *J450, double *Jp465) {
+    __shared__ double raw_l[472];
+    const int lane = threadIdx.x;
+    const PreInt &p = *P;
+    v3 G = mk(0, 0, g_norm);
+    for (int q = lane; q < 465; q += 64) raw_l[q] = Jp465[q];
+    __syncthreads();
+    if (lane == 0) {
+        bf::imu_raw_residual(p, G, par, par + 7, par + 16, par + 23, r15);
+        bf::imu_raw_jacobian(p, G, par, par + 7, par + 16, par + 23, J450);
+    } else if (lane <= 4)
+        bf::imu_raw_jacobian_part(p, G, par, par + 7, par + 16, par + 23, lane - 1, raw_l, 31);
+    __syncthreads();
+    for (int q = lane; q < 465; q += 64) Jp465[q] = raw_l[q];
+}
+// eval_projection_pair as the solver calls it, with the caller's cauchy / rs / ext: J is written in place over whatever the caller put there
+// (2 rows of stride rs from J[0]), wgt likewise (only a cauchy call stores it).
+__global__ void be_stage_projection_pair_kernel(vio_config cfg, const double *in /*pi7 pj7 ex7 inv_dep td oi9 oj9*/, int use_td, int cauchy, int rs,
+                                                int ext, double *r2, double *wgt, double *J) {
+    if (threadIdx.x != 0) return;
+    bf::PairGeo g;
+    bf::pair_geo(in, in + 7, in + 14, g);
+    double ricm[9];
+    stm(ricm, q2R(mkq(in[14 + 6], in[14 + 3], in[14 + 4], in[14 + 5])));
+    bf::eval_projection_pair(cfg, g, ricm, in + 14, in[21], in[22], cfg.tr, in + 23, in + 32, use_td != 0, r2, J, cauchy != 0, wgt, rs, ext != 0);
+}
+// PoseLocalParameterization::Plus and the prior's pose delta, one thread per input: plus7[i] = pose_plus(x7[i], d6[i]), dx6[i] = pose_dx(x7[i], x07[i])
+__global__ void be_stage_pose_ops_kernel(int n, const double *x7, const double *d6, const double *x07, double *plus7, double *dx6) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double x[7];
+    for (int k = 0; k < 7; k++) x[k] = x7[7 * i + k];
+    bf::pose_plus(x, d6 + 6 * i);
+    for (int k = 0; k < 7; k++) plus7[7 * i + k] = x[k];
+    bf::pose_dx(x7 + 7 * i, x07 + 7 * i, dx6 + 6 * i);
+}

@@ -86,6 +86,12 @@ __global__ void be_stage_imu_kernel(vio_config cfg, PreInt *P, int n, const doub
                                     const double *par, double g_norm, double *preint_out, double *r15, double *J480);
 __global__ void be_stage_projection_kernel(vio_config cfg, const double *in, int use_td, int form, double *r2, double *J46);
 __global__ void be_stage_imu_block_kernel(const PreInt *P, const double *par, double g_norm, double *G961);
+__global__ void be_stage_preint_kernel(vio_config cfg, PreInt *P, int n, const double *dt, const double *acc, const double *gyr, int mode,
+                                       double *out686);
+__global__ void be_stage_imu_raw_kernel(const PreInt *P, const double *par, double g_norm, double *r15, double *J450, double *Jp465);
+__global__ void be_stage_projection_pair_kernel(vio_config cfg, const double *in, int use_td, int cauchy, int rs, int ext, double *r2, double *wgt,
+                                                double *J);
+__global__ void be_stage_pose_ops_kernel(int n, const double *x7, const double *d6, const double *x07, double *plus7, double *dx6);
 __global__ void imu_scatter_kernel(Batch B, int total, const int *seq_of, const double *t, const double *acc, const double *gyr);
 __global__ void imu_commit_kernel(Batch B, int total, const int *seq_of);
 __global__ void synth_render_kernel(vio_synth_config c, int S, uint64_t seq0, const float *rays, const float *poses, uint8_t *gray, uint16_t *depth);
