@@ -186,6 +186,25 @@ void ovio_tracker_read(void *h, const uint8_t *gray, double t, const double *R, 
 int ovio_tracker_get(void *h, int cap, int *ids, int *cnt, float *cur, float *un, float *vel) {
     return tracker_get(*(Tracker *)h, cap, ids, cnt, cur, un, vel);
 }
+// test hooks (oracle.h Tracker::Trace).  out: 28 header ints = n_lk n_culled n_unstable ransac_ran n_ransac n_mask n_max_cnt publish
+// n_col_band n_row_band n_corner_band max_near cand_in_unstable cand_fish[3] grey_to_add n_cells n_setmask 0 border_hits[8], then 8 ints per deficit cell
+// (cell n_fast nf num_to_add replacements added textureless tied_min), then 4 per setMask candidate in sorted order (x y track_cnt kept).
+// Returns the number of ints of the whole trace; at most cap are written.
+static int tracker_trace(const Tracker &t, int cap, int *out) {
+    const Tracker::Trace &r = t.trace;
+    std::vector<int> v = {r.n_lk, r.n_culled, r.n_unstable, r.ransac_ran, r.n_ransac, r.n_mask, r.n_max_cnt, r.publish, r.n_col_band, r.n_row_band,
+                          r.n_corner_band, r.max_near, r.cand_in_unstable, r.cand_fish[0], r.cand_fish[1], r.cand_fish[2], r.grey_to_add,
+                          (int)r.cells.size(), (int)r.sm.size() / 4, 0};
+    v.insert(v.end(), r.border_hits, r.border_hits + 8);
+    for (auto &c : r.cells) v.insert(v.end(), {c.cell, c.n_fast, c.nf, c.num_to_add, c.replacements, c.added, c.textureless, c.tied_min});
+    v.insert(v.end(), r.sm.begin(), r.sm.end());
+    for (int i = 0; i < (int)v.size() && i < cap; i++) out[i] = v[i];
+    return (int)v.size();
+}
+int ovio_tracker_trace(void *h, int cap, int *out) { return tracker_trace(*(Tracker *)h, cap, out); }
+int ovio_get_tracker_trace(void *h, int cap, int *out) { return tracker_trace(((Pipeline *)h)->tracker, cap, out); }
+void ovio_tracker_set_fast_cap(void *h, int fast_cap) { ((Tracker *)h)->fast_cap = fast_cap; }
+void ovio_set_fast_cap(void *h, int fast_cap) { ((Pipeline *)h)->tracker.fast_cap = fast_cap; }
 int ovio_tracker_grid(void *h, int *rects /*4 per cell*/, int *threshold) {
     Tracker *tr = (Tracker *)h;
     for (size_t i = 0; i < tr->grids_rect.size(); i++) {

@@ -567,6 +567,7 @@ void Tracker::predictPtsInNextFrame(const double R[9]) {  // :595-608
 
 void Tracker::rejectWithF() {  // :441-473
     if (forw_pts.size() < 8) return;
+    trace.ransac_ran = 1;
     std::vector<P2f> un_cur(cur_pts.size()), un_forw(forw_pts.size());
     for (size_t i = 0; i < cur_pts.size(); i++) {
         double x, y;
@@ -593,7 +594,9 @@ void Tracker::setMask() {  // :173-208 (std::sort ties pinned to original order 
     std::vector<P2f> fp;
     std::vector<int> fid, fcnt;
     for (int i : order) {
-        if (maskAt(forw_pts[i]) == 255) {
+        const int kept = maskAt(forw_pts[i]) == 255;
+        trace.sm.insert(trace.sm.end(), {cvRoundf(forw_pts[i].x), cvRoundf(forw_pts[i].y), track_cnt[i], kept});
+        if (kept) {
             fp.push_back(forw_pts[i]);
             fid.push_back(ids[i]);
             fcnt.push_back(track_cnt[i]);
@@ -608,14 +611,30 @@ std::vector<KeyPt> Tracker::gridDetect(int g) {  // :105-171
     const Rect &r = grids_rect[g];
     std::vector<KeyPt> all, kps;
     fast_detect_roi(forw_pyr[0].d.data(), cfg.width, cfg.height, r.x, r.y, r.w, r.h, all);
+    trace.cells.push_back(CellTrace{g, (int)all.size(), 0, 0, 0, 0, 0, 0});
+    CellTrace &ct = trace.cells.back();
+    if (fast_cap > 0 && (int)all.size() > fast_cap) all.resize(fast_cap);   // test hook, off by default
+    for (auto &k : all) {   // trace only
+        const int px = r.x + (int)(k.x + 0.5f), py = r.y + (int)(k.y + 0.5f);
+        if (!fisheye_mask.empty()) { const int v = fisheye_mask[(size_t)py * cfg.width + px]; trace.cand_fish[v == 0 ? 0 : v == 255 ? 2 : 1]++; }
+        bool in_un = false;
+        for (auto &u : unstable_pts) {
+            const int dx = std::abs(px - cvRoundf(u.x)), dy = std::abs(py - cvRoundf(u.y));
+            in_un |= dy <= cfg.min_dist && dx <= circle_hw[dy];
+        }
+        trace.cand_in_unstable += in_un;
+    }
     // KeyPointsFilter::runByPixelsMask on mask(rect)
     for (auto &k : all)
         if (mask[(size_t)(r.y + (int)(k.y + 0.5f)) * cfg.width + r.x + (int)(k.x + 0.5f)] != 0) kps.push_back(k);
+    ct.nf = (int)kps.size();
     if (kps.empty()) {
         grids_texture_status[g] = 0;
+        ct.textureless = 1;
         return {};
     }
     size_t num_to_add = (size_t)(grids_threshold - grids_track_num[g] + 2);
+    ct.num_to_add = (int)num_to_add;
     if (kps.size() <= num_to_add) {
         for (auto &k : kps) { k.x += r.x; k.y += r.y; }
         return kps;
@@ -631,8 +650,13 @@ std::vector<KeyPt> Tracker::gridDetect(int g) {  // :105-171
         } else if (kps[j].response > keep[min_id].response) {
             kps[j].x += r.x; kps[j].y += r.y;
             keep[min_id] = kps[j];
+            ct.replacements++;
+            const size_t replaced = min_id;
             for (size_t k = 0; k < keep.size(); k++)
                 if (keep[k].response < keep[min_id].response) min_id = k;
+            bool earlier_equal = false;
+            for (size_t k = 0; k < replaced; k++) earlier_equal |= keep[k].response == keep[replaced].response;
+            ct.tied_min += min_id == replaced && earlier_equal;
         }
     }
     return keep;
@@ -641,7 +665,9 @@ std::vector<KeyPt> Tracker::gridDetect(int g) {  // :105-171
 void Tracker::addPoints(const std::vector<KeyPt> &kps) {  // :220-233
     for (auto &k : kps) {
         P2f p{k.x, k.y};
+        if (!fisheye_mask.empty()) { const int v = fisheye_mask[(size_t)cvRoundf(p.y) * cfg.width + cvRoundf(p.x)]; trace.grey_to_add += v != 0 && v != 255; }
         if (maskAt(p) == 255) {
+            if (!trace.cells.empty()) trace.cells.back().added++;
             forw_pts.push_back(p);
             ids.push_back(-1);
             track_cnt.push_back(1);
@@ -683,6 +709,9 @@ void Tracker::undistortedPoints() {  // :542-593
 
 void Tracker::readImage(const uint8_t *img, double t, const double R[9], bool publish) {  // :263-439
     cur_time = t;
+    trace = Trace();
+    trace.publish = publish ? 1 : 0;
+    trace.n_lk = (int)cur_pts.size();
     int maxLevel = lk_effective_level(cfg.width, cfg.height, cfg.lk_max_level);
     std::vector<Image> pyr(maxLevel + 1);
     pyr[0].w = cfg.width; pyr[0].h = cfg.height;
@@ -711,6 +740,11 @@ void Tracker::readImage(const uint8_t *img, double t, const double R[9], bool pu
             lk_track(cur_pyr, forw_pyr, cur_pts, forw_pts, status, maxLevel, false);
         }
         for (size_t i = 0; i < forw_pts.size(); i++) {
+            if (status[i]) {   // trace only
+                const int x = cvRoundf(forw_pts[i].x), y = cvRoundf(forw_pts[i].y);
+                const int at[8] = {x == 0, x == 1, x == cfg.width - 2, x == cfg.width - 1, y == 0, y == 1, y == cfg.height - 2, y == cfg.height - 1};
+                for (int k = 0; k < 8; k++) trace.border_hits[k] += at[k];
+            }
             if (!status[i] && inBorder(forw_pts[i])) unstable_pts.push_back(forw_pts[i]);
             else if (status[i] && !inBorder(forw_pts[i])) status[i] = 0;
         }
@@ -721,15 +755,23 @@ void Tracker::readImage(const uint8_t *img, double t, const double R[9], bool pu
         reduceVector(track_cnt, status);
     }
     for (auto &n : track_cnt) n++;
+    trace.n_culled = (int)forw_pts.size();
+    trace.n_unstable = (int)unstable_pts.size();
 
     if (publish) {
         rejectWithF();
+        trace.n_ransac = (int)forw_pts.size();
         setMask();
         int n_max_cnt = cfg.max_cnt - (int)forw_pts.size();
+        trace.n_mask = (int)forw_pts.size();
+        trace.n_max_cnt = n_max_cnt;
         if (n_max_cnt > 0) {
             for (auto &g : grids_track_num) g = 0;
             for (auto &p : forw_pts) {
                 int col = (int)p.x / grid_width, row = (int)p.y / grid_height;
+                trace.n_col_band += col == cfg.grid_cols;
+                trace.n_row_band += row == cfg.grid_rows;
+                trace.n_corner_band += col == cfg.grid_cols && row == cfg.grid_rows;
                 if (col == cfg.grid_cols) --col;
                 if (row == cfg.grid_rows) --row;
                 ++grids_track_num[col + cfg.grid_cols * row];
@@ -741,6 +783,17 @@ void Tracker::readImage(const uint8_t *img, double t, const double R[9], bool pu
             }
             // sequential semantics: cell k detects against the mask after cells <k were added (one legal
             // interleaving of the thread-pool race at feature_tracker.cpp:397-409)
+            for (int g : grids_id) {   // trace only: the mask centres whose disk can reach into the cell's rectangle
+                const Rect &r = grids_rect[g];
+                int near = 0;
+                auto reach = [&](const P2f &p) {
+                    const int x = cvRoundf(p.x), y = cvRoundf(p.y), d = cfg.min_dist;
+                    return x >= r.x - d && x <= r.x + r.w - 1 + d && y >= r.y - d && y <= r.y + r.h - 1 + d;
+                };
+                for (auto &p : forw_pts) near += reach(p);
+                for (auto &p : unstable_pts) near += reach(p);
+                trace.max_near = std::max(trace.max_near, near);
+            }
             for (int g : grids_id) {
                 std::vector<KeyPt> kps = gridDetect(g);
                 addPoints(kps);

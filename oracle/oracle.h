@@ -140,6 +140,33 @@ struct Tracker {
     void predictPtsInNextFrame(const double R[9]);
     void drawCircle(const P2f &pt);
     uint8_t maskAt(const P2f &pt) const;
+
+    // ---- test hooks (tests/tracker_cases.py); neither changes what readImage computes when unused
+    // fast_cap > 0: gridDetect keeps only the first fast_cap FAST survivors of a cell in raster order (what a detector with a fixed
+    // candidate buffer must produce); 0 = off (the reference)
+    int fast_cap = 0;
+    // what the last readImage did, branch by branch.  Always recorded (results unchanged; cost: one pass over a cell's FAST survivors, times the
+    // frame's unstable points)
+    // replacements: slots the top-k scan overwrote; tied_min: those after which no slot is strictly weaker than the new entry although an EARLIER slot is as weak (the rescan stays put: first-minimum would differ)
+    struct CellTrace { int cell, n_fast, nf, num_to_add, replacements, added, textureless, tied_min; };
+    struct Trace {
+        int n_lk = 0;            // points into LK
+        int n_culled = 0;        // points after the status / border cull
+        int n_unstable = 0;      // status 0 and inside the border
+        int ransac_ran = 0;      // rejectWithF had >= 8 points
+        int n_ransac = 0;        // points after rejectWithF (= n into setMask)
+        int n_mask = 0;          // points after setMask
+        int n_max_cnt = 0;       // max_cnt - n_mask
+        int publish = 0;
+        int n_col_band = 0, n_row_band = 0, n_corner_band = 0;   // tracked points with col == grid_cols / row == grid_rows / both before the decrement
+        int max_near = 0;        // most mask centres (setMask survivors + unstable points) within min_dist of a deficit cell's rectangle
+        int cand_in_unstable = 0;   // FAST survivors of the deficit cells inside the disk of an unstable point
+        int cand_fish[3] = {0, 0, 0};   // FAST survivors of the deficit cells on fisheye-mask value 0 / neither / 255
+        int border_hits[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // LK successes whose rounded x is 0, 1, W - 2, W - 1 / rounded y is 0, 1, H - 2, H - 1
+        int grey_to_add = 0;     // candidates handed to addPoints that sit on a fisheye-mask value that is neither 0 nor 255
+        std::vector<CellTrace> cells;         // the deficit cells in order
+        std::vector<int> sm;                  // setMask in sorted order: x, y, track_cnt, kept per candidate
+    } trace;
 };
 
 // ------------------------------------------------------------------------------------ back-end types

@@ -74,6 +74,8 @@ def oracle(path=None):
             "ovio_tracker_read": [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int],
             "ovio_tracker_get": [C.c_void_p, C.c_int] + [C.c_void_p] * 5,
             "ovio_tracker_grid": [C.c_void_p, C.c_void_p, C.c_void_p],
+            "ovio_tracker_trace": [C.c_void_p, C.c_int, C.c_void_p], "ovio_get_tracker_trace": [C.c_void_p, C.c_int, C.c_void_p],
+            "ovio_tracker_set_fast_cap": [C.c_void_p, C.c_int], "ovio_set_fast_cap": [C.c_void_p, C.c_int],
             "ovio_cam_lift": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
             "ovio_cam_project": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
             "ovio_pyr_down": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
@@ -101,6 +103,25 @@ def oracle(path=None):
         assert L.ovio_config_size() == C.sizeof(pkg().Config), "oracle Config and vio_config layouts differ"
         _orc[path] = L
     return _orc[path]
+
+
+TRACE_KEYS = ("n_lk", "n_culled", "n_unstable", "ransac_ran", "n_ransac", "n_mask", "n_max_cnt", "publish", "n_col_band", "n_row_band",
+              "n_corner_band", "max_near", "cand_in_unstable", "cand_fish0", "cand_fish_grey", "cand_fish255", "grey_to_add")
+CELL_KEYS = ("cell", "n_fast", "nf", "num_to_add", "replacements", "added", "textureless", "tied_min")
+
+
+def _tracker_trace(fn, h, cap=16384):
+    """Tracker::Trace of the last readImage (oracle.h): the counters of TRACE_KEYS, cells = one dict of CELL_KEYS per deficit cell in order,
+    setmask = int array [n][4] (x, y, track_cnt, kept) in setMask's sorted order"""
+    out = np.zeros(cap, np.int32)
+    n = fn(h, cap, out.ctypes.data)
+    assert n <= cap, n
+    tr = dict(zip(TRACE_KEYS, (int(x) for x in out[:len(TRACE_KEYS)])))
+    nc, ns = int(out[17]), int(out[18])
+    tr["border_hits"] = [int(x) for x in out[20:28]]
+    tr["cells"] = [dict(zip(CELL_KEYS, (int(x) for x in out[28 + 8 * k:36 + 8 * k]))) for k in range(nc)]
+    tr["setmask"] = out[28 + 8 * nc:28 + 8 * nc + 4 * ns].reshape(ns, 4).copy()
+    return tr
 
 
 class OraclePipeline:
@@ -161,6 +182,13 @@ class OraclePipeline:
     def set_fisheye_mask(self, mask):
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
         self.L.ovio_set_fisheye_mask(self.h, None if m is None else m.ctypes.data)
+
+    def set_fast_cap(self, fast_cap):
+        """test hook: gridDetect keeps the first fast_cap FAST survivors of a cell in raster order (0 = off, the reference)"""
+        self.L.ovio_set_fast_cap(self.h, int(fast_cap))
+
+    def tracker_trace(self):
+        return _tracker_trace(self.L.ovio_get_tracker_trace, self.h)
 
     def latest_odometry(self):
         o = np.zeros(11)
@@ -257,6 +285,12 @@ class OracleTracker:
     def read(self, gray, t, R=None, publish=True):
         R = np.eye(3) if R is None else np.ascontiguousarray(R, np.float64)
         self.L.ovio_tracker_read(self.h, gray.ctypes.data, float(t), R.ctypes.data, 1 if publish else 0)
+
+    def set_fast_cap(self, fast_cap):
+        self.L.ovio_tracker_set_fast_cap(self.h, int(fast_cap))
+
+    def trace(self):
+        return _tracker_trace(self.L.ovio_tracker_trace, self.h)
 
     def tracks(self, cap=2048):
         ids, cnt = np.zeros(cap, np.int32), np.zeros(cap, np.int32)

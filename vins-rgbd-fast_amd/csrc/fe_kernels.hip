@@ -1509,11 +1509,13 @@ __global__ __launch_bounds__(256) void fe_add_kernel(Batch B, int gate) {
                 uint32_t mine = 0xFFFFFFFFu;   // lane k owns slot k
                 if (nf <= K) {
                     nk = nf;
-                    if (nk > 64) {   // more survivors than a wavefront has lanes (never with grids_threshold + 2 <= 64): serial addPoints below
+                    if (nk > 64) {   // more survivors than a wavefront has lanes: K = grids_threshold - tracked + 2 > 64, i.e. max_cnt / ncells > 62 (a 1 x 1 or
+                                     // 1 x 2 grid with max_cnt 150: K = 152 / 77) and 64 < nf <= K.  Serial addPoints below
                         nk = -nf;
                     } else if (lane < nf) mine = filt[lane];
                 } else if (K > 64) {
-                    // never the case for the supported configurations (grids_threshold + 2 <= 64): serial replay of the scan, in place
+                    // few cells for many features (max_cnt / ncells > 62, e.g. max_cnt 150 on a 1 x 1 or 1 x 2 grid) and nf > K: serial replay of
+                    // the scan, in place (tests/tracker_cases.py: serial_topk*, modes, fast_overflow)
                     if (t == 0) {
                         int min_id = 0;
                         for (int j = 0; j < nf; j++) {
