@@ -509,6 +509,9 @@ int vio_stage_ransac(const vio_config *cfg, int n, const float *p1, const float 
 /* InitialEXRotation::solveRelativeR (initial_ex_rotation.cpp:70-147) through the device code of the calibration phase: corres6[n][6] =
  * (x, y, z) of frame l, (x, y, z) of frame r (normalised points, z = 1); R9 = the rotation it returns, row-major (identity for n < 9) */
 int vio_stage_relative_r(int n, const double *corres6, double *R9);
+/* The same call, and what it decided on the way: detail8 = model found (0 / 1), RANSAC inlier count, the four triangulation votes of
+ * (R1, t) (R1, -t) (R2, t) (R2, -t), which of R1 / R2 was returned (1 / 2, 0 without a model), whether the det(R1) = -1 sign change fired */
+int vio_stage_relative_r_detail(int n, const double *corres6, double *R9, int *detail8);
 /* IntegrationBase::push_back x n + IMUFactor::Evaluate (integration_base.h:32-162, imu_factor.h:20-205)
  * out: delta_p(3) delta_q(wxyz) delta_v(3) sum_dt jacobian(225) covariance(225); r(15); J = 15x7,15x9,15x7,15x9 */
 int vio_stage_imu_factor(const vio_config *cfg, int n, const double *dt, const double *acc, const double *gyr,
@@ -526,6 +529,14 @@ int vio_stage_projection_residual(const vio_config *cfg, const double *pose_i, c
 /* cv::solvePnP(SOLVEPNP_ITERATIVE, useExtrinsicGuess) with K = I as FeatureManager::solvePoseByPnP calls it in VO mode
  * (feature_manager.cpp:545-588): obj[n][3], img[n][2] normalised points, rvec3 / tvec3 (Rodrigues vector, translation) in and out */
 int vio_stage_pnp(int n, const double *obj, const double *img, double *rvec3, double *tvec3);
+/* vio_stage_pnp and the path CvLevMarq took: trace4 = outer iterations, lambda escalations, final lambda exponent (base 10), all six
+ * parameters finite (0 / 1).  vio_stage_host_pnp_trace is the host solver of the dynamic initialisation from the same (rvec, tvec) start. */
+int vio_stage_pnp_trace(int n, const double *obj, const double *img, double *rvec3, double *tvec3, int *trace4);
+int vio_stage_host_pnp_trace(int n, const double *obj, const double *img, double *rvec3, double *tvec3, int *trace4);
+/* cv::Rodrigues as the device solvePnP uses it, n items, one thread each.  mode 0: in = r[n][3], out[n][36] = R[9] row-major, then
+ * dR/dr_0, dR/dr_1, dR/dr_2 (9 each).  mode 1: in = R[n][9], out = r[n][3].  vio_stage_host_rodrigues: the host copy, no GPU needed. */
+int vio_stage_rodrigues(int mode, int n, const double *in, double *out);
+int vio_stage_host_rodrigues(int mode, int n, const double *in, double *out);
 /* Host-only building blocks of the dynamic (static_init: 0) initialisation (csrc/dyninit_host.cpp), callable without a GPU:
  * cv::solvePnP(ITERATIVE, useExtrinsicGuess) (R9 / t3 in: guess, out: result; returns 1 = converged), cv::solvePnPRansac(EPNP) as
  * solveRelativeRT_PNP uses it (solve_5pts.cpp:248-294), and relativePose + GlobalSFM::construct over a window (estimator.cpp:884-920,

@@ -781,6 +781,9 @@ void Estimator::initFramePoseByPnP(int frameCnt) {
     // solvePoseByPnP: w_T_cam -> cam_T_w, refine, back
     M3 R_initial = T(RCam);
     V3 P_initial = -1.0 * (R_initial * PCam);
+    pnp_called = 1;
+    pnp_pairs = (int)pts2.size();
+    pnp_start_of(R_initial, P_initial, pnp_start);
     if ((int)pts2.size() < 4) return;
     if (!solve_pnp_iterative(pts3, pts2, R_initial, P_initial)) return;
     RCam = T(R_initial);
@@ -1163,7 +1166,9 @@ void Estimator::solve() {
 
     NormalEq ne, ne2;
     build_normal_eq(*this, pose, sb, ex, tdv, feat, lms, ne, true, relo_on ? relo : nullptr);
+    const int nres0 = last_stats.n_residuals;   // (build_normal_eq counted them: a solve that stops before its first step must still report them)
     last_stats = SolveStats();
+    last_stats.n_residuals = nres0;
     last_stats.initial_cost = ne.cost;
     last_stats.n_landmarks = F; last_stats.n_var_landmarks = Fa;
 
@@ -1936,6 +1941,7 @@ int Estimator::processImage(std::map<int, std::array<double, 7>> &image, const u
             Ps[frame_count] = Ps[p]; Vs[frame_count] = Vs[p]; Rs[frame_count] = Rs[p]; Bas[frame_count] = Bas[p]; Bgs[frame_count] = Bgs[p];
         }
     } else {
+        pnp_called = 0;
         if (!cfg.use_imu) initFramePoseByPnP(frame_count);  // :321-322
         triangulateWithDepth();
         optimization();

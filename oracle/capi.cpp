@@ -96,6 +96,12 @@ void ovio_get_status(void *h, double *out) {
     out[11] = e.last_stats.final_cost; out[12] = e.last_stats.n_landmarks; out[13] = e.last_stats.n_residuals;
     out[14] = e.last_stats.n_var_landmarks; out[15] = e.has_prior;
 }
+// VO mode, the initFramePoseByPnP of the last processed frame: out8 = (called, pairs found, start rvec(3), start tvec(3))
+void ovio_get_pnp_info(void *h, double *out8) {
+    const Estimator &e = ((Pipeline *)h)->est;
+    out8[0] = e.pnp_called; out8[1] = e.pnp_pairs;
+    for (int k = 0; k < 6; k++) out8[2 + k] = e.pnp_start[k];
+}
 // out2 = (candidate steps cut by the inverse-depth upper bound, bounded landmarks that entered solves) since construction
 void ovio_get_bound_stats(void *h, double *out2) {
     const Estimator &e = ((Pipeline *)h)->est;
@@ -478,6 +484,16 @@ int ovio_solve_pnp_iterative(int n, const double *obj, const double *img, double
     t[0] = tv.x; t[1] = tv.y; t[2] = tv.z;
     return ok ? 1 : 0;
 }
+// the same solve from a rotation vector, with CvLevMarq's trace (oracle.h solve_pnp_iterative_trace); returns 1 when n >= 4
+int ovio_solve_pnp_trace(int n, const double *obj, const double *img, double *rvec, double *tvec, int *trace4) {
+    std::vector<V3> o(n);
+    std::vector<std::array<double, 2>> im(n);
+    for (int i = 0; i < n; i++) { o[i] = V3(obj[3 * i], obj[3 * i + 1], obj[3 * i + 2]); im[i] = {img[2 * i], img[2 * i + 1]}; }
+    solve_pnp_iterative_trace(o, im, rvec, tvec, trace4);
+    return n >= 4 ? 1 : 0;
+}
+// cv::Rodrigues and its derivative on n inputs (oracle.h stage_rodrigues)
+void ovio_rodrigues(int mode, int n, const double *in, double *out) { stage_rodrigues(mode, n, in, out); }
 int ovio_solve_pnp_ransac_epnp(int n, const double *obj, const double *img, int max_iters, double thresh, double confidence, double *R,
                                double *t, uint8_t *inliers) {
     std::vector<V3> o(n);

@@ -296,7 +296,8 @@ M3 inv3(const M3 &A) {
 // ---------------------------------------------------------------------------------------------------------------- solvePnP
 // cv::solvePnP(obj, img, K = I, no distortion, rvec, tvec, useExtrinsicGuess = true, SOLVEPNP_ITERATIVE): Levenberg-Marquardt
 // refinement of the guess (R, t: camera_point = R X + t).  Call sites: initial_sfm.cpp:59, estimator.cpp:537.
-bool solve_pnp_iterative(const std::vector<V3> &obj_in, const std::vector<std::array<double, 2>> &img_in, M3 &R, V3 &t) {
+// The refinement itself on param = (rvec, tvec).  trace (may be null): outer iterations, lambda raises, final lambdaLg10, all six finite.
+static bool pnp_refine(const std::vector<V3> &obj_in, const std::vector<std::array<double, 2>> &img_in, double *param, int *trace) {
     const int n = (int)obj_in.size();
     if (n < 4) return false;  // cv::solvePnP asserts npoints >= 4
     std::vector<V3> obj(n);
@@ -305,11 +306,8 @@ bool solve_pnp_iterative(const std::vector<V3> &obj_in, const std::vector<std::a
         obj[i] = V3(f32(obj_in[i].x), f32(obj_in[i].y), f32(obj_in[i].z));
         img[i] = {f32(img_in[i][0]), f32(img_in[i][1])};
     }
-    double param[6], prev[6];
-    {
-        V3 r = R_to_rodrigues(R);
-        param[0] = r.x; param[1] = r.y; param[2] = r.z; param[3] = t.x; param[4] = t.y; param[5] = t.z;
-    }
+    double prev[6];
+    int raises = 0;
     auto project = [&](const double *p, std::vector<double> &err, Mat *J) {
         V3 r(p[0], p[1], p[2]), tt(p[3], p[4], p[5]);
         M3 Rm = rodrigues_to_R(r), dR[3];
@@ -362,22 +360,60 @@ bool solve_pnp_iterative(const std::vector<V3> &obj_in, const std::vector<std::a
             project(param, err, nullptr);
             const double errNorm = nrm(err);
             if (errNorm > prevErrNorm) {
-                if (++lambdaLg10 <= 16) { step(); continue; }
+                if (++lambdaLg10 <= 16) { raises++; step(); continue; }
             }
             lambdaLg10 = std::max(lambdaLg10 - 1, -16);
             double dn = 0, pn = 0;
             for (int i = 0; i < 6; i++) { dn += (param[i] - prev[i]) * (param[i] - prev[i]); pn += prev[i] * prev[i]; }
-            // cvNorm(param, prevParam, CV_RELATIVE_L2) = |param - prev| / |prev|
-            if (++iters >= max_iter || std::sqrt(dn) / std::sqrt(pn) < eps) done = true;
+            // cvNorm(param, prevParam, CV_RELATIVE_L2) = |param - prev| / (|prev| + DBL_EPSILON)
+            if (++iters >= max_iter || std::sqrt(dn) / (std::sqrt(pn) + 2.220446049250313e-16) < eps) done = true;
             prevErrNorm = errNorm;
             break;
         }
         if (done) break;
     }
-    for (int i = 0; i < 6; i++) if (!std::isfinite(param[i])) return false;
+    bool fin = true;
+    for (int i = 0; i < 6; i++) fin = fin && std::isfinite(param[i]);
+    if (trace) { trace[0] = iters; trace[1] = raises; trace[2] = lambdaLg10; trace[3] = fin ? 1 : 0; }
+    return fin;
+}
+void pnp_start_of(const M3 &R, const V3 &t, double *out6) {
+    const V3 r = R_to_rodrigues(R);
+    out6[0] = r.x; out6[1] = r.y; out6[2] = r.z; out6[3] = t.x; out6[4] = t.y; out6[5] = t.z;
+}
+bool solve_pnp_iterative(const std::vector<V3> &obj_in, const std::vector<std::array<double, 2>> &img_in, M3 &R, V3 &t) {
+    const V3 r = R_to_rodrigues(R);
+    double param[6] = {r.x, r.y, r.z, t.x, t.y, t.z};
+    if (!pnp_refine(obj_in, img_in, param, nullptr)) return false;
     R = rodrigues_to_R(V3(param[0], param[1], param[2]));
     t = V3(param[3], param[4], param[5]);
     return true;
+}
+bool solve_pnp_iterative_trace(const std::vector<V3> &obj_in, const std::vector<std::array<double, 2>> &img_in, double *rvec, double *tvec, int *trace) {
+    double param[6] = {rvec[0], rvec[1], rvec[2], tvec[0], tvec[1], tvec[2]};
+    trace[0] = trace[1] = trace[2] = trace[3] = 0;
+    const bool fin = pnp_refine(obj_in, img_in, param, trace);
+    if ((int)obj_in.size() >= 4) for (int k = 0; k < 3; k++) { rvec[k] = param[k]; tvec[k] = param[3 + k]; }
+    return fin;
+}
+// cv::Rodrigues for the tests: mode 0 maps n vectors r[3] to R[9] (row-major) and dR/dr[27] (dR/dr_0, dR/dr_1, dR/dr_2), 36 doubles each;
+// mode 1 maps n matrices R[9] to r[3]
+void stage_rodrigues(int mode, int n, const double *in, double *out) {
+    for (int i = 0; i < n; i++) {
+        if (mode == 0) {
+            const V3 r(in[3 * i], in[3 * i + 1], in[3 * i + 2]);
+            const M3 R = rodrigues_to_R(r);
+            M3 dR[3];
+            rodrigues_jac(r, R, dR);
+            double *o = out + 36 * i;
+            for (int p = 0; p < 3; p++) for (int q = 0; q < 3; q++) { o[3 * p + q] = R(p, q); for (int k = 0; k < 3; k++) o[9 + 9 * k + 3 * p + q] = dR[k](p, q); }
+        } else {
+            M3 R;
+            for (int p = 0; p < 3; p++) for (int q = 0; q < 3; q++) R(p, q) = in[9 * i + 3 * p + q];
+            const V3 r = R_to_rodrigues(R);
+            out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+        }
+    }
 }
 
 // -------------------------------------------------------------------------------------------------------------------- EPnP

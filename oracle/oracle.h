@@ -264,6 +264,9 @@ struct Estimator {
     std::vector<uint8_t> prior_present;  // per block: W poses, sb0, ex, td
     SolveStats last_stats;
     int reboot_count = 0;
+    // the last initFramePoseByPnP (tests): called this frame, pairs found, the start (rvec, tvec) handed to solvePnP
+    int pnp_called = 0, pnp_pairs = 0;
+    double pnp_start[6] = {0, 0, 0, 0, 0, 0};
     // how often a candidate step was cut by the inverse-depth upper bound (estimator.cpp:1282-1297) since construction, and how many
     // bounded landmarks (estimate_flag == 2) entered solves: Ceres would run its projected line search in exactly those steps
     // (DESIGN.md deviation 5); tests/test_oracle_kat.py measures that the canonical workload never gets there
@@ -394,6 +397,12 @@ bool sfm_construct(int frame_num, om::Q *q, om::V3 *T, int l, const om::M3 &rela
 bool sfm_relative_pose(int window_size, const std::vector<SfmFeature> &sfm_f, om::M3 &relative_R, om::V3 &relative_T, int &l);
 // SfM front (restated OpenCV routines, see oracle/initial.cpp): camera_point = R X + t
 bool solve_pnp_iterative(const std::vector<om::V3> &obj, const std::vector<std::array<double, 2>> &img, om::M3 &R, om::V3 &t);
+// the same refinement from (rvec, tvec), which it overwrites even when the result is not finite; trace[4] = outer iterations, lambda raises,
+// final lambdaLg10, all six parameters finite.  Returns that last flag.
+bool solve_pnp_iterative_trace(const std::vector<om::V3> &obj, const std::vector<std::array<double, 2>> &img, double *rvec, double *tvec, int *trace);
+void stage_rodrigues(int mode, int n, const double *in, double *out);
+// the parameter vector solve_pnp_iterative starts from for a guess (R, t): (rvec, tvec)
+void pnp_start_of(const om::M3 &R, const om::V3 &t, double *out6);
 bool solve_pnp_ransac_epnp(const std::vector<om::V3> &obj, const std::vector<std::array<double, 2>> &img, int max_iters, double thresh,
                            double confidence, om::M3 &R, om::V3 &t, std::vector<uint8_t> &inliers);
 

@@ -73,8 +73,8 @@ class CaseScene(X.Scene):
     pixel lattice of the pose at t = 0 (8 px apart, depths 3 .. 9 m, so that no two of them ever share a depth pixel under the small motions
     used here) and 36 `extra` ones on the half-lattice, which only hooks show."""
 
-    def __init__(self, cfg, moves, imu_rate, blend=0.25, amp=0.4, rot=0.05, seed=3):
-        self.cfg, self.ric, self.tic = cfg, X.RIC_TRUE, X.TIC_TRUE
+    def __init__(self, cfg, moves, imu_rate, blend=0.25, amp=0.4, rot=0.05, seed=3, ric=None, tic=None):
+        self.cfg, self.ric, self.tic = cfg, (X.RIC_TRUE if ric is None else ric), (X.TIC_TRUE if tic is None else tic)
         self.moves, self.blend, self.amp, self.rot = [tuple(float(v) for v in m) for m in moves], float(blend), float(amp), float(rot)
         self.imu_rate = float(imu_rate)
         rs = np.random.RandomState(seed)
@@ -451,6 +451,143 @@ def build(name, P):
         _built[name] = CASES[name](P)
         _built[name].frames()
     return _built[name]
+
+
+# ------------------------------------------------------------------------------------------------------------- VO streams
+# use_imu = 0 (no IMU samples pushed), fix_depth = 1 and depth_max = 10 (with free depths and no IMU the scale is a gauge freedom of the window:
+# test_gpu_vo.test_vo_pipeline_matches_oracle), window 4.  Every frame after the initialisation starts from FeatureManager::initFramePoseByPnP.
+def vo_config(P, **kw):
+    cfg = case_config(P, fix_depth=1, depth_max=10.0, **kw)
+    cfg.use_imu = 0
+    return cfg
+
+
+class RingScene(CaseScene):
+    """landmarks on a ring around the rig (160 of them 3 .. 6 m away, heights within the 90 degree field of view: about 40 visible); the body
+    yaws `yaw_deg` per frame about its z axis (the camera pans) with a small translation, from frame `hold` on: over the initialisation window
+    it stands still at the identity, so that the VO world frame is the frame the truth is written in and the first solve, which starts from
+    copies of the first pose, starts at its optimum (a first solve that starts 16 degrees off is decided by round-off: the oracle's own two
+    formulations end 1e-4 m apart on it)."""
+
+    def __init__(self, cfg, stamps, yaw_deg, hold, seed=5):
+        self.cfg, self.ric, self.tic = cfg, X.RIC_TRUE, X.TIC_TRUE
+        self.t0, self.dt, self.yaw, self.hold = float(stamps[0]), float(stamps[1] - stamps[0]), np.radians(yaw_deg), hold
+        self.imu_rate = 100.0
+        rs = np.random.RandomState(seed)
+        n = 160
+        az = 2 * np.pi * (np.arange(n) + rs.uniform(-0.3, 0.3, n)) / n
+        rad = rs.uniform(3.0, 6.0, n)
+        self.L = np.stack([rad * np.cos(az), rad * np.sin(az), rad * rs.uniform(-0.6, 0.6, n)], 1)
+        self.n_base = n
+
+    def pose(self, t):
+        k = max((t - self.t0) / self.dt - self.hold, 0.0)
+        a = self.yaw * k
+        return 0.05 * np.array([np.sin(0.3 * k), 1 - np.cos(0.2 * k), 0.5 * np.sin(0.25 * k)]), X.rodrigues([0.0, 0.0, a])
+
+    def imu(self, t_end):
+        return np.zeros(0), np.zeros((0, 3)), np.zeros((0, 3))
+
+
+def vo_half_turn(P):
+    """the initialisation window at rest, then 56 frames at -4.08 degrees of yaw each (224 degrees; the rate puts the crossing midway between
+    two frames): cfg.ric alone is a 120 degree rotation, and the angle of the solvePnP start rotation
+    (Rs[fc - 1] ric)^T climbs to pi and comes down again with the axis on the other side: the matrix -> vector branch near pi, then a
+    start vector whose hemisphere flipped against the frame before"""
+    cfg = vo_config(P)
+    stamps = _stamps(cfg.window_size + 56, 5.0)
+    st = Stream("vo_half_turn", cfg, RingScene(cfg, stamps, -4.08, cfg.window_size), stamps, about="the solvePnP start rotation passes through pi")
+    return st
+
+
+def vo_few_pairs(P):
+    """all but 5, 4, 3 and 0 landmarks get fresh ids on frames 8, 12, 16 and 20: a landmark that is new in a frame has no depth when
+    initFramePoseByPnP runs, so these are the pair counts there; 3 and 0 are below cv::solvePnP's minimum and the copied pose stays"""
+    cfg, sc, stamps = _moving(P, 24, fix_depth=1, depth_max=10.0)
+    cfg.use_imu = 0
+    plan = {8: 5, 12: 4, 16: 3, 20: 0}
+    st = Stream("vo_few_pairs", cfg, sc, stamps, hooks=[thin_to(n, {k}) for k, n in plan.items()], about="5, 4, 3 and 0 pairs for solvePnP")
+    st.notes["pairs"] = plan
+    return st
+
+
+def vo_depthless(P):
+    """frame 8: every second landmark of the map comes back under a fresh id, and on frames 8 .. 10 its depth pixel is zero: it is in the list
+    without a depth (lm_depth <= 0) and must stay out of the pair list until triangulateWithDepth gives it one from frame 11's pixel"""
+    cfg, sc, stamps = _moving(P, 18, fix_depth=1, depth_max=10.0)
+    cfg.use_imu = 0
+    st = Stream("vo_depthless", cfg, sc, stamps, about="landmarks without a depth stay out of the solvePnP pairs")
+
+    def hook(st, fr):
+        half = fr.lm[1::2]
+        if fr.k == 8:
+            st.renew(half)
+            fr.ids = st.ids_of[fr.lm].copy()
+            st.notes["with_depth"] = len(fr.lm) - len(half)
+        if 8 <= fr.k <= 10:
+            for j in half:
+                fr.depth[fr.pixel(j)] = 0
+    st.hooks.append(hook)
+    st.notes["frames"] = (8, 9, 10)
+    return st
+
+
+def _vo_rest(name, P, identity, about):
+    """identity = False: the rig stands over the initialisation window, moves for four frames and stops; identity = True: ric = I, tic = 0
+    and the rig never moves, so that Rs stays within rounding of I, the matrix -> vector map returns exactly 0 and tvec is 0 within rounding"""
+    cfg = vo_config(P)
+    W = cfg.window_size
+    stamps = _stamps(W + 12, 5.0)
+    ric, tic = (np.eye(3), np.zeros(3)) if identity else (None, None)
+    if identity:
+        for i in range(9):
+            cfg.ric[i] = float(np.eye(3).reshape(-1)[i])
+        for i in range(3):
+            cfg.tic[i] = 0.0
+    moves = [] if identity else [(stamps[W], stamps[W + 4], 1.0)]
+    return Stream(name, cfg, CaseScene(cfg, moves, 100.0, ric=ric, tic=tic), stamps, about=about)
+
+
+def vo_moving_start(P):
+    """the rig moves 0.4 m through the initialisation window and on: the first VO solve starts from copies of the first pose, far from its
+    optimum (cost 403 over 196 residuals), and has to find the window by itself.  Not one of VO_CASES: landmark 48 fails the consistency test of
+    triangulateWithDepth under the copied poses and enters that solve free, with depth -1 and, the poses being identical, no baseline: its
+    first step is a rounding residue divided by the damping, so only the first iteration's poses can be compared"""
+    cfg = vo_config(P)
+    W = cfg.window_size
+    stamps = _stamps(W + 8, 5.0)
+    return Stream("vo_moving_start", cfg, CaseScene(cfg, [(stamps[0] - 0.3, stamps[W + 2], 1.0)], 100.0), stamps,
+                  about="a first VO solve that starts far from its optimum")
+
+
+def vo_standstill(P):
+    return _vo_rest("vo_standstill", P, False, "the rig at rest after the initialisation: solvePnP starts at its optimum")
+
+
+def vo_identity_extrinsic(P):
+    return _vo_rest("vo_identity_extrinsic", P, True, "ric = I, tic = 0, no motion: the first solvePnP start vector is exactly zero")
+
+
+VO_CASES = dict(vo_half_turn=vo_half_turn, vo_few_pairs=vo_few_pairs, vo_depthless=vo_depthless, vo_standstill=vo_standstill,
+                vo_identity_extrinsic=vo_identity_extrinsic)
+
+
+def build_vo(name, P):
+    if name not in _built:
+        _built[name] = VO_CASES[name](P)
+        _built[name].frames()
+    return _built[name]
+
+
+def run_oracle_vo(st):
+    """the oracle over a VO stream (no IMU pushed): per frame dict(rc, status, window, pnp = (called, pairs, start rvec, start tvec))"""
+    import vio_ct
+    o = vio_ct.OraclePipeline(st.cfg)
+    out = []
+    for stamp, ids, obs, depth, _ in st.frames():
+        rc = o.process_obs(ids, obs, oracle_depth(depth), stamp)
+        out.append(dict(rc=rc, status=o.status(), window=o.window().copy(), pnp=o.pnp_info()))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------- drivers

@@ -220,6 +220,13 @@ class OraclePipeline:
                 "n_var_landmarks", "has_prior"]
         return dict(zip(keys, s))
 
+    def pnp_info(self):
+        """VO mode, the initFramePoseByPnP of the last processed frame: (called, pairs, start rvec, start tvec)"""
+        o = np.zeros(8)
+        self.L.ovio_get_pnp_info.argtypes = [C.c_void_p, C.c_void_p]
+        self.L.ovio_get_pnp_info(self.h, o.ctypes.data)
+        return int(o[0]), int(o[1]), o[2:5].copy(), o[5:8].copy()
+
     def window(self):
         w = np.zeros((self.W + 1, 17))
         self.L.ovio_get_window(self.h, w.ctypes.data)

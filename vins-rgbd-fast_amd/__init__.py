@@ -315,6 +315,11 @@ def lib():
         L.vio_device_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.vio_stage_projection_residual.argtypes = L.vio_stage_projection.argtypes
         L.vio_stage_pnp.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vio_stage_pnp_trace.argtypes = [C.c_int] + [C.c_void_p] * 5
+        L.vio_stage_host_pnp_trace.argtypes = [C.c_int] + [C.c_void_p] * 5
+        L.vio_stage_rodrigues.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.vio_stage_host_rodrigues.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.vio_stage_relative_r_detail.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vio_stage_imu_block.argtypes = [C.POINTER(Config), C.c_int] + [C.c_void_p] * 12
         L.vio_stage_chol.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.vio_stage_preint.argtypes = [C.POINTER(Config), C.c_int, C.c_int] + [C.c_void_p] * 10

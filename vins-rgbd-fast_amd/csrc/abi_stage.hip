@@ -135,19 +135,28 @@ int vio_stage_camera(const vio_camera *cam, int n, const double *uv, const doubl
     return VIO_OK;
 }
 
-int vio_stage_relative_r(int n, const double *corres6, double *R9) {
+static int stage_relative_r_impl(int n, const double *corres6, double *R9, int *detail8) {
     if (n < 0 || (n > 0 && !corres6) || !R9) return VIO_EINVAL;
     DevBuf<double> dc, dR;
+    DevBuf<int> dd;
     const size_t lds = (size_t)n * 40 + 64;   // four coordinate arrays + the RANSAC status flags
+    // refused before anything is asked of the runtime: a limit it cannot grant would stay behind as the thread's last error
+    if (!lds_fits((const void *)be_stage_relative_r_kernel, lds, "be_stage_relative_r")) return VIO_ECAPACITY;
     HIPCHK(dc.alloc((size_t)6 * (n + 1)));
     HIPCHK(dR.alloc(9));
     if (n > 0) HIPCHK(dc.upload(corres6, (size_t)6 * n));
     (void)raise_lds_limit((const void *)be_stage_relative_r_kernel, lds);
-    if (!lds_fits((const void *)be_stage_relative_r_kernel, lds, "be_stage_relative_r")) return VIO_ECAPACITY;
-    be_stage_relative_r_kernel<<<1, 256, lds>>>(n, dc, dR);
+    if (detail8) HIPCHK(dd.alloc(8));
+    be_stage_relative_r_kernel<<<1, 256, lds>>>(n, dc, dR, detail8 ? (int *)dd : nullptr);
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(dR.download(R9, 9));
+    if (detail8) HIPCHK(dd.download(detail8, 8));
     return VIO_OK;
+}
+int vio_stage_relative_r(int n, const double *corres6, double *R9) { return stage_relative_r_impl(n, corres6, R9, nullptr); }
+int vio_stage_relative_r_detail(int n, const double *corres6, double *R9, int *detail8) {
+    if (!detail8) return VIO_EINVAL;
+    return stage_relative_r_impl(n, corres6, R9, detail8);
 }
 
 static int stage_imu_impl(const vio_config *cfg, int n, const double *dt, const double *acc, const double *gyr, const double *acc0,
@@ -329,8 +338,8 @@ static int stage_projection_impl(const vio_config *cfg, const double *pose_i, co
 }
 // cv::solvePnP(SOLVEPNP_ITERATIVE, useExtrinsicGuess = 1) with K = I as FeatureManager::solvePoseByPnP calls it (feature_manager.cpp:571):
 // obj[n][3], img[n][2] (both rounded to float like cv::Point3f / Point2f), rvec / tvec in and out
-int vio_stage_pnp(int n, const double *obj, const double *img, double *rvec3, double *tvec3) {
-    if (n < 4) return VIO_EINVAL;
+static int stage_pnp_impl(int n, const double *obj, const double *img, double *rvec3, double *tvec3, int *trace4) {
+    if (n < 4 || !obj || !img || !rvec3 || !tvec3) return VIO_EINVAL;
     std::vector<double> pts((size_t)n * 5), par(6);
     for (int i = 0; i < n; i++) {
         for (int k = 0; k < 3; k++) pts[5 * i + k] = (double)(float)obj[3 * i + k];
@@ -342,10 +351,32 @@ int vio_stage_pnp(int n, const double *obj, const double *img, double *rvec3, do
     HIPCHK(dq.alloc(6));
     HIPCHK(dp.upload(pts.data(), pts.size()));
     HIPCHK(dq.upload(par.data(), 6));
-    be_stage_pnp_kernel<<<1, 256>>>(dp, n, dq);
+    DevBuf<int> dt;
+    if (trace4) HIPCHK(dt.alloc(4));
+    be_stage_pnp_kernel<<<1, 256>>>(dp, n, dq, trace4 ? (int *)dt : nullptr);
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(dq.download(par.data(), 6));
+    if (trace4) HIPCHK(dt.download(trace4, 4));
     for (int k = 0; k < 3; k++) { rvec3[k] = par[k]; tvec3[k] = par[3 + k]; }
+    return VIO_OK;
+}
+int vio_stage_pnp(int n, const double *obj, const double *img, double *rvec3, double *tvec3) { return stage_pnp_impl(n, obj, img, rvec3, tvec3, nullptr); }
+int vio_stage_pnp_trace(int n, const double *obj, const double *img, double *rvec3, double *tvec3, int *trace4) {
+    if (!trace4) return VIO_EINVAL;
+    return stage_pnp_impl(n, obj, img, rvec3, tvec3, trace4);
+}
+// cv::Rodrigues of the device solvePnP, one thread per item: mode 0 in = r[n][3], out[n][36] = R, dR/dr; mode 1 in = R[n][9], out = r[n][3]
+int vio_stage_rodrigues(int mode, int n, const double *in, double *out) {
+    if (mode < 0 || mode > 1 || n < 0 || (n > 0 && (!in || !out))) return VIO_EINVAL;
+    if (n == 0) return VIO_OK;
+    const size_t ni = (size_t)n * (mode == 0 ? 3 : 9), no = (size_t)n * (mode == 0 ? 36 : 3);
+    DevBuf<double> di, dout;
+    HIPCHK(di.alloc(ni));
+    HIPCHK(dout.alloc(no));
+    HIPCHK(di.upload(in, ni));
+    be_stage_rodrigues_kernel<<<(n + 63) / 64, 64>>>(mode, n, di, dout);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dout.download(out, no));
     return VIO_OK;
 }
 

@@ -19,6 +19,7 @@ struct ExShared {
     double Rout[9];
     int cnt[4];                // triangulation votes of (R1, t) (R1, -t) (R2, t) (R2, -t)
     int ok;
+    int win, flip;             // which of R1 / R2 was returned (1 / 2), whether decomposeE changed the sign of E (vio_stage_relative_r_detail)
 };
 
 __device__ __forceinline__ double wave_sum_d(double v) {
@@ -150,7 +151,8 @@ __device__ void ex_relative_r(int n, const double *X1, const double *Y1, const d
                     for (int p = 0; p < 3; p++) S.t[p] = U[2][p];
                     const double *R1 = S.Rc[0];
                     const double d1 = R1[0] * (R1[4] * R1[8] - R1[5] * R1[7]) - R1[1] * (R1[3] * R1[8] - R1[5] * R1[6]) + R1[2] * (R1[3] * R1[7] - R1[4] * R1[6]);
-                    if (d1 + 1.0 < 1e-09) {
+                    S.flip = d1 + 1.0 < 1e-09;
+                    if (S.flip) {
                         for (int k = 0; k < 9; k++) { S.Rc[0][k] = -S.Rc[0][k]; S.Rc[1][k] = -S.Rc[1][k]; }
                         for (int p = 0; p < 3; p++) S.t[p] = -S.t[p];
                     }
@@ -196,6 +198,7 @@ __device__ void ex_relative_r(int n, const double *X1, const double *Y1, const d
     if (t == 0) {
         const int r1 = max(S.cnt[0], S.cnt[1]), r2 = max(S.cnt[2], S.cnt[3]);
         const double *ans = S.Rc[r1 > r2 ? 0 : 1];   // ratio1 > ratio2 ? R1 : R2 (a tie takes R2)
+        S.win = r1 > r2 ? 1 : 2;
         for (int p = 0; p < 3; p++) for (int q = 0; q < 3; q++) S.Rout[q * 3 + p] = ans[p * 3 + q];   // ans_R_eigen(j, i) = ans_R_cv(i, j)
     }
     __syncthreads();

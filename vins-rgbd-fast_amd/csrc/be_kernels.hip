@@ -296,9 +296,20 @@ __device__ v3 pnp_rodrigues_inv(const m3 &R) {
     }
     return scl(th / (2 * sn), r);
 }
+// dR / dr_i (i = 0 .. 2) at r, Rm = pnp_rodrigues(r)
+__device__ void pnp_rodrigues_jac(v3 r, const m3 &Rm, m3 dR[3]) {
+    const double th2 = dot(r, r);
+    for (int i = 0; i < 3; i++) {
+        const v3 e = mk(i == 0, i == 1, i == 2);
+        if (th2 < 1e-24) { dR[i] = skew(e); continue; }
+        const v3 w = cross(r, mul(sub(eye(), Rm), e));
+        dR[i] = scl(1.0 / th2, mul(add(scl(get(r, i), skew(r)), skew(w)), Rm));
+    }
+}
 // The Levenberg-Marquardt core of cv::solvePnP(ITERATIVE): refines par[6] = (rvec, tvec) in LDS over n pairs pts[5 n] = (X, Y, Z, u, v).
-// prev: 6 doubles of LDS, sw: >= (waves x 28) doubles of LDS.  Every thread of the block takes part.
-__device__ void pnp_refine_block(const double *pts, int n, double *sh_par, double *sh_prev, double *sw) {
+// prev: 6 doubles of LDS, sw: >= (waves x 28) doubles of LDS.  Every thread of the block takes part.  trace (may be null, written by thread
+// 0): outer iterations, lambda escalations, final lambda_lg10.
+__device__ void pnp_refine_block(const double *pts, int n, double *sh_par, double *sh_prev, double *sw, int *trace = nullptr) {
     const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6, nw = nt >> 6;
     // reduction of NV values per thread: wave DPP sums, then a fixed-order sum over the waves
     auto reduce = [&](double *v, int NV) {
@@ -313,15 +324,7 @@ __device__ void pnp_refine_block(const double *pts, int n, double *sh_par, doubl
         const v3 r = mk(sh_par[0], sh_par[1], sh_par[2]), tt = mk(sh_par[3], sh_par[4], sh_par[5]);
         const m3 Rm = pnp_rodrigues(r);
         m3 dR[3];
-        if (jac) {
-            const double th2 = dot(r, r);
-            for (int i = 0; i < 3; i++) {
-                const v3 e = mk(i == 0, i == 1, i == 2);
-                if (th2 < 1e-24) { dR[i] = skew(e); continue; }
-                const v3 w = cross(r, mul(sub(eye(), Rm), e));
-                dR[i] = scl(1.0 / th2, mul(add(scl(get(r, i), skew(r)), skew(w)), Rm));
-            }
-        }
+        if (jac) pnp_rodrigues_jac(r, Rm, dR);
         double v[28];
         for (int q = 0; q < 28; q++) v[q] = 0;
         for (int i = t; i < n; i += nt) {
@@ -348,7 +351,7 @@ __device__ void pnp_refine_block(const double *pts, int n, double *sh_par, doubl
         return sqrt(v[27]);
     };
     double acc[27];
-    int lambda_lg10 = -3, iters = 0;
+    int lambda_lg10 = -3, iters = 0, raises = 0;
     double prev_err = 0;
     auto take_step = [&]() {   // thread 0: param = prev - pinv(JtJ with damped diagonal) JtErr
         if (t == 0) {
@@ -382,16 +385,18 @@ __device__ void pnp_refine_block(const double *pts, int n, double *sh_par, doubl
         bool done = false;
         for (;;) {
             const double e = project(false, acc);
-            if (e > prev_err && ++lambda_lg10 <= 16) { take_step(); continue; }
+            if (e > prev_err && ++lambda_lg10 <= 16) { raises++; take_step(); continue; }
             lambda_lg10 = max(lambda_lg10 - 1, -16);
             double dn = 0, pn = 0;
             for (int i = 0; i < 6; i++) { dn += (sh_par[i] - sh_prev[i]) * (sh_par[i] - sh_prev[i]); pn += sh_prev[i] * sh_prev[i]; }
-            if (++iters >= 20 || sqrt(dn) / sqrt(pn) < 1.1920928955078125e-07) done = true;
+            // cvNorm(param, prevParam, CV_RELATIVE_L2) = |param - prev| / (|prev| + DBL_EPSILON)
+            if (++iters >= 20 || sqrt(dn) / (sqrt(pn) + 2.220446049250313e-16) < 1.1920928955078125e-07) done = true;
             prev_err = e;
             break;
         }
         if (done) break;
     }
+    if (trace && t == 0) { trace[0] = iters; trace[1] = raises; trace[2] = lambda_lg10; }
     __syncthreads();
 }
 
@@ -3297,13 +3302,34 @@ __global__ __launch_bounds__(256) void be_dyn_finalize_kernel(Batch B, int seq, 
     triangulate_with_depth(c, be.n_lm);
 }
 
-// stage test of the device solvePnP: par6 = (rvec, tvec) in / out
-__global__ __launch_bounds__(256) void be_stage_pnp_kernel(const double *pts, int n, double *par6) {
+// stage test of the device solvePnP: par6 = (rvec, tvec) in / out; trace4 (may be null) = outer iterations, lambda escalations, final
+// lambda_lg10, all six parameters finite
+__global__ __launch_bounds__(256) void be_stage_pnp_kernel(const double *pts, int n, double *par6, int *trace4) {
     __shared__ double sh_par[6], sh_prev[6], sw[256];
     if (threadIdx.x < 6) sh_par[threadIdx.x] = par6[threadIdx.x];
     __syncthreads();
-    pnp_refine_block(pts, n, sh_par, sh_prev, sw);
+    pnp_refine_block(pts, n, sh_par, sh_prev, sw, trace4);
     if (threadIdx.x < 6) par6[threadIdx.x] = sh_par[threadIdx.x];
+    if (trace4 && threadIdx.x == 0) {
+        bool fin = true;
+        for (int i = 0; i < 6; i++) fin = fin && isfinite(sh_par[i]);
+        trace4[3] = fin ? 1 : 0;
+    }
+}
+// cv::Rodrigues as the solve uses it, one thread per item (vio_stage_rodrigues): mode 0 r[3] -> R[9], dR/dr[27]; mode 1 R[9] -> r[3]
+__global__ void be_stage_rodrigues_kernel(int mode, int n, const double *in, double *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (mode == 0) {
+        const v3 r = ld3(in + 3 * (size_t)i);
+        const m3 Rm = pnp_rodrigues(r);
+        m3 dR[3];
+        pnp_rodrigues_jac(r, Rm, dR);
+        double *o = out + 36 * (size_t)i;
+        stm(o, Rm);
+        for (int k = 0; k < 3; k++) stm(o + 9 + 9 * k, dR[k]);
+    } else
+        st3(out + 3 * (size_t)i, pnp_rodrigues_inv(ldm(in + 9 * (size_t)i)));
 }
 
 #include "be_phased.h"
@@ -3372,7 +3398,7 @@ __global__ void be_stage_projection_kernel(vio_config cfg, const double *in /*pi
 // G961: the 31 x 31 Gram matrix, row-major, columns = pose_i(6) speedbias_i(9) pose_j(6) speedbias_j(9) | r.
 // InitialEXRotation::solveRelativeR on one set of correspondences (vio_stage_relative_r): corres6[n][6] = (x, y, z) in frame l, (x, y, z) in
 // frame r; grid 1, 256 threads, dynamic LDS 40 n + 64 bytes.  The same device code as the calibration phase of be_ingest<true>.
-__global__ __launch_bounds__(256) void be_stage_relative_r_kernel(int n, const double *corres6, double *R9) {
+__global__ __launch_bounds__(256) void be_stage_relative_r_kernel(int n, const double *corres6, double *R9, int *detail8) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_rr[];
     __shared__ ExShared S;
     double *X1 = (double *)smem_rr, *Y1 = X1 + n, *X2 = Y1 + n, *Y2 = X2 + n;
@@ -3384,6 +3410,14 @@ __global__ __launch_bounds__(256) void be_stage_relative_r_kernel(int n, const d
     __syncthreads();
     ex_relative_r(n, X1, Y1, X2, Y2, st, S);
     if (threadIdx.x < 9) R9[threadIdx.x] = S.Rout[threadIdx.x];
+    if (detail8 && threadIdx.x == 0) {   // (S.R.maxGood and the votes are defined only when the RANSAC ran / a model was found)
+        const bool ran = n >= 9, ok = ran && S.ok;
+        detail8[0] = ok ? 1 : 0;
+        detail8[1] = ran ? S.R.maxGood : 0;
+        for (int k = 0; k < 4; k++) detail8[2 + k] = ok ? S.cnt[k] : 0;
+        detail8[6] = ok ? S.win : 0;
+        detail8[7] = ok ? S.flip : 0;
+    }
 }
 
 __global__ __launch_bounds__(64) void be_stage_imu_block_kernel(const PreInt *P, const double *par /*pi7 sbi9 pj7 sbj9*/, double g_norm, double *G961) {

@@ -993,7 +993,8 @@ bool linear_alignment(const std::vector<ImageFrame> &f, v3 tic, double g_norm, v
 
 // cv::solvePnP(SOLVEPNP_ITERATIVE, useExtrinsicGuess = true), K = I (call sites: initial_sfm.cpp:59, estimator.cpp:537,
 // feature_manager.cpp:571)
-bool solve_pnp_iterative(const std::vector<v3> &obj_in, const std::vector<std::array<double, 2>> &img_in, m3 &R, v3 &t) {
+// the refinement on param = (rvec, tvec); trace (may be null): outer iterations, lambda raises, final lambda_lg10, all six finite
+static bool pnp_refine(const std::vector<v3> &obj_in, const std::vector<std::array<double, 2>> &img_in, double *param, int *trace) {
     const int n = (int)obj_in.size();
     if (n < 4) return false;
     std::vector<v3> obj(n);
@@ -1002,11 +1003,8 @@ bool solve_pnp_iterative(const std::vector<v3> &obj_in, const std::vector<std::a
         obj[i] = mk(as_float(obj_in[i].x), as_float(obj_in[i].y), as_float(obj_in[i].z));
         img[i] = {as_float(img_in[i][0]), as_float(img_in[i][1])};
     }
-    double param[6], prev[6];
-    {
-        const v3 r = rodrigues_inv(R);
-        param[0] = r.x; param[1] = r.y; param[2] = r.z; param[3] = t.x; param[4] = t.y; param[5] = t.z;
-    }
+    double prev[6];
+    int raises = 0;
     std::vector<double> err(2 * n);
     Dense J(2 * n, 6), JtJ(6, 6);
     std::vector<double> JtErr(6);
@@ -1055,20 +1053,51 @@ bool solve_pnp_iterative(const std::vector<v3> &obj_in, const std::vector<std::a
         for (;;) {
             project(param, false);
             const double e = norm2();
-            if (e > prev_err && ++lambda_lg10 <= 16) { take_step(); continue; }
+            if (e > prev_err && ++lambda_lg10 <= 16) { raises++; take_step(); continue; }
             lambda_lg10 = std::max(lambda_lg10 - 1, -16);
             double dn = 0, pn = 0;
             for (int i = 0; i < 6; i++) { dn += (param[i] - prev[i]) * (param[i] - prev[i]); pn += prev[i] * prev[i]; }
-            if (++iters >= 20 || sqrt(dn) / sqrt(pn) < 1.1920928955078125e-07) done = true;
+            // cvNorm(param, prevParam, CV_RELATIVE_L2) = |param - prev| / (|prev| + DBL_EPSILON)
+            if (++iters >= 20 || sqrt(dn) / (sqrt(pn) + 2.220446049250313e-16) < 1.1920928955078125e-07) done = true;
             prev_err = e;
             break;
         }
         if (done) break;
     }
-    for (int i = 0; i < 6; i++) if (!std::isfinite(param[i])) return false;
+    bool fin = true;
+    for (int i = 0; i < 6; i++) fin = fin && std::isfinite(param[i]);
+    if (trace) { trace[0] = iters; trace[1] = raises; trace[2] = lambda_lg10; trace[3] = fin ? 1 : 0; }
+    return fin;
+}
+bool solve_pnp_iterative(const std::vector<v3> &obj_in, const std::vector<std::array<double, 2>> &img_in, m3 &R, v3 &t) {
+    const v3 r = rodrigues_inv(R);
+    double param[6] = {r.x, r.y, r.z, t.x, t.y, t.z};
+    if (!pnp_refine(obj_in, img_in, param, nullptr)) return false;
     R = rodrigues(mk(param[0], param[1], param[2]));
     t = mk(param[3], param[4], param[5]);
     return true;
+}
+// the same solve from (rvec, tvec), overwritten even when the result is not finite, with the trace; returns the finite flag
+bool solve_pnp_iterative_trace(const std::vector<v3> &obj_in, const std::vector<std::array<double, 2>> &img_in, double *rvec, double *tvec, int *trace) {
+    double param[6] = {rvec[0], rvec[1], rvec[2], tvec[0], tvec[1], tvec[2]};
+    trace[0] = trace[1] = trace[2] = trace[3] = 0;
+    const bool fin = pnp_refine(obj_in, img_in, param, trace);
+    if ((int)obj_in.size() >= 4) for (int k = 0; k < 3; k++) { rvec[k] = param[k]; tvec[k] = param[3 + k]; }
+    return fin;
+}
+// cv::Rodrigues for the tests (vio_stage_host_rodrigues)
+void stage_rodrigues(int mode, int n, const double *in, double *out) {
+    for (int i = 0; i < n; i++) {
+        if (mode == 0) {
+            const v3 r = ld3(in + 3 * i);
+            const m3 R = rodrigues(r);
+            m3 dR[3];
+            rodrigues_derivative(r, R, dR);
+            stm(out + 36 * i, R);
+            for (int k = 0; k < 3; k++) stm(out + 36 * i + 9 + 9 * k, dR[k]);
+        } else
+            st3(out + 3 * i, rodrigues_inv(ldm(in + 9 * i)));
+    }
 }
 
 void run(const vio_config &cfg, int W, const double *headers, const double *bgs0, const double *ric9, const double *tic3,
@@ -1254,6 +1283,19 @@ int vio_stage_host_pnp(int n, const double *obj, const double *img, double *R9, 
     const bool ok = vinit::solve_pnp_iterative(o, im, R, t);
     dm::stm(R9, R); dm::st3(t3, t);
     return ok ? 1 : 0;
+}
+int vio_stage_host_pnp_trace(int n, const double *obj, const double *img, double *rvec3, double *tvec3, int *trace4) {
+    if (n < 4 || !obj || !img || !rvec3 || !tvec3 || !trace4) return VIO_EINVAL;
+    std::vector<dm::v3> o(n);
+    std::vector<std::array<double, 2>> im(n);
+    for (int i = 0; i < n; i++) { o[i] = dm::mk(obj[3 * i], obj[3 * i + 1], obj[3 * i + 2]); im[i] = {img[2 * i], img[2 * i + 1]}; }
+    vinit::solve_pnp_iterative_trace(o, im, rvec3, tvec3, trace4);
+    return VIO_OK;
+}
+int vio_stage_host_rodrigues(int mode, int n, const double *in, double *out) {
+    if (mode < 0 || mode > 1 || n < 0 || (n > 0 && (!in || !out))) return VIO_EINVAL;
+    vinit::stage_rodrigues(mode, n, in, out);
+    return VIO_OK;
 }
 int vio_stage_host_pnp_ransac(int n, const double *obj, const double *img, int max_iters, double thresh, double confidence, double *R9, double *t3) {
     if (n < 1 || !obj || !img || !R9 || !t3) return -1;

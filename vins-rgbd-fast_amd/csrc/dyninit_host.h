@@ -58,6 +58,11 @@ void run(const vio_config &cfg, int W, const double *headers, const double *bgs0
 // cv::solvePnP(ITERATIVE, useExtrinsicGuess) on normalised points: camera_point = R X + t.  Exposed for Estimator's VO mode
 // (FeatureManager::initFramePoseByPnP, feature_manager.cpp:590-642) and for tests.
 bool solve_pnp_iterative(const std::vector<dm::v3> &obj, const std::vector<std::array<double, 2>> &img, dm::m3 &R, dm::v3 &t);
+// the same solve from (rvec, tvec), overwritten even when the result is not finite; trace[4] = outer iterations, lambda raises, final
+// lambda_lg10, all six parameters finite (returned as well)
+bool solve_pnp_iterative_trace(const std::vector<dm::v3> &obj, const std::vector<std::array<double, 2>> &img, double *rvec, double *tvec, int *trace);
+// cv::Rodrigues on n inputs: mode 0 r[3] -> R[9], dR/dr[27]; mode 1 R[9] -> r[3]
+void stage_rodrigues(int mode, int n, const double *in, double *out);
 
 // cv::solvePnPRansac (EPnP minimal solver, refit on the inliers) on normalised points with the inlier mask: camera_point = R X + t
 bool pnp_ransac_with_inliers(const std::vector<dm::v3> &obj, const std::vector<std::array<double, 2>> &img, int max_iters, double thresh, double confidence,

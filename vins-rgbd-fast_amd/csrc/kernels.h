@@ -54,7 +54,7 @@ struct IngestSrc {
     int cap;
 };
 template <bool EXCALIB> __global__ void be_ingest_kernel(Batch B, const uint16_t *depth_base, size_t depth_stride, IngestSrc src);
-__global__ void be_stage_relative_r_kernel(int n, const double *corres6, double *R9);
+__global__ void be_stage_relative_r_kernel(int n, const double *corres6, double *R9, int *detail8);
 __global__ void be_solve_kernel(Batch B);
 __global__ void be_solve_kernel_512(Batch B);
 __global__ void be_marg_kernel(Batch B);
@@ -80,7 +80,8 @@ static inline size_t ps_evalf_lds_bytes(int W) {
 }
 __global__ void be_prior_factor_kernel(Batch B, int seq);
 __global__ void be_set_relo_kernel(Batch B, int seq, const double *par);
-__global__ void be_stage_pnp_kernel(const double *pts, int n, double *par6);
+__global__ void be_stage_pnp_kernel(const double *pts, int n, double *par6, int *trace4);
+__global__ void be_stage_rodrigues_kernel(int mode, int n, const double *in, double *out);
 __global__ void be_dyn_finalize_kernel(Batch B, int seq, const double *samples, const int *offs);
 __global__ void be_stage_imu_kernel(vio_config cfg, PreInt *P, int n, const double *dt, const double *acc, const double *gyr,
                                     const double *par, double g_norm, double *preint_out, double *r15, double *J480);

@@ -187,13 +187,14 @@ inline int raise_lds_limit(const void *fn, size_t bytes) {
     (void)hipGetDevice(&dev);
     std::lock_guard<std::mutex> lk(mu);
     for (auto &e : seen)
-        if (e.fn == fn && e.dev == dev) {
-            if (bytes <= e.bytes) return 0;
-            e.bytes = bytes;
-            return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : -1;
-        }
+        if (e.fn == fn && e.dev == dev && bytes <= e.bytes) return 0;
+    // a size the runtime refuses is not remembered, and its error is taken off the thread: the callers decide with lds_fits, and an
+    // error left behind would be reported by the next entry point that ends with hipGetLastError()
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    for (auto &e : seen)
+        if (e.fn == fn && e.dev == dev) { e.bytes = bytes; return 0; }
     seen.push_back({fn, dev, bytes});
-    return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : -1;
+    return 0;
 }
 
 // static + dynamic LDS of a kernel this handle will launch against what a workgroup may own: a configuration that does not fit fails at
