@@ -570,6 +570,15 @@ int vio_stage_imu_block(const vio_config *cfg, int n, const double *dt, const do
  * NULL; 64 x 7 doubles) = the sample buffer, (dt, acc[3], gyr[3]) per slot, zero where nothing was filed. */
 int vio_stage_preint(const vio_config *cfg, int mode, int n, const double *dt, const double *acc, const double *gyr, const double *acc0,
                      const double *gyr0, const double *ba, const double *bg, double *out686, int *n_buf_out, double *buf_out);
+/* vio_stage_preint_ring: beside modes 0 - 2, what the per-frame integration of be_ingest adds to preint_propagate_many(append = true): the samples
+ * come from a ring of `cap` entries (t[cap] stamps, acc[cap][3], gyr[cap][3]; sample q of the n >= 1 lies at index (head + q) % cap) with dt formed
+ * on the device -- t[first] - prev_time, stamp differences, cur_time - t[last but one] for the last of n >= 2 -- and Estimator::processIMU's
+ * world-state step (estimator.cpp:142-152) runs beside the delta-state recursion.  world31, in: acc_0(3) gyr_0(3) Ps(3) Vs(3) Rs(9 row-major)
+ * Bas(3) Bgs(3) g(3); out: acc_0, gyr_0, Ps, Vs, Rs after the n samples, and [30] = be_ingest's overflow bits (2 when more samples than a
+ * slot's buffer holds were filed).  The other arguments as vio_stage_preint's. */
+int vio_stage_preint_ring(const vio_config *cfg, int n, int head, int cap, const double *t, const double *acc, const double *gyr, double prev_time,
+                          double cur_time, double *world31, const double *acc0, const double *gyr0, const double *ba, const double *bg,
+                          double *out686, int *n_buf_out, double *buf_out);
 /* IntegrationBase::evaluate (integration_base.h:164-195) and the Jacobian blocks of IMUFactor::Evaluate (imu_factor.h:92-201) BEFORE the
  * multiplication by sqrt_info, on a caller-supplied pre-integration: pre461 as above (the covariance is not read), ba / bg = its linearisation
  * biases, gravity (0, 0, cfg->g_norm).  r15 = raw residual; J450 = imu_raw_jacobian, 15 x 30 row-major in tangent coordinates, columns pose_i(6)

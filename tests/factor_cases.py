@@ -122,6 +122,35 @@ def imu_cases():
     return out
 
 
+RING_COUNTS = (1, 2, 7, 8, 9, 16, 17, 63, 64, 65)   # the PI_CH edges, and the slot buffer one short, full and one over
+RING_CAP = 80
+
+
+@functools.lru_cache(maxsize=None)
+def ring_case(n):
+    """The first n samples of the n65 draw as be_ingest meets them (vio_stage_preint_ring): in a ring of RING_CAP entries read from the
+    unwrapped position head = 2 RING_CAP - 1, so that sample 0 lies in the last entry and the others from entry 0 on (head + n exceeds the
+    capacity for every n); the entries outside the interval are NaN.  Stamps at irregular intervals near an epoch time, prevTime before the
+    first stamp, curTime strictly between the last two (n = 1 has only prevTime to go by).  `dt` is what numpy forms from the same stamps by
+    the same float64 subtractions.  The world state is a draw of its own; its biases are the case's."""
+    c = imu_cases()["n%d" % (SLOT_CAP + 1)]
+    rng = np.random.default_rng(4242)
+    t = 1403636580.0 + np.cumsum(0.005 * (1 + 0.2 * rng.uniform(-1, 1, SLOT_CAP + 1)))[:n]
+    prev = t[0] - 0.0031
+    cur = t[n - 2] + 0.4 * (t[n - 1] - t[n - 2]) if n >= 2 else t[0] - 0.001
+    dt = np.r_[t[0] - prev, t[1:] - t[:-1]]
+    if n >= 2:
+        dt[n - 1] = cur - t[n - 2]
+    head = 2 * RING_CAP - 1
+    idx = (head + np.arange(n)) % RING_CAP
+    rt, ra, rg = np.full(RING_CAP, np.nan), np.full((RING_CAP, 3), np.nan), np.full((RING_CAP, 3), np.nan)
+    rt[idx], ra[idx], rg[idx] = t, c["acc"][:n], c["gyr"][:n]
+    q = rand_pose(rng)[3:]
+    R = np.array([[float(x) for x in r] for r in fr.q2R((q[3], q[0], q[1], q[2]))])
+    return dict(c, n=n, dt=dt, acc=np.ascontiguousarray(c["acc"][:n]), gyr=np.ascontiguousarray(c["gyr"][:n]), name="ring%d" % n, head=head, prev=prev,
+                cur=cur, ring_t=rt, ring_acc=ra, ring_gyr=rg, Ps=rng.normal(0, 2.0, 3), Vs=rng.normal(0, 0.5, 3), Rs=R, g=np.array([0.0, 0.0, G_NORM]))
+
+
 @functools.lru_cache(maxsize=None)
 def imu_preint_ref(name):
     """The reference pre-integration of a case, computed once per process."""

@@ -277,6 +277,38 @@ def preint(dt, acc, gyr, acc0, gyr0, ba, bg, noise, longdouble=False):
                 source="longdouble" if longdouble else "mpmath", ba=np.asarray(ba, np.float64), bg=np.asarray(bg, np.float64))
 
 
+def process_imu(dt, acc, gyr, acc0, gyr0, P, R, V, ba, bg, g):
+    """Estimator::processIMU's world-state recursion over n samples (estimator.cpp:142-152): R <- R toRotationMatrix(deltaQ(un_gyr dt)) with the
+    un-normalised deltaQ, midpoint acceleration in the world frame less g.  R is 3 x 3.  Returns float64 P(3), R(3 x 3), V(3) and scale_p /
+    scale_v / scale_r, the largest term that entered a sum of P / V / an entry of R (or the sum itself, if larger)."""
+    num = _num("mp")
+    dt, acc, gyr = np.asarray(dt, np.float64), np.asarray(acc, np.float64).reshape(-1, 3), np.asarray(gyr, np.float64).reshape(-1, 3)
+    a0, g0, Ba, Bg, G = _vec(num, acc0), _vec(num, gyr0), _vec(num, ba), _vec(num, bg), _vec(num, g)
+    P, V = _vec(num, P), _vec(num, V)
+    R = [[num(x) for x in r] for r in np.asarray(R, np.float64).reshape(3, 3)]
+    sp = sv = sr = 0.0
+    with mpmath.workdps(DPS):
+        for k in range(len(dt)):
+            h, a1, g1 = num(dt[k]), _vec(num, acc[k]), _vec(num, gyr[k])
+            un_acc_0 = sub(mv(R, sub(a0, Ba)), G)
+            un_gyr = sub(scl(0.5, add(g0, g1)), Bg)
+            D = q2R(delta_q(scl(h, un_gyr)))
+            sr = max([sr] + [abs(float(R[i][m] * D[m][j])) for i in range(3) for j in range(3) for m in range(3)])
+            R = mm(R, D)
+            un_acc_1 = sub(mv(R, sub(a1, Ba)), G)
+            un_acc = scl(0.5, add(un_acc_0, un_acc_1))
+            inc_p, inc_v = scl(0.5 * h * h, un_acc), scl(h, un_acc)
+            terms_p, terms_v = P + scl(h, V) + inc_p, V + inc_v
+            P = add(add(P, scl(h, V)), inc_p)
+            V = add(V, inc_v)
+            sp = max([sp] + [abs(float(x)) for x in terms_p + P])
+            sv = max([sv] + [abs(float(x)) for x in terms_v + V])
+            a0, g0 = a1, g1
+    tiny = np.finfo(float).tiny
+    return dict(P=np.array([float(x) for x in P]), R=np.array([[float(x) for x in r] for r in R]), V=np.array([float(x) for x in V]),
+                scale_p=max(sp, tiny), scale_v=max(sv, tiny), scale_r=max(sr, tiny))
+
+
 def pre_from_461(o461, ba, bg):
     """The same dict from the 461 doubles the stage entries and the oracle return."""
     o = np.asarray(o461, np.float64)

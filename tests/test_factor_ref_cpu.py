@@ -126,6 +126,28 @@ def test_reference_preintegration_closed_forms():
     assert abs(2 * np.arctan2(r["dq"][3], r["dq"][0]) - 0.5 * T) < n * (0.5 * dt) ** 3 / 12 * 1.01
 
 
+def test_reference_world_state_closed_form():
+    """process_imu at constant acceleration and zero rotation: deltaQ(0) is the identity, so R stays as given bit for bit, the world acceleration
+    A = R (a - Ba) - g is constant, and the midpoint recursion sums to V0 + A T and P0 + V0 T + A T^2 / 2 for any partition of T into steps."""
+    rng = np.random.default_rng(3)
+    n = 37
+    dt = rng.uniform(1e-3, 2e-2, n)
+    a, Ba, g = np.array([0.3, -0.2, 9.7]), np.array([0.02, -0.01, 0.03]), np.array([0.0, 0.0, 9.805])
+    P0, V0, z3 = np.array([1.5, -2.0, 0.7]), np.array([0.4, 0.1, -0.3]), np.zeros(3)
+    q = fc.axis_angle([0.3, -0.5, 0.8], 40.0)
+    R0 = np.array([[float(x) for x in r] for r in fr.q2R((q[3], q[0], q[1], q[2]))])
+    r = fr.process_imu(dt, np.tile(a, (n, 1)), np.zeros((n, 3)), a, z3, P0, R0, V0, Ba, z3, g)
+    assert np.array_equal(r["R"], R0)
+    with mpmath.workdps(40):
+        m = lambda v: [mpmath.mpf(float(x)) for x in v]
+        T = sum(m(dt))
+        A = fr.sub(fr.mv([m(row) for row in R0], fr.sub(m(a), m(Ba))), m(g))
+        V = [v0 + x * T for v0, x in zip(m(V0), A)]
+        Pm = [p0 + v0 * T + x * T * T / 2 for p0, v0, x in zip(m(P0), m(V0), A)]
+        assert np.array_equal(r["V"], [float(x) for x in V]) and np.array_equal(r["P"], [float(x) for x in Pm])
+    assert r["scale_p"] >= np.abs(r["P"]).max() and r["scale_v"] >= np.abs(r["V"]).max() and r["scale_r"] >= np.abs(R0).max() * 0.999
+
+
 def test_reference_zero_baseline_and_round_trip():
     c = fc.proj_cases()["zero_baseline"]
     for use_td in (0, 1):

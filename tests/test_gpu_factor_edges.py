@@ -126,6 +126,59 @@ def test_preintegration_both_routines_against_the_reference(P, orc, name):
         assert fc.same_but_dq(o0[:461], short[:461])
 
 
+# ------------------------------------------------------------------------------------------------ what be_ingest adds: the ring and the world state
+# Ps / Rs / Vs after the n samples against factor_ref.process_imu, in units of eps x the largest term that entered the quantity.  The oracle's
+# processIMU is a member of its estimator and cannot be driven on a state of the test's choosing, so the bars are ten times what was measured
+# on an MI355X, rounded up to one digit (the rule of test_gpu_backend_edges.BARS); a measured 0 stands for itself.
+WORLD_BARS = {          # n: (P, R, V)
+    1:  (0, 6, 0),      # measured P 0     R 0.591 V 0
+    2:  (7, 6, 0),      # measured P 0.635 R 0.589 V 0
+    7:  (20, 20, 7),    # measured P 1.27  R 1.18  V 0.674
+    8:  (20, 20, 10),   # measured P 1.27  R 1.18  V 0.972
+    9:  (20, 20, 20),   # measured P 1.9   R 1.76  V 1.25
+    16: (30, 20, 20),   # measured P 2.54  R 1.76  V 1.2
+    17: (20, 20, 20),   # measured P 1.9   R 1.76  V 1.16
+    63: (50, 30, 20),   # measured P 4.44  R 2.92  V 1.87
+    64: (60, 30, 30),   # measured P 5.08  R 2.92  V 2.23
+    65: (40, 50, 30),   # measured P 3.81  R 4.09  V 2.2
+}
+
+
+def dev_ring(P, n):
+    c = fc.ring_case(n)
+    cfg = P.default_config(**c["cfg_kw"])
+    out, nb, buf = np.full(686, np.nan), C.c_int(-1), np.full((64, 7), np.nan)
+    world = np.r_[c["acc0"], c["gyr0"], c["Ps"], c["Vs"], c["Rs"].ravel(), c["ba"], c["bg"], c["g"], np.nan]
+    rc = P.lib().vio_stage_preint_ring(C.byref(cfg), n, c["head"], fc.RING_CAP, _p(c["ring_t"]), _p(c["ring_acc"]), _p(c["ring_gyr"]), c["prev"], c["cur"],
+                                       _p(world), _p(c["acc0"]), _p(c["gyr0"]), _p(c["ba"]), _p(c["bg"]), _p(out), C.addressof(nb), _p(buf))
+    assert rc == 0
+    return out, nb.value, buf, world
+
+
+@pytest.mark.parametrize("n", fc.RING_COUNTS)
+def test_ingest_propagation_on_a_ring_with_the_world_state(P, n):
+    """be_ingest's use of preint_propagate_many -- the interval of a wrapping ring as the sample source, dt formed on the device, the world-state
+    step of processIMU as the side job -- returns the bits of the merge's use (mode 2) fed numpy's dt, files the same buffer, raises overflow
+    bit 2 exactly when more than 64 samples were filed, and moves Ps / Rs / Vs as estimator.cpp:142-152 does."""
+    c = fc.ring_case(n)
+    ts = np.sort(c["ring_t"][np.isfinite(c["ring_t"])])
+    assert c["head"] + n > fc.RING_CAP and len(ts) == n and c["prev"] < ts[0] and (n < 2 or ts[-2] < c["cur"] < ts[-1])
+    out, nb, buf, world = dev_ring(P, n)
+    o2, nb2, buf2 = dev_preint(P, c["name"], 2, c)
+    assert np.isfinite(out).all() and out.tobytes() == o2.tobytes(), np.abs(out - o2).max()
+    assert nb == nb2 == min(n, fc.SLOT_CAP) and buf.tobytes() == buf2.tobytes()
+    assert np.array_equal(buf[:nb], np.c_[c["dt"], c["acc"], c["gyr"]][:nb]) and not buf[nb:].any()
+    assert world[30] == (2.0 if n > fc.SLOT_CAP else 0.0)
+    assert np.array_equal(world[0:3], c["acc"][n - 1]) and np.array_equal(world[3:6], c["gyr"][n - 1])
+    assert np.array_equal(world[21:30], np.r_[c["ba"], c["bg"], c["g"]])
+    ref = fr.process_imu(c["dt"], c["acc"], c["gyr"], c["acc0"], c["gyr0"], c["Ps"], c["Rs"], c["Vs"], c["ba"], c["bg"], c["g"])
+    e = (np.abs(world[6:9] - ref["P"]).max() / (fr.EPS * ref["scale_p"]), np.abs(world[12:21].reshape(3, 3) - ref["R"]).max() / (fr.EPS * ref["scale_r"]),
+         np.abs(world[9:12] - ref["V"]).max() / (fr.EPS * ref["scale_v"]))
+    _log("world", c["name"], P=e[0], R=e[1], V=e[2])
+    bP, bR, bV = WORLD_BARS[n]
+    assert e[0] <= bP and e[1] <= bR and e[2] <= bV, (e, WORLD_BARS[n])
+
+
 # ------------------------------------------------------------------------------------------------ raw residual and Jacobian
 @pytest.mark.parametrize("name", IMU)
 def test_raw_imu_residual_and_jacobian(P, orc, name):

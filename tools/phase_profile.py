@@ -30,7 +30,7 @@ NAMES = {0: "vector2double", 1: "lm indexing", 2: "pair lists", 4: "evaluate(fir
          45: "  eval b0: X to LDS", 40: "  eval b0: prior dx", 44: "  eval b0: A dx partials", 46: "  eval b1: X + headers to LDS",
          100: "setup: init extras + vector2double", 101: "setup: landmark indexing (2 scans)", 102: "setup: relo + residual list", 103: "setup: pair counts",
          104: "setup: pair lists", 106: "ingest: hash + matching", 107: "ingest: new landmarks", 108: "ingest: parallax", 109: "ingest: IMU pre-integration",
-         110: "ingest: triangulate", 111: "  imu: interval + load", 112: "  imu: stage + state recursions", 113: "  imu: F / V of the samples", 114: "  imu: J / P recursion",
+         110: "ingest: triangulate", 111: "  imu: interval + load", 112: "  imu: pipelined propagation + world state",
          # front-end (fe_kernels.hip FE_PH markers)
          64: "select load + status cull", 65: "select lift (F input)", 66: "  ransac 7-point hypotheses", 67: "  ransac inlier counts", 68: "  ransac serial best/iters",
          69: "  ransac final inliers", 70: "select F compaction", 71: "select rank sort", 72: "select greedy setMask", 73: "select counts + stores",

@@ -323,6 +323,7 @@ def lib():
         L.vio_stage_imu_block.argtypes = [C.POINTER(Config), C.c_int] + [C.c_void_p] * 12
         L.vio_stage_chol.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.vio_stage_preint.argtypes = [C.POINTER(Config), C.c_int, C.c_int] + [C.c_void_p] * 10
+        L.vio_stage_preint_ring.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_double, C.c_double] + [C.c_void_p] * 8
         L.vio_stage_imu_raw.argtypes = [C.POINTER(Config)] + [C.c_void_p] * 10
         L.vio_stage_projection_pair.argtypes = [C.POINTER(Config)] + [C.c_void_p] * 3 + [C.c_double, C.c_double, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]

@@ -222,26 +222,31 @@ static void stage_preint_init(PreInt *hp, const double *acc0, const double *gyr0
     hp->valid = 1;
 }
 
-int vio_stage_preint(const vio_config *cfg, int mode, int n, const double *dt, const double *acc, const double *gyr, const double *acc0,
-                     const double *gyr0, const double *ba, const double *bg, double *out686, int *n_buf_out, double *buf_out) {
-    if (!cfg || mode < 0 || mode > 2 || n < 0 || (n > 0 && (!dt || !acc || !gyr)) || !acc0 || !gyr0 || !ba || !bg || !out686) return VIO_EINVAL;
+// world31 != NULL (vio_stage_preint_ring): dt / acc / gyr are a ring of na entries, n samples from `head` on; world31 in and out
+static int stage_preint_impl(const vio_config *cfg, int mode, int n, int na, const double *dt, const double *acc, const double *gyr, int head,
+                             double prev_time, double cur_time, double *world31, const double *acc0, const double *gyr0, const double *ba,
+                             const double *bg, double *out686, int *n_buf_out, double *buf_out) {
+    if (!cfg || n < 0 || (na > 0 && (!dt || !acc || !gyr)) || !acc0 || !gyr0 || !ba || !bg || !out686) return VIO_EINVAL;
     DevBuf<double> dbuf;
     DevBuf<PreInt> dp;
     std::vector<PreInt> hpv(1);
     PreInt *hp = hpv.data();
     stage_preint_init(hp, acc0, gyr0, ba, bg);
-    const size_t nd = (size_t)n * 7 + 686;
+    const size_t nd = (size_t)na * 7 + 686 + 31;
     std::vector<double> hb(nd, 0.0);
-    for (int i = 0; i < n; i++) { hb[i] = dt[i]; for (int k = 0; k < 3; k++) { hb[n + 3 * i + k] = acc[3 * i + k]; hb[4 * n + 3 * i + k] = gyr[3 * i + k]; } }
+    for (int i = 0; i < na; i++) { hb[i] = dt[i]; for (int k = 0; k < 3; k++) { hb[na + 3 * i + k] = acc[3 * i + k]; hb[4 * na + 3 * i + k] = gyr[3 * i + k]; } }
+    if (world31) memcpy(&hb[7 * (size_t)na + 686], world31, 31 * sizeof(double));
     HIPCHK(dp.alloc(1));
     HIPCHK(dbuf.alloc(nd));
     HIPCHK(dp.upload(hp, 1));
     HIPCHK(dbuf.upload(hb.data(), nd));
-    be_stage_preint_kernel<<<1, 256>>>(*cfg, dp, n, dbuf, dbuf + n, dbuf + 4 * n, mode, dbuf + 7 * n);
+    if (world31) be_stage_preint_ring_kernel<<<1, 256>>>(*cfg, dp, PreintRing{dbuf, dbuf + na, dbuf + 4 * na, head, na, prev_time, cur_time, n}, dbuf + 7 * na + 686, dbuf + 7 * na);
+    else be_stage_preint_kernel<<<1, 256>>>(*cfg, dp, n, dbuf, dbuf + na, dbuf + 4 * na, mode, dbuf + 7 * na);
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(dbuf.download(hb.data(), nd));
     HIPCHK(dp.download(hp, 1));
-    memcpy(out686, &hb[7 * (size_t)n], 686 * sizeof(double));
+    memcpy(out686, &hb[7 * (size_t)na], 686 * sizeof(double));
+    if (world31) memcpy(world31, &hb[7 * (size_t)na + 686], 31 * sizeof(double));
     if (n_buf_out) *n_buf_out = hp->n_buf;
     if (buf_out)
         for (int q = 0; q < VIO_IMU_SLOT_CAP; q++) {
@@ -249,6 +254,17 @@ int vio_stage_preint(const vio_config *cfg, int mode, int n, const double *dt, c
             for (int k = 0; k < 3; k++) { buf_out[7 * q + 1 + k] = hp->acc_buf[q][k]; buf_out[7 * q + 4 + k] = hp->gyr_buf[q][k]; }
         }
     return VIO_OK;
+}
+int vio_stage_preint(const vio_config *cfg, int mode, int n, const double *dt, const double *acc, const double *gyr, const double *acc0,
+                     const double *gyr0, const double *ba, const double *bg, double *out686, int *n_buf_out, double *buf_out) {
+    if (mode < 0 || mode > 2) return VIO_EINVAL;
+    return stage_preint_impl(cfg, mode, n, n, dt, acc, gyr, 0, 0, 0, nullptr, acc0, gyr0, ba, bg, out686, n_buf_out, buf_out);
+}
+int vio_stage_preint_ring(const vio_config *cfg, int n, int head, int cap, const double *t, const double *acc, const double *gyr, double prev_time,
+                          double cur_time, double *world31, const double *acc0, const double *gyr0, const double *ba, const double *bg,
+                          double *out686, int *n_buf_out, double *buf_out) {
+    if (n < 1 || head < 0 || cap < 1 || !world31) return VIO_EINVAL;
+    return stage_preint_impl(cfg, 2, n, cap, t, acc, gyr, head, prev_time, cur_time, world31, acc0, gyr0, ba, bg, out686, n_buf_out, buf_out);
 }
 
 int vio_stage_imu_raw(const vio_config *cfg, const double *pre461, const double *ba, const double *bg, const double *pose_i, const double *sb_i,

@@ -83,8 +83,9 @@ DM_HD PreintStep preint_midpoint(const PreInt &p, double dt, v3 acc_1, v3 gyr_1,
     return o;
 }
 
-// The two halves of preint_midpoint for the pipelined propagation of be_ingest (same expressions, hence the same bits): the state
-// recursion (serial, a few dozen operations per sample) and the F / V matrices of a step, which depend only on the state BEFORE it.
+// The two halves of preint_midpoint for the pipelined propagation (be_kernels.hip preint_propagate_many; same expressions, hence the same
+// bits): the state recursion (serial, a few dozen operations per sample) and the F / V matrices of a step, which depend only on the
+// state BEFORE it.  preint_step_FV writes the non-zero blocks; zero = false: the caller hands it cleared matrices.
 struct PreintPre { quat dq; v3 acc0, gyr0; };   // what a step's F / V need besides (dt, acc_1, gyr_1) and the linearisation biases
 DM_HD void preint_state_step(quat &delta_q, v3 &delta_p, v3 &delta_v, v3 acc_0, v3 gyr_0, v3 lba, v3 lbg, double dt, v3 acc_1, v3 gyr_1) {
     v3 un_acc_0 = qrot(delta_q, sub(acc_0, lba));
@@ -96,12 +97,12 @@ DM_HD void preint_state_step(quat &delta_q, v3 &delta_p, v3 &delta_v, v3 acc_0, 
     delta_v = add(delta_v, scl(dt, un_acc));
     delta_q = qnormalized(rq);
 }
-DM_HD void preint_step_FV(const PreintPre &s, v3 lba, v3 lbg, double dt, v3 acc_1, v3 gyr_1, double *F, double *V, const bool zero = true) {
+DM_HD void preint_step_FV(const PreintPre &s, v3 lba, v3 lbg, double dt, v3 acc_1, v3 gyr_1, double *F, double *V, const bool zero) {
     const quat delta_q = s.dq;
     const v3 acc_0 = s.acc0, gyr_0 = s.gyr0;
     v3 un_gyr = sub(scl(0.5, add(gyr_0, gyr_1)), lbg);
     quat rq = qmul(delta_q, mkq(1, un_gyr.x * dt / 2, un_gyr.y * dt / 2, un_gyr.z * dt / 2));
-    if (zero) {   // (be_ingest clears the matrices with all its threads beforehand: 495 stores of one lane otherwise)
+    if (zero) {
         for (int i = 0; i < 225; i++) F[i] = 0;
         for (int i = 0; i < 270; i++) V[i] = 0;
     }
@@ -319,6 +320,31 @@ DM_HD void imu_raw_jacobian_part(const PreInt &p, v3 G, const double *pi, const 
         put33(J, ld, O_BA, 24, eye());
         put33(J, ld, O_BG, 27, eye());
     }
+}
+
+// The "interval longer than 10 s" rule, stated once.  The two sides disagree at exactly 10.0 on purpose, as the reference does: the
+// solver keeps that factor and the marginalisation drops it.  A NaN sum_dt fails both comparisons: the solver keeps the factor, the
+// marginalisation drops it.
+DM_HD bool imu_solver_skips(const PreInt &p) { return p.sum_dt > 10.0; }   // estimator.cpp:1231 (optimization)
+DM_HD bool imu_marg_uses(const PreInt &p) { return p.sum_dt < 10.0; }      // estimator.cpp:1404 (MARGIN_OLD)
+
+// One work item of an IMU factor in the solvers' evaluation: part 0 = the whitened residual (column 30 of the 15 x 31 buffer `out`)
+// and its cost, parts 1-4 = the raw Jacobian column groups (whitened at assembly).  skip: the factor is not part of this solve; its
+// residual column is cleared so that the assembly adds nothing.
+DM_HD void imu_work_item(const PreInt &p, bool skip, v3 G, const double *pi, const double *sbi, const double *pj, const double *sbj, int part,
+                         bool withJ, double *out, double &cost) {
+    if (skip) { if (part == 0) for (int k = 0; k < 15; k++) out[k * 31 + 30] = 0; return; }
+    if (part == 0) {
+        double raw[15];
+        imu_raw_residual(p, G, pi, sbi, pj, sbj, raw);
+        for (int r = 0; r < 15; r++) {
+            double sacc = 0;
+            for (int k = 0; k <= r; k++) sacc += p.sqrt_info[r * 15 + k] * raw[k];
+            out[r * 31 + 30] = sacc;
+            cost += 0.5 * sacc * sacc;
+        }
+    } else if (withJ)
+        imu_raw_jacobian_part(p, G, pi, sbi, pj, sbj, part - 1, out, 31);
 }
 
 // ProjectionFactor / ProjectionTdFactor::Evaluate. obs = 9 doubles (x y z u v vx vy cur_td depth).

@@ -98,7 +98,7 @@ namespace {
 // ------------------------------------------------------------------ IntegrationBase::propagate, block-cooperative
 // LDS workspace: sJ sP sFJ sFP (225 each) sF (225) sV (270)
 struct PreWork { double J[225], Pm[225], FJ[225], FP[225], F[225], V[270]; };
-// PI_CH (kernels.h): samples per chunk of the pipelined propagation in be_ingest (F / V of a chunk live in LDS: 8 x 495 doubles)
+// PI_CH (kernels.h): samples per chunk of the pipelined propagation (F / V of a chunk live in LDS: 8 x 495 doubles)
 __device__ __forceinline__ void preint_load(const PreInt &p, PreWork &w) {
     for (int i = threadIdx.x; i < 225; i += blockDim.x) { w.J[i] = p.jac[i]; w.Pm[i] = p.cov[i]; }
     __syncthreads();
@@ -138,11 +138,33 @@ __device__ __forceinline__ void preint_store(PreInt &p, PreWork &w) {
     if (t < 225) p.sqrt_info[t] = w.FP[t];
     __syncthreads();
 }
-// one propagate(dt, acc, gyr) on the LDS-resident jacobian/covariance; p's small state is updated by thread 0
-// N: the noise densities (acc_n, gyr_n, acc_w, gyr_w): the sequence's vio_calibration, or the vio_config of a stage harness
-template <class N> __device__ void preint_propagate(PreInt &p, PreWork &w, const N &c, double dt, v3 acc1, v3 gyr1) {
+// one step of the jacobian / covariance recursion on the LDS-resident matrices, all threads: J <- F J, P <- F P F^T + V Q V^T
+// (integration_base.h:131-132).  N: the noise densities (acc_n, gyr_n, acc_w, gyr_w): the sequence's vio_calibration, or the vio_config
+// of a stage harness
+template <class N> __device__ __forceinline__ void preint_cov_step(PreWork &w, const double *Fk, const double *Vk, const N &c) {
     const int t = threadIdx.x;
-    if (t == 0) {
+    if (t < 225) {
+        int i = t / 15, j = t - i * 15;
+        double s1 = 0, s2 = 0;
+        for (int u = 0; u < 15; u++) { s1 += Fk[i * 15 + u] * w.J[u * 15 + j]; s2 += Fk[i * 15 + u] * w.Pm[u * 15 + j]; }
+        w.FJ[t] = s1; w.FP[t] = s2;
+    }
+    __syncthreads();
+    if (t < 225) {
+        int i = t / 15, j = t - i * 15;
+        double s1 = 0;
+        for (int u = 0; u < 15; u++) s1 += w.FP[i * 15 + u] * Fk[j * 15 + u];
+        const double nn[6] = {c.acc_n * c.acc_n, c.gyr_n * c.gyr_n, c.acc_n * c.acc_n, c.gyr_n * c.gyr_n, c.acc_w * c.acc_w, c.gyr_w * c.gyr_w};
+        double tt = 0;
+        for (int u = 0; u < 18; u++) tt += Vk[i * 18 + u] * nn[u / 3] * Vk[j * 18 + u];
+        w.J[t] = w.FJ[t];
+        w.Pm[t] = s1 + tt;
+    }
+    __syncthreads();
+}
+// one propagate(dt, acc, gyr) on the LDS-resident jacobian/covariance; p's small state is updated by thread 0
+template <class N> __device__ void preint_propagate(PreInt &p, PreWork &w, const N &c, double dt, v3 acc1, v3 gyr1) {
+    if (threadIdx.x == 0) {
         bf::PreintStep o = bf::preint_midpoint(p, dt, acc1, gyr1, w.F, w.V);
         st3(p.dp, o.dp); st3(p.dv, o.dv);
         quat q = qnormalized(o.dq);
@@ -151,37 +173,54 @@ template <class N> __device__ void preint_propagate(PreInt &p, PreWork &w, const
         st3(p.acc0, acc1); st3(p.gyr0, gyr1);
     }
     __syncthreads();
-    if (t < 225) {
-        int i = t / 15, j = t - i * 15;
-        double s = 0, s2 = 0;
-        for (int k = 0; k < 15; k++) { s += w.F[i * 15 + k] * w.J[k * 15 + j]; s2 += w.F[i * 15 + k] * w.Pm[k * 15 + j]; }
-        w.FJ[t] = s; w.FP[t] = s2;
-    }
-    __syncthreads();
-    if (t < 225) {
-        int i = t / 15, j = t - i * 15;
-        double s = 0;
-        for (int k = 0; k < 15; k++) s += w.FP[i * 15 + k] * w.F[j * 15 + k];
-        double nn[6] = {c.acc_n * c.acc_n, c.gyr_n * c.gyr_n, c.acc_n * c.acc_n, c.gyr_n * c.gyr_n, c.acc_w * c.acc_w, c.gyr_w * c.gyr_w};
-        double tt = 0;
-        for (int k = 0; k < 18; k++) tt += w.V[i * 18 + k] * nn[k / 3] * w.V[j * 18 + k];
-        w.J[t] = w.FJ[t];
-        w.Pm[t] = s + tt;
-    }
-    __syncthreads();
+    preint_cov_step(w, w.F, w.V, c);
 }
 
-// n propagate steps on the LDS-resident jacobian / covariance (preint_load'ed into w), pipelined in chunks of PI_CH samples like the
-// per-frame integration of be_ingest: thread 0 runs the short delta-state recursion of a chunk and keeps the state before every step,
-// one lane per sample builds that step's F and V from it, the jacobian / covariance recursion consumes them step by step.  The
-// arithmetic of n calls of preint_propagate (be_factors.h preint_state_step / preint_step_FV are the two halves of preint_midpoint)
+// Sample sources of preint_propagate_many: get(q) yields dt, acc and gyr of sample q of the n to integrate.
+struct PreintArrays {   // the samples as arrays (a slot's own buffers, a stage harness)
+    const double *dt; const double (*acc)[3]; const double (*gyr)[3];
+    __device__ __forceinline__ void get(int q, double &dt_q, double *acc_q, double *gyr_q) const {
+        dt_q = dt[q];
+        for (int k = 0; k < 3; k++) { acc_q[k] = acc[q][k]; gyr_q[k] = gyr[q][k]; }
+    }
+};
+// Side jobs of preint_propagate_many: run by thread 64 (another wavefront than thread 0's) on the m staged samples of a chunk.
+struct PreintNoSide { __device__ __forceinline__ void operator()(int, const double *, const double (*)[3], const double (*)[3]) {} };
+// Estimator::processIMU's world-state recursion of a frame (estimator.cpp:142-152); acc_0 / gyr_0 are the estimator's, not the slot's
+struct WorldStep {
+    v3 a0, g0, P, V; m3 R; v3 Ba, Bg, g;
+    __device__ __forceinline__ void operator()(int m, const double *dt_s, const double (*acc_s)[3], const double (*gyr_s)[3]) {
+        for (int k = 0; k < m; k++) {
+            const v3 acc = ld3(acc_s[k]), gyr = ld3(gyr_s[k]);
+            const double dt = dt_s[k];
+            v3 un_acc_0 = sub(mul(R, sub(a0, Ba)), g);
+            v3 un_gyr = sub(scl(0.5, add(g0, gyr)), Bg);
+            R = mul(R, q2R(deltaQ(scl(dt, un_gyr))));
+            v3 un_acc_1 = sub(mul(R, sub(acc, Ba)), g);
+            v3 un_acc = scl(0.5, add(un_acc_0, un_acc_1));
+            P = add(add(P, scl(dt, V)), scl(dt * dt, scl(0.5, un_acc)));
+            V = add(V, scl(dt, un_acc));
+            a0 = acc; g0 = gyr;
+        }
+    }
+};
+
+// n propagate steps on the LDS-resident jacobian / covariance (preint_load'ed into w), IntegrationBase::push_back pipelined in chunks of
+// PI_CH samples:
+//   A  thread 0 runs the short delta-state recursion of the chunk and keeps the state before every step, thread 64 - another
+//      wavefront - the caller's side job, and with IDLE_CLEARS the threads from 128 on clear the chunk's F / V (the caller then
+//      launches more than 128 threads);
+//   B  one lane per sample builds that step's F (15 x 15) and V (15 x 18) from the state before it, clearing them first without
+//      IDLE_CLEARS (495 stores of one lane);
+//   C  the jacobian / covariance recursion consumes them step by step.
+// The arithmetic of n calls of preint_propagate (be_factors.h preint_state_step / preint_step_FV are the two halves of preint_midpoint)
 // with the serial part of a step shrunk from the whole midpoint step to the recursion.  append: the samples are also filed into p's
-// own buffers (IntegrationBase::push_back).  Used for the merge of MARGIN_SECOND_NEW (estimator.cpp:1651-1687), where the step-by-step
-// version was 100 of the 190 us of that branch.
-// PREINT_MANY_LDS_DOUBLES (kernels.h): F and V of a chunk, LDS the caller lends (the marginalisation's tile region is free by then)
-template <class N> __device__ void preint_propagate_many(PreInt &p, PreWork &w, const N &cfg, int n, const double *dt_src, const double (*acc_src)[3],
-                                      const double (*gyr_src)[3], bool append, double *lds_fv) {
-    const int t = threadIdx.x;
+// own buffers (IntegrationBase::push_back); the caller decides what running over VIO_IMU_SLOT_CAP means.  The per-frame integration of
+// be_ingest and the merge of MARGIN_SECOND_NEW (estimator.cpp:1651-1687) both run this.
+// lds_fv: PREINT_MANY_LDS_DOUBLES (kernels.h) doubles for F and V of a chunk, lent by the caller.
+template <bool IDLE_CLEARS, class N, class Src, class Side>
+__device__ void preint_propagate_many(PreInt &p, PreWork &w, const N &cfg, int n, const Src &src, Side &side, bool append, double *lds_fv) {
+    const int t = threadIdx.x, nt = blockDim.x;
     double (*pm_F)[225] = (double (*)[225])lds_fv;
     double (*pm_V)[270] = (double (*)[270])(lds_fv + PI_CH * 225);
     __shared__ double pm_dt[PI_CH], pm_acc[PI_CH][3], pm_gyr[PI_CH][3];
@@ -194,15 +233,16 @@ template <class N> __device__ void preint_propagate_many(PreInt &p, PreWork &w, 
     __syncthreads();
     for (int q0 = 0; q0 < n; q0 += PI_CH) {
         const int m = min(PI_CH, n - q0);
-        if (t < m) {
-            const int q = q0 + t;
-            pm_dt[t] = dt_src[q];
-            for (int k = 0; k < 3; k++) { pm_acc[t][k] = acc_src[q][k]; pm_gyr[t][k] = gyr_src[q][k]; }
-            const int nb = nb0 + q;
-            if (append && nb < VIO_IMU_SLOT_CAP) { p.dt_buf[nb] = dt_src[q]; for (int k = 0; k < 3; k++) { p.acc_buf[nb][k] = acc_src[q][k]; p.gyr_buf[nb][k] = gyr_src[q][k]; } }
+        if (t < m) {   // stage the chunk's samples
+            const int q = q0 + t, nb = nb0 + q;
+            double dt, acc[3], gyr[3];
+            src.get(q, dt, acc, gyr);
+            pm_dt[t] = dt;
+            for (int k = 0; k < 3; k++) { pm_acc[t][k] = acc[k]; pm_gyr[t][k] = gyr[k]; }
+            if (append && nb < VIO_IMU_SLOT_CAP) { p.dt_buf[nb] = dt; for (int k = 0; k < 3; k++) { p.acc_buf[nb][k] = acc[k]; p.gyr_buf[nb][k] = gyr[k]; } }
         }
         __syncthreads();
-        if (t == 0)
+        if (t == 0) {
             for (int k = 0; k < m; k++) {
                 const v3 acc = ld3(pm_acc[k]), gyr = ld3(pm_gyr[k]);
                 pm_pre[k].dq = s_dq; pm_pre[k].acc0 = s_a0; pm_pre[k].gyr0 = s_g0;
@@ -210,30 +250,16 @@ template <class N> __device__ void preint_propagate_many(PreInt &p, PreWork &w, 
                 s_sum += pm_dt[k];
                 s_a0 = acc; s_g0 = gyr;
             }
-        __syncthreads();
-        if (t < m) bf::preint_step_FV(pm_pre[t], lba, lbg, pm_dt[t], ld3(pm_acc[t]), ld3(pm_gyr[t]), pm_F[t], pm_V[t]);
-        __syncthreads();
-        for (int k = 0; k < m; k++) {
-            const double *Fk = pm_F[k], *Vk = pm_V[k];
-            if (t < 225) {
-                int i = t / 15, j = t - i * 15;
-                double s1 = 0, s2 = 0;
-                for (int u = 0; u < 15; u++) { s1 += Fk[i * 15 + u] * w.J[u * 15 + j]; s2 += Fk[i * 15 + u] * w.Pm[u * 15 + j]; }
-                w.FJ[t] = s1; w.FP[t] = s2;
-            }
-            __syncthreads();
-            if (t < 225) {
-                int i = t / 15, j = t - i * 15;
-                double s1 = 0;
-                for (int u = 0; u < 15; u++) s1 += w.FP[i * 15 + u] * Fk[j * 15 + u];
-                double nn[6] = {cfg.acc_n * cfg.acc_n, cfg.gyr_n * cfg.gyr_n, cfg.acc_n * cfg.acc_n, cfg.gyr_n * cfg.gyr_n, cfg.acc_w * cfg.acc_w, cfg.gyr_w * cfg.gyr_w};
-                double tt = 0;
-                for (int u = 0; u < 18; u++) tt += Vk[i * 18 + u] * nn[u / 3] * Vk[j * 18 + u];
-                w.J[t] = w.FJ[t];
-                w.Pm[t] = s1 + tt;
-            }
-            __syncthreads();
+        } else if (t == 64) {
+            side(m, pm_dt, pm_acc, pm_gyr);
+        } else if (IDLE_CLEARS && t >= 128) {   // (idle otherwise during the recursions)
+            for (int q = t - 128; q < m * 225; q += nt - 128) (&pm_F[0][0])[q] = 0;
+            for (int q = t - 128; q < m * 270; q += nt - 128) (&pm_V[0][0])[q] = 0;
         }
+        __syncthreads();
+        if (t < m) bf::preint_step_FV(pm_pre[t], lba, lbg, pm_dt[t], ld3(pm_acc[t]), ld3(pm_gyr[t]), pm_F[t], pm_V[t], !IDLE_CLEARS);
+        __syncthreads();
+        for (int k = 0; k < m; k++) preint_cov_step(w, pm_F[k], pm_V[k], cfg);
     }
     if (t == 0) {
         st3(p.dp, s_dp); st3(p.dv, s_dv);
@@ -784,110 +810,20 @@ __global__ __launch_bounds__(256) void be_ingest_kernel(Batch B, const uint16_t 
         }
         __syncthreads();
         if (fc != 0) {
-            // IntegrationBase::push_back + Estimator::processIMU for the n samples of the frame, pipelined in chunks of PI_CH samples:
-            //   A  thread 0 runs the delta-state recursion (it keeps the state before every step), thread 64 - another wavefront -
-            //      the world-state recursion of Ps / Rs / Vs[fc], the remaining threads file the samples into the slot's buffer;
-            //   B  one lane per sample builds that step's F (15 x 15) and V (15 x 18) from the state before it;
-            //   C  the jacobian / covariance recursion J <- F J, P <- F P F^T + V Q V^T consumes them step by step.
-            // The serial part of a sample shrinks from the whole midpoint step to its two short recursions; same arithmetic as
-            // preint_propagate (be_factors.h preint_state_step / preint_step_FV are the two halves of preint_midpoint).
+            // IntegrationBase::push_back + Estimator::processIMU for the n samples of the frame: the pipelined propagation on the ring's
+            // interval, with the world-state recursion of Ps / Rs / Vs[fc] as its side job
             preint_load(P, pw);
-            __shared__ double pi_F[PI_CH][225], pi_V[PI_CH][270];
-            __shared__ double pi_dt[PI_CH], pi_acc[PI_CH][3], pi_gyr[PI_CH][3];
-            __shared__ bf::PreintPre pi_pre[PI_CH];
+            __shared__ double pi_fv[PREINT_MANY_LDS_DOUBLES];
+            const PreintRing ring = {it, ia, ig, head, C.NIMU, be.prevTime, curTime, n};
+            WorldStep ws = {ld3(be.acc_0), ld3(be.gyr_0), ld3(be.Ps[fc]), ld3(be.Vs[fc]), ldm(be.Rs[fc]), ld3(be.Bas[fc]), ld3(be.Bgs[fc]), ld3(be.g)};
             const int nb0 = P.n_buf;
-            const v3 lba = ld3(P.lin_ba), lbg = ld3(P.lin_bg);
-            // thread 0: delta state; thread 64: world state of frame fc
-            quat s_dq = mkq(P.dq[0], P.dq[1], P.dq[2], P.dq[3]);
-            v3 s_dp = ld3(P.dp), s_dv = ld3(P.dv), s_a0 = ld3(P.acc0), s_g0 = ld3(P.gyr0);
-            double s_sum = P.sum_dt;
-            v3 w_a0 = ld3(be.acc_0), w_g0 = ld3(be.gyr_0), w_P = ld3(be.Ps[fc]), w_V = ld3(be.Vs[fc]);
-            m3 w_R = ldm(be.Rs[fc]);
-            const v3 w_Ba = ld3(be.Bas[fc]), w_Bg = ld3(be.Bgs[fc]), w_g = ld3(be.g);
-            const double prevTime = be.prevTime;
-            __syncthreads();
             PH(111);
-            for (int q0 = 0; q0 < n; q0 += PI_CH) {
-                const int m = min(PI_CH, n - q0);
-                if (t < m) {   // stage the chunk's samples
-                    const int q = q0 + t, idx = (head + q) % C.NIMU;
-                    const double tq = it[idx];
-                    double dt;
-                    if (q == 0) dt = tq - prevTime;
-                    else if (q == n - 1) dt = curTime - it[(head + q - 1) % C.NIMU];
-                    else dt = tq - it[(head + q - 1) % C.NIMU];
-                    pi_dt[t] = dt;
-                    for (int k = 0; k < 3; k++) { pi_acc[t][k] = ia[(size_t)idx * 3 + k]; pi_gyr[t][k] = ig[(size_t)idx * 3 + k]; }
-                    const int nb = nb0 + q;
-                    if (nb < VIO_IMU_SLOT_CAP) { P.dt_buf[nb] = dt; for (int k = 0; k < 3; k++) { P.acc_buf[nb][k] = ia[(size_t)idx * 3 + k]; P.gyr_buf[nb][k] = ig[(size_t)idx * 3 + k]; } }
-                }
-                __syncthreads();
-                if (t == 0) {
-                    for (int k = 0; k < m; k++) {
-                        const v3 acc = ld3(pi_acc[k]), gyr = ld3(pi_gyr[k]);
-                        pi_pre[k].dq = s_dq; pi_pre[k].acc0 = s_a0; pi_pre[k].gyr0 = s_g0;
-                        bf::preint_state_step(s_dq, s_dp, s_dv, s_a0, s_g0, lba, lbg, pi_dt[k], acc, gyr);
-                        s_sum += pi_dt[k];
-                        s_a0 = acc; s_g0 = gyr;
-                    }
-                } else if (t == 64) {
-                    for (int k = 0; k < m; k++) {   // Estimator::processIMU (estimator.cpp:142-152)
-                        const v3 acc = ld3(pi_acc[k]), gyr = ld3(pi_gyr[k]);
-                        const double dt = pi_dt[k];
-                        v3 un_acc_0 = sub(mul(w_R, sub(w_a0, w_Ba)), w_g);
-                        v3 un_gyr = sub(scl(0.5, add(w_g0, gyr)), w_Bg);
-                        w_R = mul(w_R, q2R(deltaQ(scl(dt, un_gyr))));
-                        v3 un_acc_1 = sub(mul(w_R, sub(acc, w_Ba)), w_g);
-                        v3 un_acc = scl(0.5, add(un_acc_0, un_acc_1));
-                        w_P = add(add(w_P, scl(dt, w_V)), scl(dt * dt, scl(0.5, un_acc)));
-                        w_V = add(w_V, scl(dt, un_acc));
-                        w_a0 = acc; w_g0 = gyr;
-                    }
-                } else if (t >= 128) {   // (idle otherwise during the two recursions: clear the chunk's F / V for preint_step_FV)
-                    for (int q = t - 128; q < m * 225; q += nt - 128) (&pi_F[0][0])[q] = 0;
-                    for (int q = t - 128; q < m * 270; q += nt - 128) (&pi_V[0][0])[q] = 0;
-                }
-                __syncthreads();
-                PH(112);
-                if (t < m) bf::preint_step_FV(pi_pre[t], lba, lbg, pi_dt[t], ld3(pi_acc[t]), ld3(pi_gyr[t]), pi_F[t], pi_V[t], false);
-                __syncthreads();
-                PH(113);
-                for (int k = 0; k < m; k++) {
-                    const double *Fk = pi_F[k], *Vk = pi_V[k];
-                    if (t < 225) {
-                        int i = t / 15, j = t - i * 15;
-                        double s1 = 0, s2 = 0;
-                        for (int u = 0; u < 15; u++) { s1 += Fk[i * 15 + u] * pw.J[u * 15 + j]; s2 += Fk[i * 15 + u] * pw.Pm[u * 15 + j]; }
-                        pw.FJ[t] = s1; pw.FP[t] = s2;
-                    }
-                    __syncthreads();
-                    if (t < 225) {
-                        int i = t / 15, j = t - i * 15;
-                        double s1 = 0;
-                        for (int u = 0; u < 15; u++) s1 += pw.FP[i * 15 + u] * Fk[j * 15 + u];
-                        const double nn[6] = {K.acc_n * K.acc_n, K.gyr_n * K.gyr_n, K.acc_n * K.acc_n, K.gyr_n * K.gyr_n, K.acc_w * K.acc_w, K.gyr_w * K.gyr_w};
-                        double tt = 0;
-#pragma unroll
-                        for (int u = 0; u < 18; u++) tt += Vk[i * 18 + u] * nn[u / 3] * Vk[j * 18 + u];
-                        pw.J[t] = pw.FJ[t];
-                        pw.Pm[t] = s1 + tt;
-                    }
-                    __syncthreads();
-                }
-                PH(114);
-            }
-            if (t == 0) {
-                st3(P.dp, s_dp); st3(P.dv, s_dv);
-                P.dq[0] = s_dq.w; P.dq[1] = s_dq.x; P.dq[2] = s_dq.y; P.dq[3] = s_dq.z;
-                P.sum_dt = s_sum;
-                st3(P.acc0, s_a0); st3(P.gyr0, s_g0);
-                const int nb = nb0 + n;
-                if (nb > VIO_IMU_SLOT_CAP) be.overflow |= 2;
-                P.n_buf = min(nb, VIO_IMU_SLOT_CAP);
-            }
+            preint_propagate_many<true>(P, pw, K, n, ring, ws, true, pi_fv);
+            PH(112);
+            if (t == 0 && nb0 + n > VIO_IMU_SLOT_CAP) be.overflow |= 2;
             if (t == 64) {
-                stm(be.Rs[fc], w_R); st3(be.Ps[fc], w_P); st3(be.Vs[fc], w_V);
-                st3(be.acc_0, w_a0); st3(be.gyr_0, w_g0);
+                stm(be.Rs[fc], ws.R); st3(be.Ps[fc], ws.P); st3(be.Vs[fc], ws.V);
+                st3(be.acc_0, ws.a0); st3(be.gyr_0, ws.g0);
             }
             __syncthreads();
         } else if (t == 0) {   // frame 0: no pre-integration yet, acc_0 / gyr_0 follow the samples
@@ -979,19 +915,8 @@ __device__ __forceinline__ double evaluate(const Ctx &c, const Params &X, const 
     auto imu_item = [&](int i, int part) {
         const int j = i + 1;
         const PreInt &p = c.pre[be.pre_idx[j]];
-        double *out = c.imu_raw + (size_t)i * 15 * 31;
-        if (!cfg.use_imu || p.sum_dt > 10.0) { if (part == 0) for (int k = 0; k < 15; k++) out[k * 31 + 30] = 0; return; }
-        if (part == 0) {
-            double raw[15];
-            bf::imu_raw_residual(p, G, &X.pose[i * 7], &X.sb[i * 9], &X.pose[j * 7], &X.sb[j * 9], raw);
-            for (int r = 0; r < 15; r++) {
-                double sacc = 0;
-                for (int k = 0; k <= r; k++) sacc += p.sqrt_info[r * 15 + k] * raw[k];
-                out[r * 31 + 30] = sacc;
-                cost += 0.5 * sacc * sacc;
-            }
-        } else if (withJ)
-            bf::imu_raw_jacobian_part(p, G, &X.pose[i * 7], &X.sb[i * 9], &X.pose[j * 7], &X.sb[j * 9], part - 1, out, 31);  // raw, whitened in assemble
+        bf::imu_work_item(p, !cfg.use_imu || bf::imu_solver_skips(p), G, &X.pose[i * 7], &X.sb[i * 9], &X.pose[j * 7], &X.sb[j * 9], part, withJ,
+                          c.imu_raw + (size_t)i * 15 * 31, cost);
     };
     {
         // Five work types per factor (whitened residual + four Jacobian column groups), each a different code path.  With at least
@@ -1256,7 +1181,7 @@ __device__ __forceinline__ void assemble(const Batch &B, const Ctx &c, const Par
                 const int i = 2 * (base + wave) + parity;
                 bool act = wave < nconc && i < W;
                 const PreInt *pp = act ? &c.pre[be.pre_idx[i + 1]] : nullptr;
-                if (act && (!c.C->c.use_imu || pp->sum_dt > 10.0)) act = false;
+                if (act && (!c.C->c.use_imu || bf::imu_solver_skips(*pp))) act = false;
                 double *raw_l = work + (wave < nconc ? wave : 0) * 704, *M_l = raw_l + 472;
                 if (act) {
                     const double *raw = c.imu_raw + (size_t)i * 15 * 31;
@@ -2541,22 +2466,13 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
     if (!second_new) {
         // IMU factor (0,1)
         PreInt &p1 = c.pre[be.pre_idx[1]];
-        if (cfg.use_imu && p1.sum_dt < 10.0) {
+        if (cfg.use_imu && bf::imu_marg_uses(p1)) {
             double *Jw = c.pairblk;         // 15x30 whitened
             double *raw = c.imu_raw;        // 15x31
             // five work types (whitened residual + four Jacobian column groups), each on its own wavefront, like evaluate()
             if ((t & 63) == 0) for (int part = t >> 6; part < 5; part += nt >> 6) {
-                v3 G = ld3(be.g);
-                if (part == 0) {
-                    double r15[15];
-                    bf::imu_raw_residual(p1, G, &X.pose[0], &X.sb[0], &X.pose[7], &X.sb[9], r15);
-                    for (int r = 0; r < 15; r++) {
-                        double sacc = 0;
-                        for (int k = 0; k <= r; k++) sacc += p1.sqrt_info[r * 15 + k] * r15[k];
-                        raw[r * 31 + 30] = sacc;
-                    }
-                } else
-                    bf::imu_raw_jacobian_part(p1, G, &X.pose[0], &X.sb[0], &X.pose[7], &X.sb[9], part - 1, raw, 31);
+                double unused = 0;   // (the marginalisation has no use for the cost)
+                bf::imu_work_item(p1, false, ld3(be.g), &X.pose[0], &X.sb[0], &X.pose[7], &X.sb[9], part, true, raw, unused);
             }
             __syncthreads();
             for (int w = t; w < 450; w += nt) {
@@ -3204,7 +3120,8 @@ __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, un
             for (int k = 0; k < 9; k++) be.Rs[W - 1][k] = be.Rs[W][k];
         }
         preint_load(dst, pw);
-        preint_propagate_many(dst, pw, *c.K, src.n_buf, src.dt_buf, src.acc_buf, src.gyr_buf, true, (double *)smem_marg);
+        PreintNoSide none;
+        preint_propagate_many<false>(dst, pw, *c.K, src.n_buf, PreintArrays{src.dt_buf, src.acc_buf, src.gyr_buf}, none, true, (double *)smem_marg);
         preint_store(dst, pw);
         if (t == 0) bf::preint_init(src, ld3(be.acc_0), ld3(be.gyr_0), ld3(be.Bas[W]), ld3(be.Bgs[W]));
         __syncthreads();
@@ -3451,29 +3368,50 @@ __global__ __launch_bounds__(64) void be_stage_imu_block_kernel(const PreInt *P,
     }
 }
 
-// The two propagation routines of the pipeline on one sample list, for comparison with each other and with the definition: mode 0 = n calls
-// of preint_propagate (be_dyn_finalize, be_marg's repropagation), 1 = preint_propagate_many(append = false), 2 = the same with append = true
-// (the MARGIN_SECOND_NEW merge: the samples are also filed into P's buffers, n_buf saturating at VIO_IMU_SLOT_CAP).  preint_store refreshes
-// sqrt_info as everywhere.  out686 = delta_p(3) delta_q(wxyz) delta_v(3) sum_dt jacobian(225) covariance(225) sqrt_info(225).
-__global__ __launch_bounds__(256) void be_stage_preint_kernel(vio_config cfg, PreInt *P, int n, const double *dt, const double *acc,
-                                                               const double *gyr, int mode, double *out686) {
-    __shared__ PreWork pw;
-    __shared__ double lds_fv[PREINT_MANY_LDS_DOUBLES];
-    const int t = threadIdx.x;
-    preint_load(*P, pw);
-    if (mode == 0)
-        for (int q = 0; q < n; q++) preint_propagate(*P, pw, cfg, dt[q], ld3(acc + 3 * q), ld3(gyr + 3 * q));
-    else
-        preint_propagate_many(*P, pw, cfg, n, dt, (const double (*)[3])acc, (const double (*)[3])gyr, mode == 2, lds_fv);
-    preint_store(*P, pw);
-    const PreInt &p = *P;
-    if (t == 0) {
+// out686 of the pre-integration harnesses = delta_p(3) delta_q(wxyz) delta_v(3) sum_dt jacobian(225) covariance(225) sqrt_info(225)
+__device__ __forceinline__ void stage_preint_out(const PreInt &p, double *out686) {
+    if (threadIdx.x == 0) {
         out686[0] = p.dp[0]; out686[1] = p.dp[1]; out686[2] = p.dp[2];
         for (int k = 0; k < 4; k++) out686[3 + k] = p.dq[k];
         out686[7] = p.dv[0]; out686[8] = p.dv[1]; out686[9] = p.dv[2];
         out686[10] = p.sum_dt;
     }
-    for (int k = t; k < 225; k += blockDim.x) { out686[11 + k] = p.jac[k]; out686[236 + k] = p.cov[k]; out686[461 + k] = p.sqrt_info[k]; }
+    for (int k = threadIdx.x; k < 225; k += blockDim.x) { out686[11 + k] = p.jac[k]; out686[236 + k] = p.cov[k]; out686[461 + k] = p.sqrt_info[k]; }
+}
+// The two propagation routines of the pipeline on one sample list, for comparison with each other and with the definition: mode 0 = n calls
+// of preint_propagate (be_dyn_finalize, be_marg's repropagation), 1 = preint_propagate_many(append = false), 2 = the same with append = true
+// (the MARGIN_SECOND_NEW merge: the samples are also filed into P's buffers, n_buf saturating at VIO_IMU_SLOT_CAP).  preint_store refreshes
+// sqrt_info as everywhere.
+__global__ __launch_bounds__(256) void be_stage_preint_kernel(vio_config cfg, PreInt *P, int n, const double *dt, const double *acc,
+                                                               const double *gyr, int mode, double *out686) {
+    __shared__ PreWork pw;
+    __shared__ double lds_fv[PREINT_MANY_LDS_DOUBLES];
+    preint_load(*P, pw);
+    if (mode == 0)
+        for (int q = 0; q < n; q++) preint_propagate(*P, pw, cfg, dt[q], ld3(acc + 3 * q), ld3(gyr + 3 * q));
+    else {
+        PreintNoSide none;
+        preint_propagate_many<false>(*P, pw, cfg, n, PreintArrays{dt, (const double (*)[3])acc, (const double (*)[3])gyr}, none, mode == 2, lds_fv);
+    }
+    preint_store(*P, pw);
+    stage_preint_out(*P, out686);
+}
+// What be_ingest adds to preint_propagate_many: the n samples of a ring's interval as the source (PreintRing) and the world-state step
+// (WorldStep) as the side job, append on.  world31 (in and out) = WorldStep's fields acc_0 gyr_0 P V R(9) Ba Bg g, then the overflow
+// bits by be_ingest's rule.
+__global__ __launch_bounds__(256) void be_stage_preint_ring_kernel(vio_config cfg, PreInt *P, PreintRing ring, double *world31, double *out686) {
+    __shared__ PreWork pw;
+    __shared__ double lds_fv[PREINT_MANY_LDS_DOUBLES];
+    const double *w = world31;
+    const int t = threadIdx.x;
+    preint_load(*P, pw);
+    WorldStep ws = {ld3(w), ld3(w + 3), ld3(w + 6), ld3(w + 9), ldm(w + 12), ld3(w + 21), ld3(w + 24), ld3(w + 27)};
+    const int nb0 = P->n_buf;
+    preint_propagate_many<true>(*P, pw, cfg, ring.n, ring, ws, true, lds_fv);
+    if (t == 0) world31[30] = nb0 + ring.n > VIO_IMU_SLOT_CAP ? 2 : 0;
+    if (t == 64) { st3(world31, ws.a0); st3(world31 + 3, ws.g0); st3(world31 + 6, ws.P); st3(world31 + 9, ws.V); stm(world31 + 12, ws.R); }
+    preint_store(*P, pw);
+    stage_preint_out(*P, out686);
 }
 // IntegrationBase::evaluate and the raw (un-whitened) Jacobian of IMUFactor::Evaluate on a caller-supplied pre-integration (P: delta state,
 // jacobian, linearisation biases).  Lane 0: imu_raw_residual and imu_raw_jacobian (r15, J450 = 15 x 30 row-major, columns pose_i(6)

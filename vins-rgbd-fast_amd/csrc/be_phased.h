@@ -387,7 +387,8 @@ __device__ __forceinline__ double ps_eval_role(const Batch &B, const int s, cons
                 const int j = i + 1;
                 const PreInt &p = *(const PreInt *)(pl + (size_t)i * PH_LD);   // only the header fields are read
                 double *__restrict__ out = c.imu_raw + (size_t)i * 15 * 31;
-                if (!cfg.use_imu || p.sum_dt > 10.0) { if (part_ == 0) for (int k = 0; k < 15; k++) out[k * 31 + 30] = 0; continue; }
+                // bf::imu_work_item, written out: the call costs this kernel's register-capped variants (ps_eval_kernel_occ4, ps_ls_kernel) spills
+                if (!cfg.use_imu || bf::imu_solver_skips(p)) { if (part_ == 0) for (int k = 0; k < 15; k++) out[k * 31 + 30] = 0; continue; }
                 if (part_ == 0) {
                     double raw[15];
                     bf::imu_raw_residual(p, G, &X.pose[i * 7], &X.sb[i * 9], &X.pose[j * 7], &X.sb[j * 9], raw);
@@ -585,7 +586,8 @@ __device__ __forceinline__ void ps_eval_body(const Batch &B) {
                 const int j = i + 1;
                 const PreInt &p = *(const PreInt *)(pl + (size_t)i * PH_LD);   // only the header fields are read
                 double *__restrict__ out = c.imu_raw + (size_t)i * 15 * 31;
-                if (!cfg.use_imu || p.sum_dt > 10.0) { if (part_ == 0) for (int k = 0; k < 15; k++) out[k * 31 + 30] = 0; continue; }
+                // bf::imu_work_item, written out: the call costs this kernel's register-capped variants (ps_eval_kernel_occ4, ps_ls_kernel) spills
+                if (!cfg.use_imu || bf::imu_solver_skips(p)) { if (part_ == 0) for (int k = 0; k < 15; k++) out[k * 31 + 30] = 0; continue; }
                 if (part_ == 0) {
                     double raw[15];
                     bf::imu_raw_residual(p, G, &X.pose[i * 7], &X.sb[i * 9], &X.pose[j * 7], &X.sb[j * 9], raw);
@@ -795,7 +797,7 @@ __device__ __forceinline__ void ps_asm_a_body(const Batch &B) {
         const int i = item - npairs;
         const PreInt &pp = c.pre[be.pre_idx[i + 1]];
         double *G = ps_imu_blk(c) + (size_t)i * 768;
-        if (!c.C->c.use_imu || pp.sum_dt > 10.0) { for (int e = lane; e < 768; e += 64) G[e] = 0; return; }
+        if (!c.C->c.use_imu || bf::imu_solver_skips(pp)) { for (int e = lane; e < 768; e += 64) G[e] = 0; return; }
         double *raw_l = imu_lds + wave * 704, *M_l = raw_l + 472;
         const double *raw = c.imu_raw + (size_t)i * 15 * 31;
         for (int q = lane; q < 465; q += 64) raw_l[q] = raw[q];
@@ -1029,20 +1031,9 @@ __global__ __launch_bounds__(256) void ps_evalf_kernel(Batch B) {
                 const int j = i + 1;
                 const PreInt &p = *(const PreInt *)(pl + (size_t)i * PH_LD);   // only the header fields are read
                 double *out = rawl + (size_t)i * 465;
-                if (p.sum_dt > 10.0) { if (wt == 0) for (int k = 0; k < 15; k++) out[k * 31 + 30] = 0; continue; }
-                if (wt == 0) {
-                    double raw[15];
-                    bf::imu_raw_residual(p, G, &X.pose[i * 7], &X.sb[i * 9], &X.pose[j * 7], &X.sb[j * 9], raw);
-                    for (int r = 0; r < 15; r++) {
-                        double sacc = 0;
-                        for (int k = 0; k <= r; k++) sacc += p.sqrt_info[r * 15 + k] * raw[k];
-                        out[r * 31 + 30] = sacc;
-                        cost += 0.5 * sacc * sacc;
-                    }
-                } else if (withJ) {
-                    bf::imu_raw_jacobian_part(p, G, &X.pose[i * 7], &X.sb[i * 9], &X.pose[j * 7], &X.sb[j * 9], wt - 1, out, 31);
-                    if (wt == 3) bf::imu_raw_jacobian_part(p, G, &X.pose[i * 7], &X.sb[i * 9], &X.pose[j * 7], &X.sb[j * 9], 3, out, 31);
-                }
+                const bool skip = bf::imu_solver_skips(p);
+                bf::imu_work_item(p, skip, G, &X.pose[i * 7], &X.sb[i * 9], &X.pose[j * 7], &X.sb[j * 9], wt, withJ, out, cost);
+                if (wt == 3) bf::imu_work_item(p, skip, G, &X.pose[i * 7], &X.sb[i * 9], &X.pose[j * 7], &X.sb[j * 9], 4, withJ, out, cost);
             }
         }
         __syncthreads();
@@ -1050,7 +1041,7 @@ __global__ __launch_bounds__(256) void ps_evalf_kernel(Batch B) {
             for (int i = wave; i < W; i += NW) {   // IMU Gram blocks [Jw r]^T [Jw r] on the matrix cores, one wavefront per factor
                 const PreInt &p = *(const PreInt *)(pl + (size_t)i * PH_LD);
                 double *G = ps_imu_blk(c) + (size_t)i * 768;
-                if (p.sum_dt > 10.0) { for (int e = lane; e < 768; e += 64) G[e] = 0; continue; }
+                if (bf::imu_solver_skips(p)) { for (int e = lane; e < 768; e += 64) G[e] = 0; continue; }
                 v4f64 a00 = {0, 0, 0, 0}, a10 = {0, 0, 0, 0}, a11 = {0, 0, 0, 0};
                 imu_block_mfma(rawl + (size_t)i * 465, p.sqrt_info, li, lk, a00, a10, a11);
                 for (int r = 0; r < 4; r++) {
@@ -1306,7 +1297,7 @@ __device__ __forceinline__ unsigned ps_imu_ok_mask(const Ctx &c, const BeSeq &be
     // IMU factors that exist (estimator.cpp:1212-1220 skips pre-integrations longer than 10 s): one lane per factor, then a mask -- looked up per
     // entry it was two dependent global loads (pre_idx, then sum_dt) in front of every IMU term
     const int W = c.W;
-    const bool f_ok = (int)(threadIdx.x & 63) < W && c.C->c.use_imu && !(c.pre[be.pre_idx[min((int)(threadIdx.x & 63), W - 1) + 1]].sum_dt > 10.0);
+    const bool f_ok = (int)(threadIdx.x & 63) < W && c.C->c.use_imu && !bf::imu_solver_skips(c.pre[be.pre_idx[min((int)(threadIdx.x & 63), W - 1) + 1]]);
     return (unsigned)__ballot(f_ok);
 }
 __device__ __forceinline__ double ps_h_entry(const Ctx &c, const SolveSt &st, const BeSeq &be, const unsigned imu_ok, const int a, const int bcol) {
@@ -1498,7 +1489,7 @@ __device__ __forceinline__ void ps_asm_b_blocks(const Batch &B, int s, int blk, 
     const int NBLK = 2 * W1 + 2, NTRI = NBLK * (NBLK + 1) / 2, NITEM = NTRI + NBLK;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     // IMU factors that exist (estimator.cpp:1212-1220 skips pre-integrations longer than 10 s): one lane per factor, then a mask
-    const bool f_ok = lane < W && c.C->c.use_imu && !(c.pre[be.pre_idx[min(lane, W - 1) + 1]].sum_dt > 10.0);
+    const bool f_ok = lane < W && c.C->c.use_imu && !bf::imu_solver_skips(c.pre[be.pre_idx[min(lane, W - 1) + 1]]);
     const unsigned imu_ok = (unsigned)__ballot(f_ok);
     const bool scale_pending = st.scale_pending != 0;
     for (int item0 = blk * nw + wave; item0 < NITEM; item0 += nb_b * nw) {
@@ -2118,7 +2109,7 @@ __global__ __launch_bounds__(256, 2) void ps_ls_kernel(Batch B) {   // (held to 
                 const int i = q / 15, r = q - 15 * i;
                 const PreInt &p = c.pre[be.pre_idx[i + 1]];
                 double acc = 0;
-                if (cfg.use_imu && !(p.sum_dt > 10.0)) {
+                if (cfg.use_imu && !bf::imu_solver_skips(p)) {
                     const double *Jr = c.imu_raw + (size_t)i * 15 * 31 + r * 31;
                     for (int d = 0; d < 6; d++) acc += Jr[d] * delta[6 * i + d] + Jr[15 + d] * delta[6 * (i + 1) + d];
                     for (int d = 0; d < 9; d++) acc += Jr[6 + d] * delta[6 * W1 + 9 * i + d] + Jr[21 + d] * delta[6 * W1 + 9 * (i + 1) + d];
@@ -2129,7 +2120,7 @@ __global__ __launch_bounds__(256, 2) void ps_ls_kernel(Batch B) {   // (held to 
             for (int q = t; q < 15 * W; q += nt) {
                 const int i = q / 15, r = q - 15 * i;
                 const PreInt &p = c.pre[be.pre_idx[i + 1]];
-                if (!cfg.use_imu || p.sum_dt > 10.0) continue;
+                if (!cfg.use_imu || bf::imu_solver_skips(p)) continue;
                 double mu_r = 0;
                 for (int k = 0; k <= r; k++) mu_r += p.sqrt_info[r * 15 + k] * vj[15 * i + k];
                 gd += c.imu_raw[(size_t)i * 15 * 31 + r * 31 + 30] * mu_r;

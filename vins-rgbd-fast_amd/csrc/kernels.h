@@ -4,8 +4,9 @@
 #include "vio_state.h"
 #include "../../include/vio_synth.h"
 
-// pipelined pre-integration (be_kernels.hip): samples per chunk, and the LDS doubles preint_propagate_many borrows from its caller
-// (F 15x15 and V 15x18 of every sample of a chunk); the host sizes the marginalisation's dynamic LDS with the same macro
+// pipelined pre-integration (be_kernels.hip preint_propagate_many; be_ingest and be_marg run it): samples per chunk, and the LDS doubles
+// it borrows from its caller (F 15x15 and V 15x18 of every sample of a chunk); the host sizes the marginalisation's dynamic LDS with the same
+// macro
 #define PI_CH 8
 #define PREINT_MANY_LDS_DOUBLES (PI_CH * (225 + 270))
 // dynamic LDS of fast_cell (fe_kernels.hip) for a rw x rh region: tile (pitch up to rw + 6) + score plane + NMS ballot words
@@ -89,6 +90,21 @@ __global__ void be_stage_projection_kernel(vio_config cfg, const double *in, int
 __global__ void be_stage_imu_block_kernel(const PreInt *P, const double *par, double g_norm, double *G961);
 __global__ void be_stage_preint_kernel(vio_config cfg, PreInt *P, int n, const double *dt, const double *acc, const double *gyr, int mode,
                                        double *out686);
+// Sample source of preint_propagate_many (be_kernels.hip) in be_ingest and in its stage harness: the frame's interval of a sequence's IMU
+// ring (getIMUInterval + the dt of processMeasurements, estimator.cpp:185-200): n samples from `head`, the last one being the first at or
+// after curTime.  dt runs from prevTime to the first stamp, between stamps, and up to curTime.
+struct PreintRing {
+    const double *it, *ia, *ig; int head, NIMU; double prevTime, curTime; int n;
+    __device__ __forceinline__ void get(int q, double &dt_q, double *acc_q, double *gyr_q) const {
+        const int idx = (head + q) % NIMU;
+        const double tq = it[idx];
+        if (q == 0) dt_q = tq - prevTime;
+        else if (q == n - 1) dt_q = curTime - it[(head + q - 1) % NIMU];
+        else dt_q = tq - it[(head + q - 1) % NIMU];
+        for (int k = 0; k < 3; k++) { acc_q[k] = ia[(size_t)idx * 3 + k]; gyr_q[k] = ig[(size_t)idx * 3 + k]; }
+    }
+};
+__global__ void be_stage_preint_ring_kernel(vio_config cfg, PreInt *P, PreintRing ring, double *world31, double *out686);
 __global__ void be_stage_imu_raw_kernel(const PreInt *P, const double *par, double g_norm, double *r15, double *J450, double *Jp465);
 __global__ void be_stage_projection_pair_kernel(vio_config cfg, const double *in, int use_td, int cauchy, int rs, int ext, double *r2, double *wgt,
                                                 double *J);
