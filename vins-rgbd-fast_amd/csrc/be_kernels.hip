@@ -290,6 +290,21 @@ __device__ void lm_compact(Ctx &c, int *flags, int *offs, int *scratch) {
     __syncthreads();
 }
 
+// the same compaction on LDS copies of the order list, the flags and the offsets (finish_body<true>): the counters stay in registers (n, nfree:
+// uniform over the workgroup), the freed slots go to the free stack in HBM in the same places; the caller writes order / counters back once
+__device__ void lm_compact_staged(Ctx &c, int *ord, int *tmp, int *flags, int *offs, int *scratch, int &n, int &nfree) {
+    const int kept = block_scan_flags(flags, n, offs, scratch);
+    const int t = threadIdx.x, nt = blockDim.x;
+    for (int k = t; k < n; k += nt) tmp[k] = ord[k];
+    __syncthreads();
+    // (two loops: as one if / else the compiler merges the two stores into a single flat store through a selected LDS-or-HBM address)
+    for (int k = t; k < n; k += nt) if (flags[k]) ord[offs[k]] = tmp[k];
+    for (int k = t; k < n; k += nt) if (!flags[k]) c.lm_free[nfree + (k - offs[k])] = tmp[k];
+    __syncthreads();
+    nfree += n - kept;
+    n = kept;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ VO mode: FeatureManager::initFramePoseByPnP
@@ -1763,8 +1778,10 @@ __device__ __forceinline__ void solve_epilogue(Ctx &c, const Params &X, double c
 
 }  // namespace
 
-template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem_marg);
-__device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, unsigned char *smem_marg);
+// LDSA: the reduced system A, b, b_r and the frame blocks G_j live in the dynamic LDS (kernels.h marg_resident_lds_bytes) instead of c.margA / margB /
+// margV / vec / pairblk; LT: the window slide works on LDS copies of the landmark tables.  Compile-time, so that every loop addresses one address space.
+template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem_marg);
+template <bool LT> __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, unsigned char *smem_marg);
 
 // solve -> marginalise -> window slide for one sequence per workgroup (1024 threads); fusing the three stages makes the
 // step time the maximum over sequences of the *sum* of the stage times instead of the sum of per-stage maxima.
@@ -1794,9 +1811,21 @@ __global__ __launch_bounds__(512) void be_marg_kernel(Batch B) {
     __shared__ double sred[64];
     __shared__ PreWork pw;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    marg_body<false>(B, s, scratch, sred, smem);
+    marg_body<false, true>(B, s, scratch, sred, smem);
     __syncthreads();
-    finish_body(B, s, scratch, pw, smem);
+    finish_body<true>(B, s, scratch, pw, smem);
+}
+// the same stage with the reduced system, the frame blocks and the landmark tables in HBM scratch (rounds 1 - 6): windows whose system does not fit
+// the workgroup's LDS (W = 12 and up) and VIO_MARG_LDS = 0
+__global__ __launch_bounds__(512) void be_marg_hbm_kernel(Batch B) {
+    const int s = blockIdx.x + B.s0;
+    __shared__ int scratch[2 * 512 + 8];
+    __shared__ double sred[64];
+    __shared__ PreWork pw;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    marg_body<false, false>(B, s, scratch, sred, smem);
+    __syncthreads();
+    finish_body<false>(B, s, scratch, pw, smem);
 }
 // vio_config.marg_exact: the same stage with the marginalisation of marginalization_factor.cpp:281-315 followed literally (its own kernel so
 // that the hot kernel's registers / LDS are untouched by the parity instrument)
@@ -1806,9 +1835,9 @@ __global__ __launch_bounds__(512) void be_marg_exact_kernel(Batch B) {
     __shared__ double sred[64];
     __shared__ PreWork pw;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    marg_body<true>(B, s, scratch, sred, smem);
+    marg_body<true, false>(B, s, scratch, sred, smem);
     __syncthreads();
-    finish_body(B, s, scratch, pw, smem);
+    finish_body<false>(B, s, scratch, pw, smem);
 }
 
 __device__ __forceinline__ void solve_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem, PreWork &pw) {
@@ -2357,7 +2386,8 @@ __device__ void marg_exact_finish(const Ctx &c, BeSeq &be, double *A, const doub
     if (VIO_TIMERS && t == 0) be.dbg[10] = (int)(VIO_CLOCK() - tx0);
 }
 
-template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem_marg) {
+template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem_marg) {
+    static_assert(!(EXACT && LDSA), "the literal marginalisation keeps its system in HBM");
     const int t = threadIdx.x, nt = blockDim.x;
     Ctx c = make_ctx(B, s);
     const DevCfg &C = *B.cfg;
@@ -2409,7 +2439,11 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
     // reduced system over q = [m-block (md) | kept block (n)]
     const int md = second_new ? 6 : 15;
     const int mq = md + n;
-    double *A = c.margA, *b = c.margB;
+    // (LDSA: behind the overlay region, laid out for md = 15; the overlay itself holds Jw, then G_j, then T1 / A_mr, then the tiles of c0)
+    double *const ovl = (double *)smem_marg;
+    double *const Ares = (double *)(smem_marg + marg_overlay_bytes(n, W, true));
+    double *A = LDSA ? Ares : c.margA, *b = LDSA ? Ares + (size_t)(n + 15) * (n + 15) : c.margB;
+    double *Gj = LDSA ? ovl : c.pairblk;   // frame blocks, W x 210
     for (int i = t; i < mq * mq; i += nt) A[i] = 0;
     for (int i = t; i < mq; i += nt) b[i] = 0;
     __syncthreads();
@@ -2467,7 +2501,7 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
         // IMU factor (0,1)
         PreInt &p1 = c.pre[be.pre_idx[1]];
         if (cfg.use_imu && bf::imu_marg_uses(p1)) {
-            double *Jw = c.pairblk;         // 15x30 whitened
+            double *Jw = Gj;                // 15x30 whitened (the frame blocks' place, before they exist)
             double *raw = c.imu_raw;        // 15x31
             // five work types (whitened residual + four Jacobian column groups), each on its own wavefront, like evaluate()
             if ((t & 63) == 0) for (int part = t >> 6; part < 5; part += nt >> 6) {
@@ -2622,7 +2656,7 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
                         a11 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1[u], x1[u], a11, 0, 0, 0);
                     }
                 }
-                double *out = c.pairblk + (size_t)(j - 1) * 210;
+                double *out = Gj + (size_t)(j - 1) * 210;
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     int row = lk + 4 * r, col = li;
@@ -2671,7 +2705,7 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
                 rhs[u] = bb == mq; row[u] = a; dst[u] = a * mq + bb;
                 sidx[u] = sym_idx(la, lb);
                 const int f1 = fa > 0 ? fa : (fb > 0 ? fb : 1);
-                pv[u] = use[u] ? c.pairblk[(size_t)(f1 - 1) * 210 + sidx[u]] : 0.0;
+                pv[u] = use[u] ? Gj[(size_t)(f1 - 1) * 210 + sidx[u]] : 0.0;
                 av[u] = use[u] ? (rhs[u] ? b[a] : A[dst[u]]) : 0.0;
             }
 #pragma unroll
@@ -2681,7 +2715,7 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
                 if (multi[u]) {   // a column every residual carries against another such: one term per frame, all loads first
                     double fv[VIO_MAXW];
 #pragma unroll
-                    for (int j = 0; j < VIO_MAXW; j++) fv[j] = c.pairblk[(size_t)min(j, W - 1) * 210 + sidx[u]];
+                    for (int j = 0; j < VIO_MAXW; j++) fv[j] = Gj[(size_t)min(j, W - 1) * 210 + sidx[u]];
                     sacc = 0;
 #pragma unroll
                     for (int j = 0; j < VIO_MAXW; j++) if (j < W) sacc += fv[j];
@@ -2778,8 +2812,10 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
     }
     __syncthreads();
     PH(37);
-    double *Ar = c.margV;             // reuse as A_r first (n x n), eigenvectors go to margW+...
-    double *br = c.vec;               // n
+    // A_r (n x n): c.margV, or (LDSA) in place in the kept block of A -- each entry needs its own entry of A and the staged T1 / A_mr only
+    const int lda = LDSA ? mq : n;
+    double *Ar = LDSA ? A + (size_t)md * mq + md : c.margV;
+    double *br = LDSA ? Ares + (size_t)(n + 15) * (n + 16) : c.vec;   // n
     for (int w0 = t; w0 < n * n; w0 += 8 * nt) {
         double av[8];
 #pragma unroll
@@ -2791,7 +2827,7 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
             const int i = w / n, j = w - i * n;
             double tt = av[u];
             for (int k = 0; k < md; k++) tt -= T1[i * md + k] * Amr[k * n + j];
-            Ar[w] = tt;
+            Ar[i * lda + j] = tt;
         }
     }
     for (int i = t; i < n; i += nt) {
@@ -2849,7 +2885,7 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
     for (int w0 = t; w0 < n * n; w0 += 8 * nt) {
         double x[8], y[8];
 #pragma unroll
-        for (int u = 0; u < 8; u++) { const int w = min(w0 + u * nt, n * n - 1), i = w / n, j = w - i * n; x[u] = Ar[i * n + j]; y[u] = Ar[j * n + i]; }
+        for (int u = 0; u < 8; u++) { const int w = min(w0 + u * nt, n * n - 1), i = w / n, j = w - i * n; x[u] = Ar[i * lda + j]; y[u] = Ar[j * lda + i]; }
 #pragma unroll
         for (int u = 0; u < 8; u++) if (w0 + u * nt < n * n) c.prior_H[w0 + u * nt] = 0.5 * (x[u] + y[u]);
     }
@@ -2863,7 +2899,7 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
         const int nbq = (n + 15) >> 4;
         double *T = (double *)smem_marg;
         double dmax = 0;
-        for (int i = t; i < n; i += nt) dmax = fmax(dmax, fabs(Ar[i * n + i]));
+        for (int i = t; i < n; i += nt) dmax = fmax(dmax, fabs(Ar[i * lda + i]));
         dmax = block_max(dmax, sred);
         const double delta = 64.0 * 2.220446049250313e-16 * (double)n * dmax;
         const int ntl = nbq * (nbq + 1) / 2 * 256;
@@ -2877,7 +2913,7 @@ template <bool EXACT> __device__ void marg_body(const Batch &B, int s, int *scra
                 tri_decode(tile, ti, tj);
                 const int i = 16 * ti + r, j = 16 * tj + cc, ic = min(i, n - 1), jc = min(j, n - 1);
                 ii[u] = i; jj[u] = j; dd[u] = tl_idx(ti, tj, r, cc);
-                x[u] = Ar[ic * n + jc]; y[u] = Ar[jc * n + ic];
+                x[u] = Ar[ic * lda + jc]; y[u] = Ar[jc * lda + ic];
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
@@ -2994,7 +3030,7 @@ __global__ __launch_bounds__(512) void be_prior_factor_kernel(Batch B, int seq) 
 }
 
 // ====================================================================================================== be_finish
-__device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, unsigned char *smem_marg) {   // smem_marg: the marginalisation's dynamic LDS, free again (>= PREINT_MANY_LDS_DOUBLES doubles)
+template <bool LT> __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, unsigned char *smem_marg) {   // smem_marg: the marginalisation's dynamic LDS, free again (>= PREINT_MANY_LDS_DOUBLES doubles)
     const int t = threadIdx.x, nt = blockDim.x;
     Ctx c = make_ctx(B, s);
     const DevCfg &C = *B.cfg;
@@ -3006,7 +3042,23 @@ __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, un
     if (!be.processed || be.rebooted) return;
     PH_INIT;
     int nlm = be.n_lm;
-    int *flag = c.lm_pidx, *offs = c.lm_aidx;  // free after the solve
+    // LT: the order list, the start frame and observation count of its entries (by position), the flags and the offsets staged in the dynamic LDS
+    // where the reduced system was (MARG_LM_TABLES arrays of NL integers); n_lm / n_free in registers.  The order list, the flags and the offsets go
+    // back to HBM once (stage_back): entry for entry what the two compactions in HBM leave, the stale tails included.
+    int *const tab = (int *)(smem_marg + marg_overlay_bytes(c.NPR, W, true));
+    int *const flag = LT ? tab + 2 * c.NL : c.lm_pidx, *const offs = LT ? tab + 3 * c.NL : c.lm_aidx;  // (HBM: free after the solve)
+    int *const ord = LT ? tab : c.lm_order, *const otmp = tab + c.NL, *const lst = tab + 4 * c.NL, *const lno = tab + 5 * c.NL;
+    const int nlm0 = nlm;
+    int nfree = be.n_free;
+    if (LT) for (int k = t; k < nlm; k += nt) { const int slot = c.lm_order[k]; ord[k] = slot; lst[k] = c.lm_start[slot]; lno[k] = c.lm_nobs[slot]; }
+    auto lm_st = [&](int k, int slot) -> int { return LT ? lst[k] : c.lm_start[slot]; };
+    auto lm_no = [&](int k, int slot) -> int { return LT ? lno[k] : c.lm_nobs[slot]; };
+    auto compact = [&]() { if (LT) lm_compact_staged(c, ord, otmp, flag, offs, scratch, nlm, nfree); else lm_compact(c, flag, offs, scratch); };
+    auto stage_back = [&]() {
+        if (!LT) return;
+        for (int k = t; k < nlm0; k += nt) { c.lm_order[k] = ord[k]; c.lm_pidx[k] = flag[k]; c.lm_aidx[k] = offs[k]; }
+        if (t == 0) { be.n_lm = nlm; be.n_free = nfree; }
+    };
     const int fc = be.frame_count;
     const int sflag0 = be.solver_flag;
     __syncthreads();
@@ -3039,11 +3091,11 @@ __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, un
         m3 ric = ldm(be.ric);
         v3 tic = ld3(be.tic);
         for (int k = t; k < nlm; k += nt) {
-            int slot = c.lm_order[k];
-            if (!(c.lm_nobs[slot] >= 2 && c.lm_start[slot] < W - 2)) continue;
+            int slot = ord[k];
+            const int imu_i = lm_st(k, slot), no = lm_no(k, slot);
+            if (!(no >= 2 && imu_i < W - 2)) continue;
             double depth = c.lm_depth[slot];
             if (depth < 0) continue;
-            int imu_i = c.lm_start[slot], no = c.lm_nobs[slot];
             const double *oi = obs_ptr(c, slot, imu_i);
             v3 pts_i = mk(oi[0], oi[1], oi[2]);
             double err = 0, err3 = 0;
@@ -3087,13 +3139,14 @@ __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, un
         m3 R0 = mul(ldm(be.back_R0), ldm(be.ric)), R1 = mul(ldm(be.Rs[0]), ldm(be.ric));
         v3 P0 = add(ld3(be.back_P0), mul(ldm(be.back_R0), ld3(be.tic))), P1 = add(ld3(be.Ps[0]), mul(ldm(be.Rs[0]), ld3(be.tic)));
         for (int k = t; k < nlm; k += nt) {
-            int slot = c.lm_order[k];
+            int slot = ord[k];
             int keep = 1;
-            if (c.lm_start[slot] != 0) c.lm_start[slot]--;
+            const int st = lm_st(k, slot);
+            if (st != 0) c.lm_start[slot] = st - 1;
             else {
                 const double *o0 = obs_ptr(c, slot, 0);
                 v3 uv_i = mk(o0[0], o0[1], o0[2]);
-                int no = c.lm_nobs[slot] - 1;
+                int no = lm_no(k, slot) - 1;
                 c.lm_nobs[slot] = no;
                 if (dyn_initial) keep = no > 0;     // FeatureManager::removeBack (feature_manager.cpp:693-708): solver_flag == INITIAL
                 else if (no < 2) keep = 0;
@@ -3109,7 +3162,7 @@ __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, un
         __syncthreads();
         if (t == 0) be.ring_base = (be.ring_base + 1) % W1;  // frame f becomes frame f-1 without moving observations
         __syncthreads();
-        lm_compact(c, flag, offs, scratch);
+        compact();
     } else {
         // MARGIN_SECOND_NEW: merge the IMU samples of frame W into W-1 (:1651-1687)
         PreInt &dst = c.pre[be.pre_idx[W - 1]];
@@ -3127,9 +3180,9 @@ __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, un
         __syncthreads();
         // slideWindowNew -> removeFront(frame_count) (feature_manager.cpp:710-730)
         for (int k = t; k < nlm; k += nt) {
-            int slot = c.lm_order[k];
+            int slot = ord[k];
             int keep = 1;
-            int st = c.lm_start[slot], no = c.lm_nobs[slot];
+            int st = lm_st(k, slot), no = lm_no(k, slot);
             if (st == W) {
                 double *d = obs_ptr(c, slot, W - 1);
                 const double *sr = obs_ptr(c, slot, W);
@@ -3150,20 +3203,22 @@ __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, un
             flag[k] = keep;
         }
         __syncthreads();
-        lm_compact(c, flag, offs, scratch);
+        compact();
     }
     PH(29);
     if (dyn_initial) {   // still INITIAL: nothing to publish (the frame's flags still count)
         if (t == 0 && (be.overflow & ~VIO_OVF_DEVIATION)) be.overflow_frames++;
+        stage_back();
         return;
     }
     // ---- removeFailures (feature_manager.cpp:225-233); not called on the STATIC initialisation frame (estimator.cpp:282-290)
     if (sflag0 == 1) {
-        nlm = be.n_lm;
-        for (int k = t; k < nlm; k += nt) flag[k] = c.lm_solve[c.lm_order[k]] == 2 ? 0 : 1;
+        if (!LT) nlm = be.n_lm;
+        for (int k = t; k < nlm; k += nt) flag[k] = c.lm_solve[ord[k]] == 2 ? 0 : 1;
         __syncthreads();
-        lm_compact(c, flag, offs, scratch);
+        compact();
     }
+    stage_back();
     if (t == 0) {
         for (int k = 0; k < 9; k++) { be.last_R[k] = be.Rs[W][k]; be.last_R0[k] = be.Rs[0][k]; }
         for (int k = 0; k < 3; k++) { be.last_P[k] = be.Ps[W][k]; be.last_P0[k] = be.Ps[0][k]; }

@@ -9,6 +9,20 @@
 // macro
 #define PI_CH 8
 #define PREINT_MANY_LDS_DOUBLES (PI_CH * (225 + 270))
+// dynamic LDS of be_marg.  The overlay region holds, one after the other: the whitened IMU Jacobian, (gj) the packed frame blocks G_j, T1 / A_mr, the
+// lower 16x16 tiles of the new prior (Cholesky for its constant term) and the F / V of a chunk of the pre-integration merge in the window slide
+__host__ __device__ static inline size_t marg_overlay_bytes(int nprior, int W, bool gj) {
+    const size_t nbq = ((size_t)nprior + 15) >> 4, tiles = nbq * (nbq + 1) / 2 * 2048, t1 = (size_t)2 * nprior * 15 * 8, pi = (size_t)PREINT_MANY_LDS_DOUBLES * 8;
+    size_t m = tiles > t1 ? tiles : t1;
+    m = m > pi ? m : pi;
+    if (gj && (size_t)W * 210 * 8 > m) m = (size_t)W * 210 * 8;
+    return ((m + 15) & ~(size_t)15) + 64;
+}
+// be_marg with the reduced system resident in LDS (VIO_MARG_LDS): [overlay | A (15 + n)^2 | b 15 + n | b_r n]; the window slide's landmark tables
+// (MARG_LM_TABLES arrays of NL integers) take A's place afterwards
+#define MARG_LM_TABLES 6
+__host__ __device__ static inline size_t marg_resident_doubles(int nprior) { const size_t q = (size_t)nprior + 15; return q * q + q + (size_t)nprior; }
+__host__ __device__ static inline size_t marg_resident_lds_bytes(int nprior, int W) { return marg_overlay_bytes(nprior, W, true) + marg_resident_doubles(nprior) * 8; }
 // dynamic LDS of fast_cell (fe_kernels.hip) for a rw x rh region: tile (pitch up to rw + 6) + score plane + NMS ballot words
 static inline size_t fast_lds_bytes(int rw, int rh) {
     return (size_t)(((rw + 6) * rh + 15) & ~15) + (size_t)((rw * rh + 15) & ~15) + (size_t)(((rw - 6) * (rh - 6) + 63) / 64 + 2) * 8 + 16;
@@ -58,7 +72,8 @@ template <bool EXCALIB> __global__ void be_ingest_kernel(Batch B, const uint16_t
 __global__ void be_stage_relative_r_kernel(int n, const double *corres6, double *R9, int *detail8);
 __global__ void be_solve_kernel(Batch B);
 __global__ void be_solve_kernel_512(Batch B);
-__global__ void be_marg_kernel(Batch B);
+__global__ void be_marg_kernel(Batch B);       // reduced system, frame blocks and landmark tables in LDS (vio_batch::marg_lds)
+__global__ void be_marg_hbm_kernel(Batch B);   // the same stage with them in HBM scratch: windows whose system does not fit, VIO_MARG_LDS = 0
 __global__ void be_marg_exact_kernel(Batch B);
 // phased solver (be_phased.h)
 __global__ void ps_setup_kernel(Batch B);

@@ -569,7 +569,8 @@ int launch_backend(vio_batch *h, vio_batch::Group &g, const uint16_t *d_depth, c
         h->state_pending = true;
     }
     if (C.MX > 0) be_marg_exact_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);   // vio_config.marg_exact (parity instrument)
-    else be_marg_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);  // marginalisation + window slide (be_finish is fused into it)
+    else if (h->marg_lds) be_marg_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);  // marginalisation + window slide (be_finish is fused into it)
+    else be_marg_hbm_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);
     if (prof) PEV(h, 11);
     HIPCHK(hipGetLastError());
     return VIO_OK;
@@ -808,6 +809,7 @@ static void read_knobs(vio_batch *h) {
     // (VIO_SERIAL_THREADS = 1024 is gone: the 1024-thread build of ps_serial had been producing wrong steps since round 4 -- 2.1 iterations per solve,
     // metres of ATE, found in round 6 by a knob sweep -- while bench.py's `valid` only looked at the solver flags; never the default, no test ran it)
     h->marg_threads = std::min(512, std::max(64, env_int("VIO_MARG_THREADS", h->marg_threads) & ~63));
+    h->marg_lds = env_int("VIO_MARG_LDS", 1) != 0;
     h->B.flags = env_int("VIO_FLAGS", 0);
 }
 
@@ -917,11 +919,23 @@ static int size_launches(vio_batch *h) {
         h->lds_marg = std::max(std::max((size_t)nbq * (nbq + 1) / 2 * 2048, (size_t)2 * C.NPRIOR * 15 * 8), (size_t)PREINT_MANY_LDS_DOUBLES * 8) + 64;   // (the last: F / V of a chunk of the pre-integration merge)  // lower 16x16 tiles of the new prior (Cholesky for its constant term); before that T1 and A_mr
         if (C.MXL > 0) h->lds_marg = std::max(h->lds_marg, marg_exact_lds_bytes(C.MXL));
         if (C.MX > 0) h->lds_marg = std::max(h->lds_marg, (size_t)7 * 512 * 8 + 64);   // sym_eig_hbm's vectors (SYM_EIG_HBM_LDS_DOUBLES)
+        {
+            // VIO_MARG_LDS: the reduced system (A, b, b_r) behind the overlay region, where the kernel's static LDS leaves room for it and the
+            // landmark tables of the window slide fit in A's place; otherwise (and for marg_exact) the HBM form with today's request
+            hipFuncAttributes fa;
+            int cap = 0;
+            if (hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) != hipSuccess || cap <= 0) cap = 160 * 1024;
+            const size_t want = marg_resident_lds_bytes(C.NPRIOR, C.W);
+            h->marg_lds = h->marg_lds && C.MX == 0 && (size_t)MARG_LM_TABLES * C.NL * 4 <= marg_resident_doubles(C.NPRIOR) * 8 &&
+                          hipFuncGetAttributes(&fa, (const void *)be_marg_kernel) == hipSuccess && fa.sharedSizeBytes + want <= (size_t)cap;
+            if (h->marg_lds) h->lds_marg = want;
+        }
         h->lds_factor = C.NPRIOR <= 96 ? (size_t)C.NPRIOR * (C.NPRIOR | 1) * 8 + 64 : 64;  // on-demand eigen-decomposition (vio_get_prior)
         (void)raise_lds_limit((const void *)be_prior_factor_kernel, h->lds_factor);
     }
     (void)raise_lds_limit((const void *)be_marg_kernel, (size_t)(h->lds_marg));
     (void)raise_lds_limit((const void *)be_marg_exact_kernel, (size_t)(h->lds_marg));
+    (void)raise_lds_limit((const void *)be_marg_hbm_kernel, (size_t)(h->lds_marg));
     const bool excalib = C.c.estimate_extrinsic == 2;
     const void *ingest = excalib ? (const void *)be_ingest_kernel<true> : (const void *)be_ingest_kernel<false>;
     (void)raise_lds_limit(ingest, ingest_lds_bytes(C, excalib));
@@ -929,7 +943,7 @@ static int size_launches(vio_batch *h) {
     (void)raise_lds_limit((const void *)fe_select_kernel, (size_t)(h->lds_select));
     (void)raise_lds_limit((const void *)fe_add_kernel, (size_t)(h->lds_add));
     (void)raise_lds_limit((const void *)fe_fast_kernel, (size_t)(h->lds_fast));
-    bool fits = lds_fits(C.MX > 0 ? (const void *)be_marg_exact_kernel : (const void *)be_marg_kernel, h->lds_marg, "be_marg") &&
+    bool fits = lds_fits(C.MX > 0 ? (const void *)be_marg_exact_kernel : h->marg_lds ? (const void *)be_marg_kernel : (const void *)be_marg_hbm_kernel, h->lds_marg, "be_marg") &&
                 lds_fits(ingest, ingest_lds_bytes(C, excalib), "be_ingest") &&
                 lds_fits((const void *)fe_select_kernel, h->lds_select, "fe_select") && lds_fits((const void *)fe_add_kernel, h->lds_add, "fe_add") &&
                 lds_fits((const void *)fe_fast_kernel, h->lds_fast, "fe_fast");

@@ -141,6 +141,9 @@ struct vio_batch {
     // with 6 instead of 8 wavefronts (256 VGPRs each) two SIMDs per CU keep half of their register file free and the LK wavefronts can
     // co-reside (be_marg 1.4 -> 1.6 ms, fe_lk 0.77 -> 0.60 ms; the front-end is the longer of the two, so the step gets shorter).
     int be_threads = 512, marg_threads = 384;
+    // VIO_MARG_LDS (default 1): be_marg keeps its reduced system, frame blocks and landmark tables in LDS where they fit (size_launches decides: W = 10
+    // does, W = 12 and up do not); false = be_marg_hbm_kernel, the HBM scratch of rounds 1 - 6
+    bool marg_lds = true;
     // VIO_SOLVE_MODE: 0 = persistent kernel (one workgroup per sequence for the whole solve), 1 = phased solver (be_phased.h, default)
     int solve_mode = 1;
     bool asm_a_occ4 = false;          // VIO_ASM_A_OCC=4
