@@ -464,6 +464,12 @@ int64_t vio_debug_snapshot_staging_bytes(vio_batch *h);
 /* The layout table: entry i of the table as (name, kind: 1 state / 0 scratch, bytes per sequence, offset inside the device part or -1);
  * returns the number of entries (i out of range: that count, nothing written). */
 int vio_debug_snapshot_layout(vio_batch *h, int i, char *name64, int32_t *kind, int64_t *bytes_per_seq, int64_t *blob_offset);
+/* test / measurement helper of VIO_PREINT_AHEAD (be_ingest): how often, since vio_create, be_ingest took over a frame's IMU
+ * pre-integration computed ahead of it beside the previous frame's marginalisation (out2[0]) and how often it was handed such a result but
+ * integrated itself (out2[1]: the sequence was not in steady state, the frame was not processed, or an input had changed), summed over the
+ * sequences; per_seq (may be NULL): the same pair for every sequence, [S][2].  All zero on a handle created with VIO_PREINT_AHEAD=0.
+ * Waits for all work of the handle. */
+int vio_debug_preint_ahead(vio_batch *h, int64_t *out2, int64_t *per_seq);
 /* FeatureTracker public vectors after readImage (estimator_nodelet.cpp:337-343): returns count */
 int vio_get_tracks(vio_batch *h, int seq, int cap, int32_t *ids, int32_t *track_cnt, float *cur_pts_xy, float *cur_un_pts_xy,
                    float *pts_velocity_xy);

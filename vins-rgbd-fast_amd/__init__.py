@@ -689,6 +689,14 @@ class VioBatch:
         self._chk(self.L.vio_get_bound_stats(self.h, int(seq), o.ctypes.data), "vio_get_bound_stats")
         return tuple(int(x) for x in o)
 
+    def preint_ahead_stats(self, per_seq=False):
+        """(used, declined): frames for which be_ingest took over the IMU pre-integration computed ahead of it (VIO_PREINT_AHEAD) / was handed
+        one but integrated itself, summed over the sequences since creation; per_seq=True: an [S][2] array instead.  Waits for the handle."""
+        o, ps = np.zeros(2, np.int64), np.zeros((self.S, 2), np.int64)
+        self.L.vio_debug_preint_ahead.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.L.vio_debug_preint_ahead(self.h, o.ctypes.data, ps.ctypes.data), "vio_debug_preint_ahead")
+        return ps if per_seq else (int(o[0]), int(o[1]))
+
     def ex_calibration(self, seq=0, history=False):
         """estimate_extrinsic = 2 (InitialEXRotation): dict(state = 2 calibrating / 1 calibrated / 0 not a mode-2 handle, pairs, success_frame
         (frames_processed after the frame that succeeded, -1 while calibrating), ric (3 x 3, current estimate), sv (4 singular values of the last

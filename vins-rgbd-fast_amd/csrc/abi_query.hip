@@ -516,6 +516,24 @@ int vio_debug_seq(vio_batch *h, int seq, int *out16) {
     return VIO_OK;
 }
 
+// debug: be_ingest's use of the records of be_preint_ahead_kernel (PreAhead::used / declined), summed and per sequence
+int vio_debug_preint_ahead(vio_batch *h, int64_t *out2, int64_t *per_seq) {
+    VIO_ENTER(h, VIO_NO_SEQ, true);
+    if (!out2) return VIO_EINVAL;
+    out2[0] = out2[1] = 0;
+    if (per_seq) memset(per_seq, 0, (size_t)h->S * 2 * sizeof(int64_t));
+    if (!h->d_ahead) return VIO_OK;
+    const size_t head = offsetof(PreAhead, pre);   // (the counters precede the pre-integration image)
+    std::vector<unsigned char> rec(head);
+    for (int s = 0; s < h->S; s++) {
+        HIPCHK(hipMemcpy(rec.data(), h->d_ahead + s, head, hipMemcpyDeviceToHost));
+        const PreAhead *r = (const PreAhead *)rec.data();
+        out2[0] += (int64_t)r->used; out2[1] += (int64_t)r->declined;
+        if (per_seq) { per_seq[2 * s] = (int64_t)r->used; per_seq[2 * s + 1] = (int64_t)r->declined; }
+    }
+    return VIO_OK;
+}
+
 // debug: accumulated in-kernel phase ticks (100 MHz) of sequence 0; reset != 0 clears them
 int vio_debug_phases(vio_batch *h, float *out128, int reset) {
     VIO_ENTER(h, VIO_NO_SEQ, true);

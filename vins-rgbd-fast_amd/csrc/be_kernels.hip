@@ -614,6 +614,139 @@ __device__ void repropagate_window(Ctx &c, PreWork &pw) {
         }
 }
 
+// ====================================================================================================== the frame's IMU, ahead of be_ingest
+// getIMUInterval (estimator.cpp:1910-1942) on a sequence's ring, by one wavefront: head = the first sample later than prevT from head0 on, k = the
+// first one at or after curTime: 64 samples per trip, one lane each (the two scalar loops were a chain of dependent loads, ~14 of them per frame at
+// 200 Hz).  Every lane returns the same head and k.
+__device__ __forceinline__ void imu_interval_search(const double *it, int NIMU, int cnt_all, double prevT, double curTime, int head0, int &head, int &k) {
+    const int t = threadIdx.x & 63;
+    head = head0;
+    for (;;) {
+        const int idx = head + t;
+        const bool pass = idx < cnt_all && it[idx % NIMU] <= prevT;
+        const unsigned long long stop = ~__ballot(pass);
+        if (stop) { head += __ffsll((long long)stop) - 1; break; }
+        head += 64;
+    }
+    k = head;
+    for (;;) {
+        const int idx = k + t;
+        const bool pass = idx < cnt_all && it[idx % NIMU] < curTime;
+        const unsigned long long stop = ~__ballot(pass);
+        if (stop) { k += __ffsll((long long)stop) - 1; break; }
+        k += 64;
+    }
+}
+// PreAhead::in, entry i, as the sequence holds it now
+__device__ __forceinline__ const double *ahead_in_ptr(const BeSeq &be, int W, int i) {
+    return i < 3 ? be.acc_0 + i : i < 6 ? be.gyr_0 + (i - 3) : i < 9 ? be.Ps[W] + (i - 6) : i < 12 ? be.Vs[W] + (i - 9) : i < 21 ? be.Rs[W] + (i - 12)
+         : i < 24 ? be.Bas[W] + (i - 21) : i < 27 ? be.Bgs[W] + (i - 24) : be.g + (i - 27);
+}
+__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+
+// What be_ingest does between its feature part and the triangulation for a steady-state frame (NON_LINEAR, full window), on copies: the interval search,
+// the fresh pre-integration of slot W and its n propagate steps with processIMU's world-state recursion as the side job -- through the very device
+// functions be_ingest calls, so that the bits are the same.  Its inputs are final once the previous frame's solve has ended (the window slide of
+// be_marg never writes slot W of Ps / Vs / Rs / Bas / Bgs, nor acc_0 / gyr_0 / g / td / prevTime / imu_head), so it runs beside that frame's be_marg.
+// It reads the sequence and writes nothing but its record.
+__global__ __launch_bounds__(256) void be_preint_ahead_kernel(Batch B, const double *stamps, PreAhead *ahead) {
+    const int s = blockIdx.x + B.s0, t = threadIdx.x;
+    Ctx c = make_ctx(B, s);
+    const DevCfg &C = *B.cfg;
+    const vio_calibration &K = *c.K;
+    const BeSeq &be = *c.be;
+    const int W = c.W;
+    PreAhead &rec = ahead[s];
+    __shared__ int sh_i[8];
+    __shared__ double sh_in[30];
+    __shared__ PreWork pw;
+    __shared__ double pi_fv[PREINT_MANY_LDS_DOUBLES];
+    const double *it = B.imu_t + (size_t)s * C.NIMU;
+    const double *ia = B.imu_acc + (size_t)s * C.NIMU * 3, *ig = B.imu_gyr + (size_t)s * C.NIMU * 3;
+    const double stamp = stamps[s], prevT = be.prevTime, curTime = stamp + be.td;
+    const int head0 = be.imu_head, cnt_all = be.imu_count;
+    if (t < 30) sh_in[t] = *ahead_in_ptr(be, W, t);
+    if (t == 0) {
+        bool ok = C.c.use_imu && W > 0 && be.solver_flag == 1 && be.frame_count == W && !be.rebooted && be.first_imu && be.initFirstPoseFlag;
+        ok = ok && head0 >= 0 && cnt_all > head0 && cnt_all - head0 <= C.NIMU;   // (a longer backlog: be_ingest moves the head and flags the overrun)
+        ok = ok && curTime <= it[(cnt_all - 1) % C.NIMU];                          // the IMU reaches the frame (estimator.cpp:178-183)
+        sh_i[0] = ok;
+        if (!ok) rec.valid = 0;
+    }
+    __syncthreads();
+    if (!sh_i[0]) return;
+    if (t < 64) {
+        int head, k;
+        imu_interval_search(it, C.NIMU, cnt_all, prevT, curTime, head0, head, k);
+        sh_i[6] = head; sh_i[7] = k;
+    }
+    PreInt &P = rec.pre;
+    if (t == 0) {
+        rec.valid = 0;   // until the record is complete
+        rec.stamp = stamp; rec.cur_time = curTime; rec.prev_time = prevT;
+        rec.imu_head = head0; rec.imu_count = cnt_all;
+        rec.noise[0] = K.acc_n; rec.noise[1] = K.gyr_n; rec.noise[2] = K.acc_w; rec.noise[3] = K.gyr_w;
+        bf::preint_init(P, ld3(sh_in), ld3(sh_in + 3), ld3(sh_in + 21), ld3(sh_in + 24));
+    }
+    if (t >= 64 && t < 94) rec.in[t - 64] = sh_in[t - 64];
+    __syncthreads();
+    const int head = sh_i[6], n = sh_i[7] - head + 1;
+    preint_load(P, pw);
+    const PreintRing ring = {it, ia, ig, head, C.NIMU, prevT, curTime, n};
+    WorldStep ws = {ld3(sh_in), ld3(sh_in + 3), ld3(sh_in + 6), ld3(sh_in + 9), ldm(sh_in + 12), ld3(sh_in + 21), ld3(sh_in + 24), ld3(sh_in + 27)};
+    preint_propagate_many<true>(P, pw, K, n, ring, ws, true, pi_fv);
+    if (t == 64) { st3(rec.out, ws.P); st3(rec.out + 3, ws.V); stm(rec.out + 6, ws.R); st3(rec.out + 15, ws.a0); st3(rec.out + 18, ws.g0); }
+    preint_store(P, pw);
+    if (t == 0) { rec.head = head; rec.k = sh_i[7]; rec.n = n; rec.valid = 1; }
+}
+
+// be_ingest's side: is `rec` the result of exactly the integration this frame would run (every input bit for bit, slot W's pre-integration P the
+// untouched fresh one)?  Then file it -- what the integration would have written, no byte more (the tails of the slot's sample buffers keep their stale
+// content, as they do today) -- and return true.  Every thread of the block, uniform result.
+__device__ __forceinline__ bool preint_ahead_take(Ctx &c, PreAhead &rec, double stamp, double curTime, int *sh_flag) {
+    const int t = threadIdx.x, nt = blockDim.x, W = c.W;
+    BeSeq &be = *c.be;
+    const vio_calibration &K = *c.K;
+    PreInt &P = c.pre[be.pre_idx[W]];
+    if (t < 64) {
+        bool ok = true;
+        if (t < 30) ok = same_bits(rec.in[t], *ahead_in_ptr(be, W, t));
+        else if (t < 42) { const int i = t - 30; ok = same_bits(P.lin_acc[i], rec.in[i < 6 ? i : i + 15]); }   // lin_acc lin_gyr lin_ba lin_bg, contiguous
+        else if (t == 42) ok = same_bits(rec.noise[0], K.acc_n) && same_bits(rec.noise[1], K.gyr_n) && same_bits(rec.noise[2], K.acc_w) && same_bits(rec.noise[3], K.gyr_w);
+        else if (t == 43) ok = same_bits(rec.stamp, stamp) && same_bits(rec.cur_time, curTime) && same_bits(rec.prev_time, be.prevTime);
+        else if (t == 44) ok = rec.valid == 1 && rec.imu_head == be.imu_head && rec.imu_count == be.imu_count && P.valid && P.n_buf == 0 && be.first_imu && be.initFirstPoseFlag;
+        const bool all = __ballot(ok) == ~0ull;
+        if (t == 0) *sh_flag = all;
+    }
+    __syncthreads();
+    if (!*sh_flag) return false;
+    const int n = rec.n, m = min(n, VIO_IMU_SLOT_CAP);
+    const PreInt &Q = rec.pre;
+    {
+        double *d = (double *)&P;
+        const double *q = (const double *)&Q;
+        for (int i = t; i < (int)(offsetof(PreInt, dt_buf) / sizeof(double)); i += nt) d[i] = q[i];
+        for (int i = t; i < m; i += nt) P.dt_buf[i] = Q.dt_buf[i];
+        for (int i = t; i < 3 * m; i += nt) { (&P.acc_buf[0][0])[i] = (&Q.acc_buf[0][0])[i]; (&P.gyr_buf[0][0])[i] = (&Q.gyr_buf[0][0])[i]; }
+    }
+    if (t >= 64 && t < 85) {
+        const int i = t - 64;
+        double *d = i < 3 ? be.Ps[W] + i : i < 6 ? be.Vs[W] + (i - 3) : i < 15 ? be.Rs[W] + (i - 6) : i < 18 ? be.acc_0 + (i - 15) : be.gyr_0 + (i - 18);
+        *d = rec.out[i];
+    }
+    if (t == 0) {
+        P.n_buf = Q.n_buf;
+        be.imu_head = rec.k;   // that last sample is not popped
+        be.n_imu_frame = n;
+        be.imu_frame_head = rec.head;
+        be.prevTime = curTime;
+        if (n > VIO_IMU_SLOT_CAP) be.overflow |= 2;
+        rec.used++;
+    }
+    __syncthreads();
+    return true;
+}
+
 // ====================================================================================================== be_ingest
 // src.ids == NULL: the feature map packaged by the last vio_track / front-end of vio_feed (B.obs_id / B.obs / FeSeq);
 // otherwise a caller-supplied map (vio_process_obs = Estimator::processImage(image, header), estimator.h:46): n_obs[s] < 0 skips s.
@@ -650,7 +783,11 @@ __global__ __launch_bounds__(256) void be_ingest_kernel(Batch B, const uint16_t 
         if (be.imu_count - be.imu_head > C.NIMU) { be.imu_head = be.imu_count - C.NIMU; be.overflow |= 16; }  // samples overwritten in the ring before they were consumed
     }
     __syncthreads();
-    if (ext ? ext_n <= 0 : (fe.n_forw < 0 || !fe.publish_ok)) return;
+    PreAhead *const ahead = src.ahead ? src.ahead + s : nullptr;   // a record that is not taken over counts as declined, whatever the reason
+    if (ext ? ext_n <= 0 : (fe.n_forw < 0 || !fe.publish_ok)) {
+        if (ahead && t == 0) ahead->declined++;
+        return;
+    }
     // ---- IMU availability (estimator.cpp:178-183, :1882-1888)
     const double *it = B.imu_t + (size_t)s * C.NIMU;
     const double *ia = B.imu_acc + (size_t)s * C.NIMU * 3, *ig = B.imu_gyr + (size_t)s * C.NIMU * 3;
@@ -659,7 +796,7 @@ __global__ __launch_bounds__(256) void be_ingest_kernel(Batch B, const uint16_t 
         bool have = be.imu_count > be.imu_head;
         double back_t = have ? it[(be.imu_count - 1) % C.NIMU] : -1e300;
         if (!(have && curTime <= back_t)) {
-            if (t == 0) be.status_code = VIO_NEED_IMU;
+            if (t == 0) { be.status_code = VIO_NEED_IMU; if (ahead) ahead->declined++; }
             return;
         }
     }
@@ -772,31 +909,19 @@ __global__ __launch_bounds__(256) void be_ingest_kernel(Batch B, const uint16_t 
         __syncthreads();
     }
     PH(108);
-    // ---- getIMUInterval + processIMU (estimator.cpp:185-200, 1910-1942, 118-154); VO mode (USE_IMU == 0) has neither
-    if (cfg.use_imu && t < 64) {
-        // head = the first sample later than prevTime, k = the first one at or after curTime: 64 samples per trip, one lane each (the two scalar
-        // loops were a chain of dependent loads, ~14 of them per frame at 200 Hz)
-        const int cnt_all = be.imu_count;
-        const double prevT = be.prevTime;
-        int head = be.imu_head;
-        for (;;) {
-            const int idx = head + t;
-            const bool pass = idx < cnt_all && it[idx % C.NIMU] <= prevT;
-            const unsigned long long stop = ~__ballot(pass);
-            if (stop) { head += __ffsll((long long)stop) - 1; break; }
-            head += 64;
-        }
-        int k = head;
-        for (;;) {
-            const int idx = k + t;
-            const bool pass = idx < cnt_all && it[idx % C.NIMU] < curTime;
-            const unsigned long long stop = ~__ballot(pass);
-            if (stop) { k += __ffsll((long long)stop) - 1; break; }
-            k += 64;
-        }
+    // ---- getIMUInterval + processIMU (estimator.cpp:185-200, 1910-1942, 118-154); VO mode (USE_IMU == 0) has neither.  A steady-state frame whose
+    // interval be_preint_ahead_kernel has integrated already, from exactly these inputs, only files that result.
+    bool imu_here = cfg.use_imu;
+    if (ahead && imu_here) {
+        if (fc == W && fc != 0 && preint_ahead_take(c, *ahead, stamp, curTime, &sh_i[5])) imu_here = false;
+        else if (t == 0) ahead->declined++;
+    }
+    if (imu_here && t < 64) {
+        int head, k;
+        imu_interval_search(it, C.NIMU, be.imu_count, be.prevTime, curTime, be.imu_head, head, k);
         sh_i[6] = head; sh_i[7] = k;
     }
-    if (cfg.use_imu && t == 0) {
+    if (imu_here && t == 0) {
         const int head = sh_i[6], k = sh_i[7];
         sh_i[0] = head;          // first sample of the interval
         sh_i[1] = k - head + 1;  // number of samples incl. the first one with t >= curTime
@@ -815,7 +940,7 @@ __global__ __launch_bounds__(256) void be_ingest_kernel(Batch B, const uint16_t 
         }
     }
     __syncthreads();
-    if (cfg.use_imu) {
+    if (imu_here) {
         int head = sh_i[0], n = sh_i[1];
         PreInt &P = c.pre[be.pre_idx[fc]];
         if (t == 0) {

@@ -60,6 +60,7 @@ __global__ void fe_select_kernel(Batch B);
 __global__ void fe_fast_kernel(Batch B);
 __global__ void fe_fast_stage_kernel(const uint8_t *img, int W, GridRect r, uint32_t *out, int cap, int *count);
 __global__ void fe_add_kernel(Batch B, int gate);
+struct PreAhead;
 // feature-map source of be_ingest: ids == NULL selects the map packaged on the device by the front-end
 struct IngestSrc {
     const int *n_obs;       // [S] entries per sequence (< 0: skip the sequence)
@@ -67,7 +68,28 @@ struct IngestSrc {
     const double *obs;      // [S][cap][7] x y z u v vx vy
     const double *stamps;   // [S] header stamps
     int cap;
+    PreAhead *ahead;        // [S] (indexed by sequence) results of be_preint_ahead_kernel for this frame, or NULL: be_ingest integrates the IMU itself
 };
+// One sequence's record of be_preint_ahead_kernel: the frame's IMU interval pre-integrated, and processIMU's world-state step taken, beside be_marg of
+// the previous frame.  A per-call buffer of the handle (vio_batch::d_ahead), not per-sequence state: it is in no table and in no snapshot.  be_ingest takes
+// the result over only where every input recorded here has, bit for bit, the value it would use itself; otherwise it integrates as ever.
+//   in      acc_0 gyr_0 Ps[W] Vs[W] Rs[W] Bas[W] Bgs[W] g   (acc_0 / gyr_0 / Bas[W] / Bgs[W] are also the fresh slot's lin_acc / lin_gyr / lin_ba / lin_bg)
+//   noise   acc_n gyr_n acc_w gyr_w of the sequence's calibration
+//   out     Ps[W] Vs[W] Rs[W] acc_0 gyr_0 after the interval
+//   pre     the pre-integration of slot W: everything up to the sample buffers, and the first min(n, VIO_IMU_SLOT_CAP) entries of those
+struct PreAhead {
+    double stamp, cur_time, prev_time;
+    double in[30], noise[4];
+    int imu_head, imu_count;   // BeSeq::imu_head / imu_count the interval search started from
+    int valid;                 // 0: nothing was computed (not steady state, ring overrun, the IMU does not reach cur_time yet)
+    int head, k, n;            // first sample of the interval, the first one at or after cur_time, their number (k - head + 1)
+    double out[21];
+    unsigned long long used, declined;   // frames of this sequence for which be_ingest took the record over / integrated itself although it was handed one
+    PreInt pre;
+};
+static_assert(offsetof(PreInt, dt_buf) == (VIO_PREINT_HDR + 225) * sizeof(double), "PreInt: what be_ingest takes over from a PreAhead whole");
+// S workgroups x 256 threads, on the front-end stream once the previous frame's solve has ended (its ev_solve); stamps: the call's [S] header stamps
+__global__ void be_preint_ahead_kernel(Batch B, const double *stamps, PreAhead *ahead);
 template <bool EXCALIB> __global__ void be_ingest_kernel(Batch B, const uint16_t *depth_base, size_t depth_stride, IngestSrc src);
 __global__ void be_stage_relative_r_kernel(int n, const double *corres6, double *R9, int *detail8);
 __global__ void be_solve_kernel(Batch B);

@@ -810,6 +810,7 @@ static void read_knobs(vio_batch *h) {
     // metres of ATE, found in round 6 by a knob sweep -- while bench.py's `valid` only looked at the solver flags; never the default, no test ran it)
     h->marg_threads = std::min(512, std::max(64, env_int("VIO_MARG_THREADS", h->marg_threads) & ~63));
     h->marg_lds = env_int("VIO_MARG_LDS", 1) != 0;
+    h->preint_ahead = env_int("VIO_PREINT_AHEAD", 1) != 0;
     h->B.flags = env_int("VIO_FLAGS", 0);
 }
 
@@ -973,6 +974,7 @@ static int handle_init(vio_batch *h, int n_seq) {
     // the input buffers of a call: not per-sequence state, not in the table
     VIO_TRY(dev_alloc(h, &h->d_stamps, S)); VIO_TRY(dev_alloc(h, &h->d_modes, S)); VIO_TRY(dev_alloc(h, &h->d_rrel, S * 9)); VIO_TRY(dev_alloc(h, &h->d_r9, 16));
     VIO_TRY(dev_alloc(h, &h->d_in_n, S)); VIO_TRY(dev_alloc(h, &h->d_in_stamps, S)); VIO_TRY(dev_alloc(h, &h->d_in_ids, S * NP)); VIO_TRY(dev_alloc(h, &h->d_in_obs, S * NP * 7));
+    if (h->preint_ahead && C.c.use_imu) VIO_TRY(dev_alloc(h, &h->d_ahead, S));   // (zeroed: no record is valid, the counters start at 0)
     B.gW = h->hc.W; B.gP = h->hc.P; B.gLW = h->hc.LW; B.gNL = h->hc.NL; B.gNP = h->hc.NP; B.gNRES = h->hc.NRES; B.gNPRIOR = h->hc.NPRIOR; B.gMX = h->hc.MX;
     HIPCHK(hipMemcpy(B.cfg, &h->hc, sizeof(DevCfg), hipMemcpyHostToDevice));
     VIO_TRY(create_groups(h));
@@ -1231,8 +1233,20 @@ int vio_feed_modes(vio_batch *h, const uint8_t *gray, const uint16_t *depth_mm, 
         VIO_TRY(launch_frontend(h, g, dg, 1, 1, modes ? h->d_modes : nullptr, nullptr));
         if (g.s0 == 0) HIPCHK(hipEventRecord(h->ev[1], g.fe_stream));
         if (!on_device) VIO_TRY(note_stage_read(h, g.ev_rd_gray[g.flip], g.have_rd_gray[g.flip], g.fe_stream));
+        IngestSrc src = kTrackerMap;
+        if (h->d_ahead && g.have_solve_ev) {
+            // VIO_PREINT_AHEAD: this frame's IMU interval, behind the front-end kernels (the grey image is released to the upload path above, before
+            // the wait) and beside be_marg of the previous frame: everything it reads is final when that frame's solve has ended.  With tracker lag 0
+            // the stream has waited for that event already (fe_wait).  be_ingest follows it through ev_fe, and so does the next writer of the IMU rings
+            // (flush_imu_frontend waits for ev_ingest / ev_solve of this frame, flush_imu_backend for ev_fe).
+            if (h->tracker_lag) HIPCHK(hipStreamWaitEvent(g.fe_stream, g.ev_solve, 0));
+            Batch Bg = h->B;
+            Bg.s0 = g.s0;
+            be_preint_ahead_kernel<<<g.n, 256, 0, g.fe_stream>>>(Bg, h->d_stamps, h->d_ahead);
+            src.ahead = h->d_ahead;
+        }
         VIO_TRY(be_wait(g));
-        VIO_TRY(launch_backend(h, g, dd, kTrackerMap));
+        VIO_TRY(launch_backend(h, g, dd, src));
         if (!on_device) {
             VIO_TRY(note_stage_read(h, g.ev_rd_depth[g.flip], g.have_rd_depth[g.flip], g.stream));
             g.flip ^= 1;

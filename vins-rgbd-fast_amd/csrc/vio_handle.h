@@ -144,6 +144,11 @@ struct vio_batch {
     // VIO_MARG_LDS (default 1): be_marg keeps its reduced system, frame blocks and landmark tables in LDS where they fit (size_launches decides: W = 10
     // does, W = 12 and up do not); false = be_marg_hbm_kernel, the HBM scratch of rounds 1 - 6
     bool marg_lds = true;
+    // VIO_PREINT_AHEAD (default 1): vio_feed pre-integrates a frame's IMU interval on the front-end stream beside be_marg of the previous frame
+    // (be_preint_ahead_kernel) and be_ingest takes the result over where its inputs still hold; false = never launched, be_ingest integrates itself.
+    // d_ahead: the [S] records, a per-call buffer like d_stamps (allocated at vio_create where the knob is on and the handle has an IMU)
+    bool preint_ahead = true;
+    PreAhead *d_ahead = nullptr;
     // VIO_SOLVE_MODE: 0 = persistent kernel (one workgroup per sequence for the whole solve), 1 = phased solver (be_phased.h, default)
     int solve_mode = 1;
     bool asm_a_occ4 = false;          // VIO_ASM_A_OCC=4
@@ -300,7 +305,7 @@ inline void stream_release(vio_batch *h, hipStream_t &s) { if (s) { disown(h->st
 // When in doubt an array is state.  The ORDER of the entries is the snapshot format (VIO_SNAPSHOT_FORMAT): do not reorder.
 // A count of 0 means "this configuration has no such array": nothing is allocated, the pointer stays null (code tests for that: B.fuse needs
 // B.pairpart, DevCfg::exc selects the calibrating ingest) and the row reports 0 bytes.  The per-call input buffers of a handle (d_stamps,
-// d_modes, d_rrel, d_r9, d_odo, d_in_*) are not per-sequence state and are not in the table.
+// d_modes, d_rrel, d_r9, d_odo, d_in_*, d_ahead) are not per-sequence state and are not in the table.
 // Entry forms (the walkers define h, B = h->B, C = h->hc, D = the dimensions below, S = sequences):
 //   SEQ(kind, member, count)             Batch member B.member, row named after the member, S * count elements
 //   ROW(kind, name, lvalue, count, n)    a per-sequence row over an array that is not a plain Batch member; n elements are allocated in all
