@@ -358,8 +358,11 @@ int vio_get_imu_rate_odometry(vio_batch *h, const double *since, int cap, int32_
  * relo_frame_local_index among the matches) and computes the drift outputs (:1034-1056); otherwise nothing happens, like upstream.
  * relo_Pose borrows the six tangent columns of the extrinsic in the reduced system: when ESTIMATE_EXTRINSIC has opened the extrinsic it is
  * held constant in the ONE solve that carries the factors and refined again from the next solve on (DESIGN.md deviation 15: below a
- * millimetre against the joint optimisation).  Limits of this build: IMU mode and the phased solver; on the persistent solver (windows
- * beyond its range) the request is dropped and the frame carries overflow flag 64. */
+ * millimetre against the joint optimisation).  Limits of this build: IMU mode and the phased solver.  On the persistent solver (windows
+ * beyond its range, VIO_SOLVE_MODE=0) and on a handle with use_imu = 0 (VO mode) a latched request is dropped by the next solve of the
+ * sequence: that frame carries overflow flag 64, vio_get_relo reports pending = 0 and 0 factors, and the frame is otherwise computed as if
+ * the request had never been made.  A request made before the first optimisation copies an identity pose (the reference copies from an
+ * array it has not written yet); it waits for the solve that ends the initialisation, which carries its factors. */
 int vio_set_relo_frame(vio_batch *h, int seq, double frame_stamp, int frame_index, int n, const double *match_points, const double *relo_t3,
                        const double *relo_r9);
 /* what pubRelocalization and the pose graph read after that solve (visualization.cpp:454-538): out30 = relo_relative_t(3),

@@ -379,6 +379,9 @@ void eval_projection(const Config &c, const double *pi, const double *pj, const 
 // ------------------------------------------------------------------ Estimator
 Estimator::Estimator(const Config &c) : cfg(c), W(c.window_size) {
     for (int i = 0; i <= MAXW; i++) pre_integrations[i] = nullptr;
+    // upstream never writes para_Pose before the first optimization(), and setReloFrame copies from it whatever solver_flag is: a request made
+    // during the initialisation would read indeterminate memory.  Here, as in the HIP state, the array starts as identity poses.
+    for (int i = 0; i <= MAXW; i++) for (int k = 0; k < 7; k++) para_Pose[i][k] = k == 6 ? 1.0 : 0.0;
     {
         const char *dv = std::getenv("OVIO_DEVIATIONS");
         deviations = dv ? std::atoi(dv) : 0;

@@ -1578,10 +1578,13 @@ __device__ __forceinline__ void solve_prologue(const Batch &B, Ctx &c, Params &X
         else ex_active = 0;
         int td_active = cfg.use_imu && cfg.estimate_td && !(v0 < 0.2);   // no td block without the IMU (estimator.cpp:1204)
         sh_i[0] = ex_active; sh_i[1] = td_active;
-        int relo_on = be.relo_info && be.solver_flag == 1;
-        if (relo_on && !allow_relo) {
-            // relocalisation on the persistent solver (windows beyond the phased solver's range) is not supported: the request is dropped and
-            // the frame flagged (overflow bit 64); optimization() without relocalization_info is what runs
+        // (no solver_flag test, like optimization(): the solve that ends the static initialisation runs with solver_flag still 0 here, and
+        // solve_epilogue consumes the request after it)
+        int relo_on = be.relo_info;
+        if (relo_on && (!allow_relo || !cfg.use_imu)) {
+            // relocalisation on the persistent solver (windows beyond the phased solver's range) and in VO mode (solve_epilogue's VO branch
+            // neither moves relo_Pose nor consumes the request) is not supported: the request is dropped and the frame flagged (overflow
+            // bit 64); optimization() without relocalization_info is what runs
             relo_on = 0; be.relo_info = 0; be.overflow |= 64;
         } else if (relo_on && ex_active) {
             // DEVIATION 15: relo_Pose borrows the six tangent columns of the extrinsic in the reduced system, so the extrinsic is held constant
@@ -3094,6 +3097,9 @@ __global__ void be_set_relo_kernel(Batch B, int seq, const double *par) {
             be.relo_local = i;
             be.relo_info = 1;
             for (int j = 0; j < 7; j++) be.relo_Pose[j] = be.para_Pose[i][j];
+            // before the first optimization() nothing has written para_Pose (upstream copies indeterminate memory there): the state holds
+            // zeros, and the copy is the identity pose, as in the oracle
+            if (be.relo_Pose[3] == 0 && be.relo_Pose[4] == 0 && be.relo_Pose[5] == 0 && be.relo_Pose[6] == 0) be.relo_Pose[6] = 1.0;
         }
 }
 
@@ -3133,7 +3139,7 @@ __global__ __launch_bounds__(512) void be_prior_factor_kernel(Batch B, int seq) 
         if ((nt >> 6) <= 8) sym_eig_tridiag_mt(Ag, n, ldj, ev_d, ev_e, ev_g, ev_part);
         else sym_eig_tridiag(Ag, n, ldj, ev_d, ev_e, ev_g, sred);
         if (t == 0) be.dbg[5] = (int)(VIO_CLOCK() - tj0);
-        tridiag_ql_wave(Ag, n, ldj, ev_d, ev_e);
+        tridiag_ql_wave<3>(Ag, n, ldj, ev_d, ev_e);   // (n = 136 at W = 20: three rows per lane)
     }
     if (t == 0) be.dbg[6] = (int)(VIO_CLOCK() - tj0);
     Vv = As;  // eigenvectors overwrite the matrix

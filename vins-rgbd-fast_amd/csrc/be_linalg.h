@@ -591,7 +591,9 @@ __device__ __forceinline__ void sym_eig_tridiag_mt(double *V, int n, int ld, dou
     __syncthreads();
 }
 
-// implicit QL on the tridiagonal (d, e) with eigenvector accumulation into V; one wavefront, lanes own rows k, k+64, ...
+// implicit QL on the tridiagonal (d, e) with eigenvector accumulation into V; one wavefront, lanes own rows k, k+64, ...: NR of them,
+// n <= 64 NR (NR = 3: the prior of a 20-frame window, n = 136, in be_prior_factor_kernel)
+template <int NR = 2>
 __device__ __forceinline__ void tridiag_ql_wave(double *V, int n, int ld, double *d, double *e) {
     const int lane = threadIdx.x & 63;
     if (threadIdx.x < 64) {
@@ -626,16 +628,21 @@ __device__ __forceinline__ void tridiag_ql_wave(double *V, int n, int ld, double
                     f += h;
                     p = d[m];
                     double c = 1.0, c2 = 1.0, c3 = 1.0, el1 = e[l + 1], s = 0.0, s2 = 0.0;
-                    const int r0 = lane < n ? lane : 0, r1 = lane + 64 < n ? lane + 64 : r0;  // n <= 128; duplicates write equal values
-                    double car0 = V[r0 * ld + m], car1 = V[r1 * ld + m];
+                    int rw[NR];   // n <= 64 NR; duplicates write equal values
+                    double car[NR], vi[NR];
+#pragma unroll
+                    for (int q = 0; q < NR; q++) { rw[q] = lane + 64 * q < n ? lane + 64 * q : (q ? rw[0] : 0); car[q] = V[rw[q] * ld + m]; }
                     // software pipeline: e[i-1], d[i-1] and the next V column are fetched before this rotation's stores
                     double ei = e[m - 1], di = d[m - 1];
-                    double vi0 = V[r0 * ld + m - 1], vi1 = V[r1 * ld + m - 1];
+#pragma unroll
+                    for (int q = 0; q < NR; q++) vi[q] = V[rw[q] * ld + m - 1];
                     for (int i = m - 1; i >= l; i--) {
                         c3 = c2; c2 = c; s2 = s;
                         const int in = i > l ? i - 1 : i;
                         const double ei_n = e[in], di_n = d[in];
-                        const double vn0 = V[r0 * ld + in], vn1 = V[r1 * ld + in];
+                        double vn[NR];
+#pragma unroll
+                        for (int q = 0; q < NR; q++) vn[q] = V[rw[q] * ld + in];
                         g = c * ei;
                         h = c * p;
                         const double rr2 = p * p + ei * ei;
@@ -647,15 +654,13 @@ __device__ __forceinline__ void tridiag_ql_wave(double *V, int n, int ld, double
                         p = c * di - s * g;
                         double d_ip1 = h + s * (c * g + s * di);
                         if (lane == 0) { e[i + 1] = e_ip1; d[i + 1] = d_ip1; }  // read again only after the sweep's fence
-                        // rows lane and lane+64 of V: the rotated column i is carried in registers to the next rotation
-                        V[r0 * ld + i + 1] = s * vi0 + c * car0;
-                        V[r1 * ld + i + 1] = s * vi1 + c * car1;
-                        car0 = c * vi0 - s * car0;
-                        car1 = c * vi1 - s * car1;
-                        ei = ei_n; di = di_n; vi0 = vn0; vi1 = vn1;
+                        // rows lane, lane + 64, ... of V: the rotated column i is carried in registers to the next rotation
+#pragma unroll
+                        for (int q = 0; q < NR; q++) { V[rw[q] * ld + i + 1] = s * vi[q] + c * car[q]; car[q] = c * vi[q] - s * car[q]; vi[q] = vn[q]; }
+                        ei = ei_n; di = di_n;
                     }
-                    V[r0 * ld + l] = car0;
-                    V[r1 * ld + l] = car1;
+#pragma unroll
+                    for (int q = 0; q < NR; q++) V[rw[q] * ld + l] = car[q];
                     p = -s * s2 * c3 * el1 * e[l] / dl1;
                     __builtin_amdgcn_wave_barrier();
                     if (lane == 0) { e[l] = s * p; d[l] = c * p; }
@@ -2002,7 +2007,10 @@ template <int RB = 4>
 __device__ __forceinline__ void matvec_pass_2range(const double *M, int ld, int nrows, int n, int n0, int e0, int ne, const double *u, const double *v,
                                                    double *out_col, double *out_row, double *part) {
     if (n0 + ne <= 128) matvec_pass_2range_t<2, RB>(M, ld, nrows, n, n0, e0, ne, u, v, out_col, out_row, part);
-    else matvec_pass_t<6>(M, ld, nrows, n, u, v, out_col, out_row, part);  // larger windows: dense pass
+    // W = 20 with the extrinsic / td columns open or lent to relo_Pose: 6 * 21 + 7 = 133 columns.  Never the dense pass over all n columns: the
+    // assembly writes a landmark row only around the two ranges, and the columns between them hold what be_marg, which uses the rows as scratch,
+    // left there -- not zeros
+    else matvec_pass_2range_t<3, RB>(M, ld, nrows, n, n0, e0, ne, u, v, out_col, out_row, part);
 }
 template <int RB = 4>
 __device__ __forceinline__ void matvec_pass(const double *M, int ld, int nrows, int n, const double *u, const double *v, double *out_col, double *out_row,

@@ -1681,9 +1681,8 @@ __device__ __forceinline__ void ps_schur_body(const Batch &B, int s, int tile_in
 
 // Column sums out[a] = sum_k u[k] M[k][a] of the landmark rows, with the BITS of matvec_pass_2range / matvec_pass_t run by ps_serial's eight wavefronts:
 // wavefront w of this 256-thread block plays wavefronts w and w + 4 of that pass one after the other (rows k = w', w' + 8, ..., RB of them per trip,
-// accumulated in that order), then the eight partial sums are added in wavefront order.  Only the columns [0, n0) and [e0, e0 + ne) are walked (the
-// others of a landmark row are identically zero: the dense pass ps_serial falls back to beyond 128 such columns sums exact zeros there, so its result
-// is the same bits too); the partial rows are kept compact, 64 NC doubles each.
+// accumulated in that order), then the eight partial sums are added in wavefront order.  Only the columns [0, n0) and [e0, e0 + ne) are walked, as
+// in that pass (the columns between the ranges are not the solver's: ps_asm_a does not write them); the partial rows are kept compact, 64 NC doubles each.
 template <int NC, int RB>
 __device__ __forceinline__ void ps_colsum_as_eight_waves(const double *M, int ld, int nrows, int n, int n0, int e0, int ne, const double *u, double *out_col, double *part) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
