@@ -90,8 +90,7 @@ def hip_solo(P, name):
     return _hip[name]
 
 
-KNOBS = ("VIO_FUSE", "VIO_EVAL_RPT", "VIO_MARG_THREADS", "VIO_FORM_S", "VIO_GN_EXT", "VIO_ASM_B_MODE", "VIO_SOLVE_MODE", "VIO_FLAGS", "VIO_BE_THREADS",
-         "VIO_LINE_SEARCH")
+KNOBS = ("VIO_FUSE", "VIO_EVAL_RPT", "VIO_MARG_THREADS", "VIO_SOLVE_MODE", "VIO_FLAGS", "VIO_BE_THREADS", "VIO_LINE_SEARCH")
 # the sum_dt > 10 rule is written out once per solver path: the default two-kernel path (ps_eval / ps_asm_a) runs in every test above, the
 # fused evaluate + assemble kernel and the persistent fallback solver are chosen when the handle is created
 SOLVER_PATHS = {"fused": ({"VIO_FUSE": "1"}, 1), "fallback": ({"VIO_SOLVE_MODE": "0"}, 0)}

@@ -157,83 +157,6 @@ def test_alternative_kernel_configurations_agree(P, monkeypatch, env):
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(estimate_extrinsic=1, estimate_td=1)])
-def test_mirrored_assembly_of_H_equals_the_entrywise_one(P, monkeypatch, kw):
-    """round 6: VIO_ASM_B_MODE = 2 forms only the entries a >= b of H and stores the mirror image too (half the index arithmetic and gathers of the
-    entrywise kernel; H's terms are symmetric source by source and added in the same order): the windows must be the same BITS as mode 0."""
-    cfg = P.canonical_config(**kw)
-    sc = vio_ct.synth_like(cfg)
-    monkeypatch.setenv("VIO_ASM_B_MODE", "0")
-    ref = _drive(P, cfg, sc, [60, 61, 62], 30)
-    ref_w = [ref.window(i).copy() for i in range(3)]
-    monkeypatch.setenv("VIO_ASM_B_MODE", "2")
-    alt = _drive(P, cfg, sc, [60, 61, 62], 30)
-    for i in range(3):
-        assert alt.status(i).solver_flag == 1 and alt.status(i).has_prior == 1
-        assert np.array_equal(alt.window(i).view(np.uint64), ref_w[i].view(np.uint64)), (i, float(np.abs(alt.window(i) - ref_w[i]).max()))
-
-
-@pytest.mark.parametrize("kw", [dict(), dict(estimate_extrinsic=1, estimate_td=1), dict(window_size=12), dict(window_size=20),
-                                dict(window_size=12, estimate_extrinsic=1, estimate_td=1), dict(window_size=20, estimate_extrinsic=1, estimate_td=1)])
-def test_schur_launch_forming_S_itself_equals_the_load_in_ps_serial(P, monkeypatch, kw):
-    """round 6: with VIO_FORM_S = 1 (the default) ps_asm_b_schur writes
-    S = Sp (H - U) Sp + mu D^2 itself -- the tiles the landmark rows touch by their Schur block, which sums their entries of H too, the others by the
-    thread that sums the entry -- and ps_serial only copies the tiles into LDS (W <= 10) or, with the Schur complement in HBM (ps_serial_big,
-    larger windows), skips its load of H and U altogether.  Same expressions on the same operands: the windows must be the
-    same BITS as with VIO_FORM_S = 0, with the extrinsic / td columns constant and variable (their tiles hold the padding rows beyond P)."""
-    cfg = P.canonical_config(**kw)
-    sc = vio_ct.synth_like(cfg)
-    n = cfg.window_size + 14
-    monkeypatch.setenv("VIO_FORM_S", "0")
-    ref = _drive(P, cfg, sc, [60, 61, 62], n)
-    ref_w = [ref.window(i).copy() for i in range(3)]
-    ref_it = [ref.status(i).iterations_total for i in range(3)]
-    monkeypatch.setenv("VIO_FORM_S", "1")
-    alt = _drive(P, cfg, sc, [60, 61, 62], n)
-    for i in range(3):
-        assert alt.status(i).solver_flag == 1 and alt.status(i).has_prior == 1
-        assert alt.status(i).iterations_total == ref_it[i] and ref_it[i] > n - cfg.window_size, (ref_it, alt.status(i).iterations_total)
-        assert np.array_equal(alt.window(i).view(np.uint64), ref_w[i].view(np.uint64)), (i, float(np.abs(alt.window(i) - ref_w[i]).max()))
-
-
-@pytest.mark.parametrize("kw", [dict(), dict(estimate_extrinsic=1, estimate_td=1), dict(window_size=20), dict(window_size=20, estimate_extrinsic=1, estimate_td=1)])
-def test_gauss_newton_rhs_formed_in_the_schur_launch_equals_ps_serials(P, monkeypatch, kw):
-    """round 6: with VIO_GN_EXT = 1 (the default) one more workgroup of the Schur launch forms Hpl^T (sl inv gls), the landmark term of the Gauss-Newton
-    right-hand side, playing ps_serial's eight wavefronts on four (ps_colsum_as_eight_waves: same rows per wavefront, same order of the partial
-    sums) -- on the two-range pass (W = 10; W = 20 with the extrinsic constant) and on its dense fallback (W = 20 with the extrinsic variable).
-    The windows must be the same BITS as with VIO_GN_EXT = 0."""
-    cfg = P.canonical_config(**kw)
-    sc = vio_ct.synth_like(cfg)
-    n = cfg.window_size + 14
-    monkeypatch.setenv("VIO_GN_EXT", "0")
-    ref = _drive(P, cfg, sc, [60, 61, 62], n)
-    ref_w = [ref.window(i).copy() for i in range(3)]
-    ref_it = [ref.status(i).iterations_total for i in range(3)]
-    monkeypatch.setenv("VIO_GN_EXT", "1")
-    alt = _drive(P, cfg, sc, [60, 61, 62], n)
-    for i in range(3):
-        assert alt.status(i).solver_flag == 1 and alt.status(i).has_prior == 1
-        assert alt.status(i).iterations_total == ref_it[i] and ref_it[i] > n - cfg.window_size, (ref_it, alt.status(i).iterations_total)
-        assert np.array_equal(alt.window(i).view(np.uint64), ref_w[i].view(np.uint64)), (i, float(np.abs(alt.window(i) - ref_w[i]).max()))
-
-
-@pytest.mark.parametrize("kw", [dict(), dict(estimate_extrinsic=1, estimate_td=1)])
-def test_block_pair_assembly_of_H_equals_the_entrywise_one(P, monkeypatch, kw):
-    """round 5: ps_asm_b sums H and the gradient by pairs of parameter blocks (scalar index decisions, mirrored upper triangle) instead of one
-    thread per entry; VIO_ASM_B_MODE = 0 keeps the entrywise kernel.  Same terms in the same order: the windows must be the same BITS, with the
-    extrinsic / td blocks constant (default) and variable."""
-    cfg = P.canonical_config(**kw)
-    sc = vio_ct.synth_like(cfg)
-    monkeypatch.setenv("VIO_ASM_B_MODE", "0")
-    ref = _drive(P, cfg, sc, [60, 61, 62], 30)
-    ref_w = [ref.window(i).copy() for i in range(3)]
-    monkeypatch.setenv("VIO_ASM_B_MODE", "1")
-    alt = _drive(P, cfg, sc, [60, 61, 62], 30)
-    for i in range(3):
-        assert alt.status(i).solver_flag == 1 and alt.status(i).has_prior == 1
-        assert np.array_equal(alt.window(i).view(np.uint64), ref_w[i].view(np.uint64)), (i, float(np.abs(alt.window(i) - ref_w[i]).max()))
-
-
-@pytest.mark.parametrize("kw", [dict(), dict(estimate_extrinsic=1, estimate_td=1)])
 def test_fused_evaluate_and_assemble_equals_the_two_kernel_path(P, monkeypatch, kw):
     """round 6: ps_evalf_kernel evaluates the residuals into LDS records and forms the frame-pair Gram blocks, the IMU blocks and the landmark
     rows from there (the rows double-buffered: a rejected candidate must not touch the current ones); VIO_FUSE = 0 keeps ps_eval + ps_asm_a with

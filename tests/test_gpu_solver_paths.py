@@ -1,6 +1,6 @@
 """Every solver path through the inverse-depth bound.  The non-default paths kept behind environment knobs (the fused evaluate + assemble
-kernel, VIO_FUSE; residuals per thread of the evaluation, VIO_EVAL_RPT; the marginalisation's thread count; the Schur-complement, Gauss-Newton
-and assembly variants; the streaming solver of windows beyond W = 10; the persistent fallback solver) are otherwise tested on the canonical
+kernel, VIO_FUSE; residuals per thread of the evaluation, VIO_EVAL_RPT; the marginalisation's thread count; the streaming solver of windows
+beyond W = 10; the persistent fallback solver) are otherwise tested on the canonical
 workload only, whose depth is valid everywhere: it never reaches the bound and never runs Ceres' projected line search (ps_ls_kernel).  Here
 they run the scenes of tests/test_gpu_depth_holes.py, where every solve is bounds-constrained, against the oracle with the bar the default path
 meets there: every clamp, bounded landmark, line-search trial and contraction counted equal (vio_get_bound_stats), the landmark tables equal
@@ -18,8 +18,7 @@ import vio_ct
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("VIO_FUSE", "VIO_EVAL_RPT", "VIO_MARG_THREADS", "VIO_FORM_S", "VIO_GN_EXT", "VIO_ASM_B_MODE", "VIO_SOLVE_MODE", "VIO_FLAGS",
-         "VIO_BE_THREADS", "VIO_LINE_SEARCH")
+KNOBS = ("VIO_FUSE", "VIO_EVAL_RPT", "VIO_MARG_THREADS", "VIO_SOLVE_MODE", "VIO_FLAGS", "VIO_BE_THREADS", "VIO_LINE_SEARCH")
 OVF_CALIB_FULL, OVF_DEVIATION = 128, 512   # vio_status.overflow_flags (include/vio_abi.h)
 
 
@@ -133,12 +132,10 @@ def test_solver_paths_meet_the_oracle_through_the_bound(P, runs, monkeypatch, en
         assert all(s.overflow_flags == 0 for s in h.stat), [s.overflow_flags for s in h.stat]
 
 
-@pytest.mark.parametrize("env,ref", [({"VIO_FUSE": "2"}, {"VIO_FUSE": "1"}), ({"VIO_FUSE": "3"}, {"VIO_FUSE": "1"}), ({"VIO_FORM_S": "0"}, {}),
-                                     ({"VIO_GN_EXT": "0"}, {}), ({"VIO_ASM_B_MODE": "0"}, {}), ({"VIO_ASM_B_MODE": "1"}, {})])
+@pytest.mark.parametrize("env,ref", [({"VIO_FUSE": "2"}, {"VIO_FUSE": "1"}), ({"VIO_FUSE": "3"}, {"VIO_FUSE": "1"})])
 def test_bit_identical_paths_stay_identical_through_the_bound(P, runs, monkeypatch, env, ref):
-    """The knobs whose tests in test_gpu_batch.py claim the same BITS on the canonical workload (fused chunk workgroups, S formed in the Schur
-    launch, the Gauss-Newton right-hand side there, the assembly modes of H) keep that claim on constrained solves: the window after every
-    frame to the bit and every bound / line-search count equal."""
+    """The knob whose test in test_gpu_batch.py claims the same BITS on the canonical workload (fused chunk workgroups) keeps that claim on
+    constrained solves: the window after every frame to the bit and every bound / line-search count equal."""
     _same_bits(runs.hip("bound", env, monkeypatch), runs.hip("bound", ref, monkeypatch))
 
 
@@ -182,11 +179,6 @@ def test_streaming_solver_meets_the_oracle_through_the_bound(P, runs, monkeypatc
     h = runs.hip(name, {}, monkeypatch)
     assert h.kind == 2
     _oracle_bar(runs, name, h)
-
-
-def test_schur_complement_formed_in_the_schur_launch_at_w20_through_the_bound(P, runs, monkeypatch):
-    """VIO_FORM_S = 0 against the default at W = 20 (test_schur_launch_forming_S_itself_equals_the_load_in_ps_serial's claim, constrained)"""
-    _same_bits(runs.hip("w20", {"VIO_FORM_S": "0"}, monkeypatch), runs.hip("w20", {}, monkeypatch))
 
 
 @pytest.mark.parametrize("env", [{"VIO_SOLVE_MODE": "0"}, {"VIO_FLAGS": "1"}])

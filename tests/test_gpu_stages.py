@@ -224,7 +224,7 @@ def test_imu_block_on_the_matrix_cores_matches_oracle(P, orc):
 @pytest.mark.parametrize("nb", [1, 2, 7, 11])
 def test_tile_cholesky_against_numpy(P, nb):
     """The dense solve of the reduced camera system (Ceres DENSE_SCHUR, estimator.cpp:1251-1263) through the LDS-tile Cholesky of
-    ps_serial (be_linalg.h chol_tiles / chol_backward_tiles: diagonal blocks by rank-1 updates on v_mfma_f64_16x16x4, panels as
+    ps_serial (be_linalg.h chol_tiles / chol_backward_tiles_wave: diagonal blocks by rank-1 updates on v_mfma_f64_16x16x4, panels as
     A M^T with M = L^-1 of the block) against numpy on a matrix with condition 1e6: the factor to 1e-11 of its largest entry, the
     solution to 1e-9 (cond x eps); a matrix that is not positive definite is reported, not factored."""
     n = 16 * nb
@@ -249,7 +249,7 @@ def test_tile_cholesky_against_numpy(P, nb):
 
 @pytest.mark.parametrize("nb", [12, 21, 24])
 def test_streaming_tile_cholesky_against_numpy_and_the_lds_path(P, nb):
-    """ps_serial_big's factorisation for windows beyond 10 keyframes (be_linalg.h chol_tiles_stream / chol_backward_tiles: the tiles stay in
+    """ps_serial_big's factorisation for windows beyond 10 keyframes (be_linalg.h chol_tiles_stream / chol_backward_tiles_wave: the tiles stay in
     HBM / L2, one block column at a time goes through LDS): against numpy at the sizes only it serves, and bit for bit against the
     LDS-resident factorisation (vio_stage_chol blocks = -7 forces the streaming path) where both apply -- the two share every arithmetic step."""
     def spd(n, seed):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Where the literal marginalisation (vio_config.marg_exact = 1) spends its time: per sequence and frame the size m of the marginalised block, the
-Jacobi sweeps (0 = the LDS-resident Householder + QL path) and the in-kernel ticks of the stages of marg_exact_finish (timers build).
+"""Where the literal marginalisation (vio_config.marg_exact = 1) spends its time: per sequence and frame the size m of the marginalised block
+and the in-kernel ticks of the stages of marg_exact_finish (timers build).
     python tools/marg_exact_probe.py [--seqs 16] [--frames 24]"""
 import os as _os
 _os.environ.setdefault("VIO_HIP_LIB", "timers")
@@ -50,16 +50,16 @@ def main():
         for s in range(S):
             L.vio_debug_seq(b.h, s, dbg.ctypes.data)
             if b.status(s).solver_flag == 1:
-                rows.append((f, s, dbg[4], dbg[0], dbg[2], dbg[3] / 100.0, dbg[7] / 100.0, dbg[8] / 100.0, dbg[9] / 100.0, dbg[10] / 100.0))
+                rows.append((f, s, dbg[4], dbg[2], dbg[3] / 100.0, dbg[7] / 100.0, dbg[8] / 100.0, dbg[9] / 100.0, dbg[10] / 100.0))
     r = np.array(rows)
-    print("frame seq m sweeps second_new | marg us | eig1 products eig2 prior (cumulative us)")
+    print("frame seq m second_new | marg us | eig1 products eig2 prior (cumulative us)")
     for row in rows[:: max(1, len(rows) // 60)]:
-        print("%3d %3d %4d %5d %d | %8.0f | %8.0f %8.0f %8.0f %8.0f" % row)
-    old = r[r[:, 4] == 0]
+        print("%3d %3d %4d %d | %8.0f | %8.0f %8.0f %8.0f %8.0f" % row)
+    old = r[r[:, 3] == 0]
     if len(old):
         print("MARGIN_OLD frames: m mean %.0f max %.0f; share with m <= 104: %.2f; marg us mean %.0f max %.0f" % (
-            old[:, 2].mean(), old[:, 2].max(), (old[:, 2] <= 104).mean(), old[:, 5].mean(), old[:, 5].max()))
-    print("all frames: marg us mean %.0f p90 %.0f max %.0f" % (r[:, 5].mean(), np.percentile(r[:, 5], 90), r[:, 5].max()))
+            old[:, 2].mean(), old[:, 2].max(), (old[:, 2] <= 104).mean(), old[:, 4].mean(), old[:, 4].max()))
+    print("all frames: marg us mean %.0f p90 %.0f max %.0f" % (r[:, 4].mean(), np.percentile(r[:, 4], 90), r[:, 4].max()))
 
 
 if __name__ == "__main__":

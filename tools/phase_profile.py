@@ -21,7 +21,7 @@ NAMES = {0: "vector2double", 1: "lm indexing", 2: "pair lists", 4: "evaluate(fir
          16: "marg prior", 17: "marg imu", 18: "marg proj eval", 19: "marg lm rows", 20: "marg frame blocks+rank update", 21: "marg 15x15 + reduce",
          22: "marg new prior + c0", 23: "marg keep data", 24: "  marg frame blocks (mfma)", 25: "  marg scatter", 27: "finish consistency check",
          48: "ser prepare_point", 49: "ser GN rhs (Hpl matvec)", 50: "ser tile load", 51: "ser cholesky", 52: "ser solves + back-subst", 53: "ser cauchy (H, Hpl matvec)",
-         54: "ser dogleg/model", 55: "ser candidate", 56: "  ser chol_solve_tiles", 57: "  ser finite check", 58: "  ser y vectors + Hpl matvec",
+         54: "ser dogleg/model", 55: "ser candidate", 56: "  ser chol_backward_tiles_wave", 57: "  ser finite check", 58: "  ser y vectors + Hpl matvec",
          59: "  chol panel (wave 0 view)", 60: "  chol diag + trailing (wave 0)", 61: "  chol barrier wait",
          62: "eval block 0 (prior)", 63: "eval block 1 (imu)", 14: "eval block 3 (256 projections)", 15: "eval accept",
          28: "finish slide states", 29: "finish slide landmarks", 30: "finish removeFailures + odom",

@@ -2296,37 +2296,34 @@ __device__ __forceinline__ void solve_body(const Batch &B, int s, int *scratch, 
 // marg_exact (vio_config): elimination of the marginalised block and the new prior exactly as MarginalizationInfo::marginalize does them
 // (marginalization_factor.cpp:270-315).  In: A (mq x mq over q = [md | n]) and b with NO landmark eliminated, the landmark coupling rows
 // Cl (F0 x ldc, columns indexed like q), d_l = c.Hll (J_l^T J_l), c.gl (J_l^T r).  Marginalised block: m = md + F0 = [pose 0, speed-bias 0
-// | inverse depths of the landmarks that start in frame 0] (md = 6 and F0 = 0 for MARGIN_SECOND_NEW).  Both eigen-decompositions are the
-// threshold Jacobi of jacobi_block (the oracle's om::sym_eig is the cyclic form of the same iteration) on matrices in HBM scratch.
+// | inverse depths of the landmarks that start in frame 0] (md = 6 and F0 = 0 for MARGIN_SECOND_NEW).  Both eigen-decompositions are Householder
+// tridiagonalisation + implicit QL: LDS-resident where the block fits (sym_eig_lds), on the matrix in HBM scratch otherwise (sym_eig_hbm).
 // LDS layout of the literal marginalisation's eigen-decompositions: the matrix (ld = n | 1: conflict-free column access), then d / e / g and
 // the per-wavefront partial sums of sym_eig_tridiag_mt.  Host side: marg_exact_lds_bytes (vio_abi.hip) sizes the launch with the same formula.
 #define MARG_EIG_AUX_DOUBLES (11 * EIG_LD)
 // Symmetric eigen-decomposition in LDS: A (n x n, ld) -> eigenvectors in place (columns), eigenvalues in d.  Householder tridiagonalisation over
 // the whole workgroup + implicit QL on one wavefront (be_linalg.h; the same pair be_prior_factor_kernel runs).  n <= 128 (tridiag_ql_wave).
-__device__ __forceinline__ void sym_eig_lds(double *Al, int n, int ld, double *aux, bool one_wave) {
+__device__ __forceinline__ void sym_eig_lds(double *Al, int n, int ld, double *aux) {
     double *d = aux, *e = aux + EIG_LD, *g = aux + 2 * EIG_LD, *part = aux + 3 * EIG_LD;
-    if (one_wave) sym_eig_tridiag(Al, n, ld, d, e, g, part);   // one wavefront, wave-level ordering only (the others wait at its final barrier)
-    else sym_eig_tridiag_mt(Al, n, ld, d, e, g, part);
+    sym_eig_tridiag_mt(Al, n, ld, d, e, g, part);
     tridiag_ql_wave(Al, n, ld, d, e);
 }
 // The SECOND half of MarginalizationInfo::marginalize (marginalization_factor.cpp:293-315), literally: saes2(A), S = eigenvalues > 1e-8,
 // linearized_jacobians = S^1/2 V^T, linearized_residuals = S^-1/2 V^T b, and from them what the solver consumes (J^T J, J^T r, |r|^2).
-// Ar (n x n, HBM) / br (n) = the reduced system.  LDS-resident Householder + implicit QL when n <= MXL, else Jacobi sweeps over HBM scratch
-// (scrA: n x n for the symmetrised matrix, scrV: n x n for the eigenvectors).  Returns the sweep count of the fallback (0 = LDS path).
+// Ar (n x n, HBM) / br (n) = the reduced system.  Householder + implicit QL, LDS-resident when n <= MXL, else on HBM scratch (scrA: n x n for the
+// symmetrised matrix, which its eigenvectors replace).
 // Not inlined: its own register allocation, one copy in the kernel for both literal modes (marg_exact 1 and 2).
-__device__ __noinline__ int marg_literal_prior(const Ctx &c, BeSeq &be, const double *Ar, const double *br, int n, double *scrA, double *scrV, double *sred,
-                                               unsigned char *smem) {
+__device__ __noinline__ void marg_literal_prior(const Ctx &c, BeSeq &be, const double *Ar, const double *br, int n, double *scrA, double *sred) {
     const int t = threadIdx.x, nt = blockDim.x;
     const double eps = 1e-8;
     extern __shared__ __attribute__((aligned(16))) unsigned char marg_dyn_lds[];
     __shared__ double ev2[EIG_LD], vb2[EIG_LD];
-    int sw2 = 0;
     if (n <= c.C->MXL) {
         const int ld = n | 1;
         double *Al = (double *)marg_dyn_lds, *aux = Al + (size_t)n * ld;
         for (int w = t; w < n * n; w += nt) { const int i = w / n, j = w - i * n; Al[i * ld + j] = 0.5 * (Ar[i * n + j] + Ar[j * n + i]); }
         __syncthreads();
-        sym_eig_lds(Al, n, ld, aux, c.C->eig_one_wave != 0);   // SelfAdjointEigenSolver<MatrixXd> saes2(A) (:298)
+        sym_eig_lds(Al, n, ld, aux);   // SelfAdjointEigenSolver<MatrixXd> saes2(A) (:298)
         for (int k = t; k < n; k += nt) {
             const double ev = aux[k];
             double vb = 0;
@@ -2351,17 +2348,13 @@ __device__ __noinline__ int marg_literal_prior(const Ctx &c, BeSeq &be, const do
             c.prior_r[a] = sacc;
         }
     } else {
-        double *cs = (double *)smem, *sn = cs + 256;
-        int *pp = (int *)(sn + 256), *qq = pp + 256;
-        double *As = scrA, *V2 = scrV;
+        double *As = scrA;
         for (int w = t; w < n * n; w += nt) { const int i = w / n, j = w - i * n; As[w] = 0.5 * (Ar[i * n + j] + Ar[j * n + i]); }
         __syncthreads();
-        // round 6: Householder + implicit QL on the matrix where it lies (sym_eig_hbm) instead of cyclic Jacobi sweeps over HBM (VIO_MARG_EIG_JACOBI = 1)
-        const bool hbm_ql = !c.C->eig_jacobi;
-        if (hbm_ql) { sym_eig_hbm(As, n, n, (double *)marg_dyn_lds, sred); V2 = As; }
-        else sw2 = jacobi_block(As, V2, n, n, cs, sn, pp, qq, sred);
+        sym_eig_hbm(As, n, n, (double *)marg_dyn_lds, sred);   // Householder + implicit QL on the matrix where it lies: the eigenvectors replace it
+        const double *V2 = As;
         for (int k = t; k < n; k += nt) {
-            ev2[k] = hbm_ql ? ((const double *)marg_dyn_lds)[k] : As[k * n + k];
+            ev2[k] = ((const double *)marg_dyn_lds)[k];
             double vb = 0;
             for (int i = 0; i < n; i++) vb += V2[i * n + k] * br[i];
             vb2[k] = vb;
@@ -2395,29 +2388,25 @@ __device__ __noinline__ int marg_literal_prior(const Ctx &c, BeSeq &be, const do
     const double c0 = block_sum(acc, sred);
     __syncthreads();
     if (t == 0) be.prior_c0 = c0;
-    return sw2;
 }
 
-__device__ void marg_exact_finish(const Ctx &c, BeSeq &be, double *A, const double *b, int md, int mq, int n, const double *Cl, int ldc, int F0,
-                                  bool second_new, double *sred, unsigned char *smem) {
+// Not inlined, like marg_literal_prior: inlined into marg_body the kernel spills 111 VGPRs, with its own register allocation none.
+__device__ __noinline__ void marg_exact_finish(const Ctx &c, BeSeq &be, double *A, const double *b, int md, int mq, int n, const double *Cl, int ldc, int F0,
+                                  bool second_new, double *sred) {
     const int t = threadIdx.x, nt = blockDim.x;
     const double eps = 1e-8;
     const int MX = c.C->MX, m = md + F0;
-    double *Emm = c.margE, *EV = Emm + (size_t)MX * MX, *Einv = EV + (size_t)MX * MX, *ET1 = Einv + (size_t)MX * MX;
+    double *Emm = c.margE, *Einv = Emm + 2 * (size_t)MX * MX, *ET1 = Einv + (size_t)MX * MX;   // (A_mm, which its eigenvectors replace; a free block; A_mm^+; A_rm A_mm^+)
     // the dynamic LDS of this kernel, declared here so that the eigen-solver below is compiled for ds_* accesses (a pointer handed down
     // through two calls would be flat); same base address as the caller's smem
     extern __shared__ __attribute__((aligned(16))) unsigned char marg_dyn_lds[];
-    double *cs = (double *)smem, *sn = cs + 256;
-    int *pp = (int *)(sn + 256), *qq = pp + 256;
     // Amm = 0.5 (Amm + Amm^T) (:276); the landmark-landmark block is diagonal (an inverse depth only meets itself)
     auto amm = [&](int i, int j) -> double {
         if (i < md && j < md) return 0.5 * (A[i * mq + j] + A[j * mq + i]);
         if (i >= md && j >= md) return i == j ? c.Hll[i - md] : 0.0;
         return Cl[(size_t)((i >= md ? i : j) - md) * ldc + (i >= md ? j : i)];
     };
-    // The first eigen-decomposition (saes(Amm), :281) runs LDS-resident when the block fits (m <= MXL): Householder + implicit QL instead of
-    // Jacobi sweeps over HBM (round 5); the second one lives in marg_literal_prior.
-    int sw1 = 0;
+    // The first eigen-decomposition (saes(Amm), :281) runs LDS-resident when the block fits (m <= MXL); the second one lives in marg_literal_prior.
     double *Ar = c.margV, *br = c.vec;
     const long long tx0 = VIO_CLOCK();   // (timers build only: dbg[7..10] = ticks to the end of eig 1 / the Schur products / eig 2 / the prior; tools/marg_exact_probe.py)
     if (m <= c.C->MXL) {
@@ -2425,7 +2414,7 @@ __device__ void marg_exact_finish(const Ctx &c, BeSeq &be, double *A, const doub
         double *Al = (double *)marg_dyn_lds, *aux = Al + (size_t)m * ld;
         for (int w = t; w < m * m; w += nt) { const int i = w / m, j = w - i * m; Al[i * ld + j] = amm(i, j); }
         __syncthreads();
-        sym_eig_lds(Al, m, ld, aux, c.C->eig_one_wave != 0);
+        sym_eig_lds(Al, m, ld, aux);
         if (VIO_TIMERS && t == 0) be.dbg[7] = (int)(VIO_CLOCK() - tx0);
         // Amm_inv = V diag(lambda > eps ? 1 / lambda : 0) V^T (:281-283); 1 / lambda once per column
         for (int k = t; k < m; k += nt) { const double ev = aux[k]; aux[EIG_LD + k] = ev > eps ? 1.0 / ev : 0.0; }
@@ -2439,35 +2428,24 @@ __device__ void marg_exact_finish(const Ctx &c, BeSeq &be, double *A, const doub
     } else {
         for (int w = t; w < m * m; w += nt) { const int i = w / m, j = w - i * m; Emm[w] = amm(i, j); }
         __syncthreads();
-        if (!c.C->eig_jacobi) {
-            // round 6: Householder + implicit QL on the matrix where it lies (be_linalg.h sym_eig_hbm; 23 ms at m = 185 against 50 - 100 ms of Jacobi sweeps)
-            double *ewk = (double *)marg_dyn_lds;
-            sym_eig_hbm(Emm, m, m, ewk, sred);
-            if (VIO_TIMERS && t == 0) be.dbg[7] = (int)(VIO_CLOCK() - tx0);
-            for (int k = t; k < m; k += nt) { const double ev = ewk[k]; ewk[SYM_EIG_HBM_MAX + k] = ev > eps ? 1.0 / ev : 0.0; }
-            __syncthreads();
-            for (int w = t; w < m * m; w += nt) {   // Amm_inv = V diag(lambda > eps ? 1 / lambda : 0) V^T: rows i and j of V, sixteen columns per trip
-                const int i = w / m, j = w - i * m;
-                const double *vi = Emm + (size_t)i * m, *vj = Emm + (size_t)j * m;
-                double sacc = 0;
-                for (int k0 = 0; k0 < m; k0 += 16) {
-                    double a[16], b[16];
-#pragma unroll
-                    for (int u = 0; u < 16; u++) { const int k = min(k0 + u, m - 1); a[u] = vi[k]; b[u] = vj[k]; }
-#pragma unroll
-                    for (int u = 0; u < 16; u++) if (k0 + u < m) sacc += a[u] * b[u] * ewk[SYM_EIG_HBM_MAX + k0 + u];
-                }
-                Einv[w] = sacc;
-            }
-        } else {
-        sw1 = jacobi_block(Emm, EV, m, m, cs, sn, pp, qq, sred);
+        // Householder + implicit QL on the matrix where it lies (be_linalg.h sym_eig_hbm; 23 ms at m = 185)
+        double *ewk = (double *)marg_dyn_lds;
+        sym_eig_hbm(Emm, m, m, ewk, sred);
         if (VIO_TIMERS && t == 0) be.dbg[7] = (int)(VIO_CLOCK() - tx0);
-        for (int w = t; w < m * m; w += nt) {
+        for (int k = t; k < m; k += nt) { const double ev = ewk[k]; ewk[SYM_EIG_HBM_MAX + k] = ev > eps ? 1.0 / ev : 0.0; }
+        __syncthreads();
+        for (int w = t; w < m * m; w += nt) {   // Amm_inv = V diag(lambda > eps ? 1 / lambda : 0) V^T: rows i and j of V, sixteen columns per trip
             const int i = w / m, j = w - i * m;
+            const double *vi = Emm + (size_t)i * m, *vj = Emm + (size_t)j * m;
             double sacc = 0;
-            for (int k = 0; k < m; k++) { const double ev = Emm[(size_t)k * m + k]; if (ev > eps) sacc += EV[(size_t)i * m + k] * EV[(size_t)j * m + k] / ev; }
+            for (int k0 = 0; k0 < m; k0 += 16) {
+                double a[16], b[16];
+#pragma unroll
+                for (int u = 0; u < 16; u++) { const int k = min(k0 + u, m - 1); a[u] = vi[k]; b[u] = vj[k]; }
+#pragma unroll
+                for (int u = 0; u < 16; u++) if (k0 + u < m) sacc += a[u] * b[u] * ewk[SYM_EIG_HBM_MAX + k0 + u];
+            }
             Einv[w] = sacc;
-        }
         }
     }
     __syncthreads();
@@ -2507,10 +2485,10 @@ __device__ void marg_exact_finish(const Ctx &c, BeSeq &be, double *A, const doub
     }
     __syncthreads();
     if (VIO_TIMERS && t == 0) be.dbg[8] = (int)(VIO_CLOCK() - tx0);
-    // second eigen-decomposition and the prior (:293-315); A is free from here on (the fallback's eigenvector scratch)
-    const int sw2 = marg_literal_prior(c, be, Ar, br, n, c.margW, A, sred, smem);
+    // second eigen-decomposition and the prior (:293-315)
+    marg_literal_prior(c, be, Ar, br, n, c.margW, sred);
     if (VIO_TIMERS && t == 0) be.dbg[9] = (int)(VIO_CLOCK() - tx0);
-    if (t == 0) { be.dbg[0] = sw1 * 100 + sw2; be.dbg[2] = second_new ? 1 : 0; be.dbg[4] = m; }
+    if (t == 0) { be.dbg[0] = 0; be.dbg[2] = second_new ? 1 : 0; be.dbg[4] = m; }
     if (VIO_TIMERS && t == 0) be.dbg[10] = (int)(VIO_CLOCK() - tx0);
 }
 
@@ -2534,7 +2512,7 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
     if (second_new && !(be.has_prior && be.prior_present[W - 1])) return;
     // marg_exact: MarginalizationInfo::marginalize followed literally (marginalization_factor.cpp:281-315) -- the full m x m block of
     // pose 0, speed-bias 0 AND the landmarks that start in frame 0 goes through one truncated eigen-decomposition, and the new prior is
-    // rebuilt from the truncated factors of the reduced system.  A parity instrument (one workgroup, Jacobi sweeps in HBM), not the hot path.
+    // rebuilt from the truncated factors of the reduced system.  A parity instrument (one workgroup), not the hot path.
     const bool exact = EXACT && cfg.marg_exact == 1 && c.margE != nullptr;
     // marg_exact = 2 (round 5): the literal algorithm with its first eigen-decomposition replaced by a CERTIFIED inverse.  A_mm^+ of the
     // reference (:281-283) equals A_mm^-1 whenever no eigenvalue of A_mm is at or below the 1e-8 cut; this mode eliminates the marginalised
@@ -2899,7 +2877,7 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
     }
     if (VIO_TIMERS && s == 0 && t == 0 && !second_new) B.timings[31] += 1.0f;
     PH(20);
-    if (exact) marg_exact_finish(c, be, A, b, md, mq, n, c.Hpl, c.LW, F0x, second_new, sred, smem_marg);
+    if (exact) marg_exact_finish(c, be, A, b, md, mq, n, c.Hpl, c.LW, F0x, second_new, sred);
     else {
     // ---- eliminate the m-block (md x md) with a truncated eigen-decomposition
     for (int w = t; w < md * md; w += nt) { int i = w / md, j = w - i * md; A15[w] = 0.5 * (A[i * mq + j] + A[j * mq + i]); }
@@ -3001,8 +2979,8 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
             if (!certified) be.dbg[12] += 1;
         }
         __syncthreads();
-        const int sw2 = marg_literal_prior(c, be, Ar, br, n, c.margW, A, sred, smem_marg);
-        if (t == 0) { be.dbg[0] = sw2; be.dbg[2] = second_new ? 1 : 0; be.dbg[4] = md; }
+        marg_literal_prior(c, be, Ar, br, n, c.margW, sred);
+        if (t == 0) { be.dbg[0] = 0; be.dbg[2] = second_new ? 1 : 0; be.dbg[4] = md; }
     } else {
     // ---- the new prior, kept as the quadratic form the solver consumes: A = sym(A_r), b = b_r, c0 = b^T A^+ b.
     // The reference factors A = V S V^T, drops eigenvalues <= 1e-8 and stores J = S^1/2 V^T, r = S^-1/2 V^T b

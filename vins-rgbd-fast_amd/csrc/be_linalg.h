@@ -945,55 +945,6 @@ __device__ __noinline__ void sym_eig_hbm(double *V, int n, int ld, double *wk, d
     if (tm && t == 0) { const long long n_ = (long long)wall_clock64(); tm[3] = (float)(n_ - tm0); }
 }
 
-__device__ bool chol_block(double *A, int n, int ld, int *sh_flag) {
-    const int t = threadIdx.x, nt = blockDim.x;
-    if (t == 0) *sh_flag = 1;
-    __syncthreads();
-    for (int j = 0; j < n; j++) {
-        if (t == 0) {
-            double d = A[j * ld + j];
-            if (!(d > 0.0) || !isfinite(d)) *sh_flag = 0; else A[j * ld + j] = sqrt(d);
-        }
-        __syncthreads();
-        if (!*sh_flag) return false;
-        double l = A[j * ld + j];
-        for (int i = j + 1 + t; i < n; i += nt) A[i * ld + j] /= l;
-        __syncthreads();
-        int m = n - j - 1;
-        for (int w = t; w < m * m; w += nt) {
-            int r = w / m, cc = w - r * m;
-            if (cc > r) continue;
-            int i = j + 1 + r, k = j + 1 + cc;
-            A[i * ld + k] -= A[i * ld + j] * A[k * ld + j];
-        }
-        __syncthreads();
-    }
-    return true;
-}
-// solve L L^T x = b with one wavefront (lanes own strided entries of x held in LDS xs)
-__device__ void chol_solve_wave(const double *L, int n, int ld, double *xs) {
-    const int t = threadIdx.x;
-    if (t < 64) {
-        for (int j = 0; j < n; j++) {
-            double xj = xs[j] / L[j * ld + j];
-            __builtin_amdgcn_wave_barrier();
-            if (t == 0) xs[j] = xj;
-            for (int i = j + 1 + t; i < n; i += 64) xs[i] -= L[i * ld + j] * xj;
-            __builtin_amdgcn_wave_barrier();
-            __threadfence_block();
-        }
-        for (int j = n - 1; j >= 0; j--) {
-            double xj = xs[j] / L[j * ld + j];
-            __builtin_amdgcn_wave_barrier();
-            if (t == 0) xs[j] = xj;
-            for (int i = t; i < j; i += 64) xs[i] -= L[j * ld + i] * xj;
-            __builtin_amdgcn_wave_barrier();
-            __threadfence_block();
-        }
-    }
-    __syncthreads();
-}
-
 // ------------------------------------------------------------------ dense linear algebra on the scaled system
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 #define VIO_LWMAX 336  // >= LW for W = 20
@@ -1248,45 +1199,6 @@ __device__ __forceinline__ void chol_diag_tile(double *D, double *dinv16, int *s
         if (kb < 3) {
             acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-xk, xk, acc, 0, 0, 0);
             fcc = __builtin_amdgcn_mfma_f64_16x16x4f64(-xk, ek, fcc, 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int j = lk + 4 * q;
-        if (li >= j) D[(li << 4) + (j ^ li)] = lcol[q];          // L[li][j]
-        else D[(li << 4) + (j ^ li)] = mrow[q];                   // M[j][li], li < j, at (row li, column j)
-    }
-    if (!ok && lane == 0) *sh_flag = 0;
-    WAVE_SYNC();
-}
-// the rank-1 form of rounds 2 / 3 (one MFMA pair per pivot), kept for the harness (tools/chol_bench.py micro modes compare the two)
-__device__ __forceinline__ void chol_diag_tile_rank1(double *D, double *dinv16, int *sh_flag) {
-    const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
-    // acc = the symmetric tile S; fcc = F = E^T where E starts as the identity "panel" below the block: eliminating S from
-    // [[S, I], [I, 0]] leaves E = L^-T, i.e. the finished column j of E is row j of M = L^-1 (the panel operation applied to the identity).
-    // In the transposed form row j of F sits in the lanes lk == j % 4 like row j of S, so its update is the same kind of rank-1 MFMA.
-    v4f64 acc, fcc;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int row = lk + 4 * r;
-        acc[r] = D[(row << 4) + (li ^ row)];     // (diagonal tiles are stored complete: both triangles, bitwise symmetric)
-        fcc[r] = row == li ? 1.0 : 0.0;
-    }
-    bool ok = true;
-    double lcol[4], mrow[4];
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const double ajj = bcast_lane(acc[j >> 2], j + 16 * (j & 3));   // S[j][j]: lane li = j, lk = j % 4, register j / 4
-        ok = ok && (ajj > 0.0) && isfinite(ajj);
-        const double rl = rsqrt(ajj);
-        const bool own = lk == (j & 3);
-        const double lj = own ? acc[j >> 2] * rl : 0.0;    // L[li][j] in the k-slot j % 4, zeros in the other three
-        const double ej = own ? fcc[j >> 2] * rl : 0.0;    // M[j][li]
-        if (own) { lcol[j >> 2] = lj; mrow[j >> 2] = ej; }
-        if (lane == j + 16 * (j & 3)) dinv16[j] = rl;
-        if (j < 15) {
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-lj, lj, acc, 0, 0, 0);
-            fcc = __builtin_amdgcn_mfma_f64_16x16x4f64(-lj, ej, fcc, 0, 0, 0);
         }
     }
 #pragma unroll
@@ -1609,36 +1521,9 @@ __device__ __forceinline__ bool chol_tiles_stream(double *G, int nb, double *col
 }
 
 // backward half of the solve: L^T x = y (y from the forward substitution that rode along with chol_tiles).  The diagonal blocks are
-// applied as x_p = M_p^T b_p with M = L^-1 from the strictly upper triangle of the factored tile (chol_diag_tile).
-__device__ __forceinline__ void chol_backward_tiles(const double *T, int nb, double *xs, const double *dinv) {
-    const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6;
-    for (int p = nb - 1; p >= 0; p--) {
-        if (wave == 0) {
-            const double *D = T + ((size_t)(p * (p + 1) / 2 + p) << 8);
-            double x = 0;
-            if (lane < 16) {
-                const int c = lane;
-#pragma unroll
-                for (int k = 0; k < 16; k++) x += (k > c ? D[(c << 4) + (k ^ c)] : (k == c ? dinv[16 * p + c] : 0.0)) * xs[16 * p + k];   // M[k][c]
-            }
-            WAVE_SYNC();
-            if (lane < 16) xs[16 * p + lane] = x;
-        }
-        __syncthreads();
-        for (int q = t; q < 16 * p; q += nt) {
-            int tj = q >> 4, cc = q & 15;
-            double sacc = 0;
-#pragma unroll
-            for (int k = 0; k < 16; k++) sacc += T[tl_idx(p, tj, k, cc)] * xs[16 * p + k];
-            xs[q] -= sacc;
-        }
-        __syncthreads();
-    }
-}
-
-// The same backward half by wavefront 0 alone for tiles resident in LDS: no workgroup barrier inside (the 2 x nb barriers and the
-// conditional loads of chol_backward_tiles were 20 us of a 75 us solve at nb = 11), every load of a step unconditional and in flight
-// at once, per element the operations of chol_backward_tiles in the same order (bit-identical results).  Ends with one barrier.
+// applied as x_p = M_p^T b_p with M = L^-1 from the strictly upper triangle of the factored tile (chol_diag_tile).  Wavefront 0 alone walks
+// the tiles: no workgroup barrier inside (the 2 x nb barriers and the conditional loads of an all-wavefront walk were 20 us of a 75 us solve
+// at nb = 11), every load of a step unconditional and in flight at once.  Ends with one barrier.
 __device__ __forceinline__ void chol_backward_tiles_wave(const double *T, int nb, double *xs, const double *dinv) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (wave == 0) {
@@ -1670,78 +1555,6 @@ __device__ __forceinline__ void chol_backward_tiles_wave(const double *T, int nb
         }
     }
     __syncthreads();
-}
-
-__device__ __forceinline__ void chol_solve_tiles(const double *T, int nb, double *xs, const double *dinv) {
-    const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6;
-    for (int p = 0; p < nb; p++) {  // forward: L y = b
-        if (wave == 0) {
-            const int row = lane & 15;
-            double b = xs[16 * p + row];
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-                double xj = bcast_lane(b, j) * dinv[16 * p + j];
-                if (row == j) b = xj; else if (row > j) b -= T[tl_idx(p, p, row, j)] * xj;
-            }
-            if (lane < 16) xs[16 * p + row] = b;
-        }
-        __syncthreads();
-        for (int q = t; q < 16 * (nb - 1 - p); q += nt) {
-            int ti = p + 1 + (q >> 4), r = q & 15;
-            double sacc = 0;
-#pragma unroll
-            for (int k = 0; k < 16; k++) sacc += T[tl_idx(ti, p, r, k)] * xs[16 * p + k];
-            xs[16 * ti + r] -= sacc;
-        }
-        __syncthreads();
-    }
-    for (int p = nb - 1; p >= 0; p--) {  // backward: L^T x = y
-        if (wave == 0) {
-            const int row = lane & 15;
-            double b = xs[16 * p + row];
-#pragma unroll
-            for (int j = 15; j >= 0; j--) {
-                double xj = bcast_lane(b, j) * dinv[16 * p + j];
-                if (row == j) b = xj; else if (row < j) b -= T[tl_idx(p, p, j, row)] * xj;
-            }
-            if (lane < 16) xs[16 * p + row] = b;
-        }
-        __syncthreads();
-        for (int q = t; q < 16 * p; q += nt) {
-            int tj = q >> 4, cc = q & 15;
-            double sacc = 0;
-#pragma unroll
-            for (int k = 0; k < 16; k++) sacc += T[tl_idx(p, tj, k, cc)] * xs[16 * p + k];
-            xs[q] -= sacc;
-        }
-        __syncthreads();
-    }
-}
-
-// forward substitution only: xs <- L^-1 xs (used for the constant |L^-1 b|^2 = b^T A^-1 b of the prior)
-__device__ __forceinline__ void chol_forward_tiles(const double *T, int nb, double *xs, const double *dinv) {
-    const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6;
-    for (int p = 0; p < nb; p++) {
-        if (wave == 0) {
-            const int row = lane & 15;
-            double b = xs[16 * p + row];
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-                double xj = bcast_lane(b, j) * dinv[16 * p + j];
-                if (row == j) b = xj; else if (row > j) b -= T[tl_idx(p, p, row, j)] * xj;
-            }
-            if (lane < 16) xs[16 * p + row] = b;
-        }
-        __syncthreads();
-        for (int q = t; q < 16 * (nb - 1 - p); q += nt) {
-            int ti = p + 1 + (q >> 4), r = q & 15;
-            double sacc = 0;
-#pragma unroll
-            for (int k = 0; k < 16; k++) sacc += T[tl_idx(ti, p, r, k)] * xs[16 * p + k];
-            xs[16 * ti + r] -= sacc;
-        }
-        __syncthreads();
-    }
 }
 
 // Blocked (16) right-looking Cholesky of the lower triangle of A (n x n, n multiple of 16): diagonal block by one
@@ -1861,36 +1674,6 @@ __device__ __forceinline__ void chol_solve_blocked(const double *L, int n, int l
         }
         __syncthreads();
     }
-}
-
-// out[a] = sum_b M[b][a] * v[b] for a < n (M symmetric or "column sum" of a row-major matrix with nrows rows), split over
-// blockDim/256 row groups and combined through LDS part[(blockDim/256)*VIO_LWMAX]
-__device__ __forceinline__ void colsum(const double *M, int ld, int nrows, const double *v, int n, double *out, double *part) {
-    const int t = threadIdx.x, nt = blockDim.x;
-    const int groups = nt >> 8, g = t >> 8, a0 = t & 255;
-    for (int a = a0; a < n; a += 256) {
-        double s = 0;
-        for (int b = g; b < nrows; b += groups) s += M[(size_t)b * ld + a] * v[b];
-        part[g * VIO_LWMAX + a] = s;
-    }
-    __syncthreads();
-    for (int a = t; a < n; a += nt) {
-        double s = 0;
-        for (int q = 0; q < groups; q++) s += part[q * VIO_LWMAX + a];
-        out[a] = s;
-    }
-    __syncthreads();
-}
-// out[k] = sum_a M[k][a] * v[a], one wavefront per row
-__device__ __forceinline__ void rowdot(const double *M, int ld, int nrows, const double *v, int n, double *out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    for (int k = wave; k < nrows; k += nw) {
-        double s = 0;
-        for (int a = lane; a < n; a += 64) s += M[(size_t)k * ld + a] * v[a];
-        s = wave_sum_dpp(s);
-        if (lane == 0) out[k] = s;
-    }
-    __syncthreads();
 }
 
 // One pass over a row-major matrix M (nrows x n, leading dimension ld) producing either or both of

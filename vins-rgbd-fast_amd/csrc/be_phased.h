@@ -387,7 +387,7 @@ __device__ __forceinline__ double ps_eval_role(const Batch &B, const int s, cons
                 const int j = i + 1;
                 const PreInt &p = *(const PreInt *)(pl + (size_t)i * PH_LD);   // only the header fields are read
                 double *__restrict__ out = c.imu_raw + (size_t)i * 15 * 31;
-                // bf::imu_work_item, written out: the call costs this kernel's register-capped variants (ps_eval_kernel_occ4, ps_ls_kernel) spills
+                // bf::imu_work_item, written out: the call costs this kernel's register-capped variant (ps_ls_kernel) spills
                 if (!cfg.use_imu || bf::imu_solver_skips(p)) { if (part_ == 0) for (int k = 0; k < 15; k++) out[k * 31 + 30] = 0; continue; }
                 if (part_ == 0) {
                     double raw[15];
@@ -586,7 +586,7 @@ __device__ __forceinline__ void ps_eval_body(const Batch &B) {
                 const int j = i + 1;
                 const PreInt &p = *(const PreInt *)(pl + (size_t)i * PH_LD);   // only the header fields are read
                 double *__restrict__ out = c.imu_raw + (size_t)i * 15 * 31;
-                // bf::imu_work_item, written out: the call costs this kernel's register-capped variants (ps_eval_kernel_occ4, ps_ls_kernel) spills
+                // bf::imu_work_item, written out: the call costs this kernel's register-capped variant (ps_ls_kernel) spills
                 if (!cfg.use_imu || bf::imu_solver_skips(p)) { if (part_ == 0) for (int k = 0; k < 15; k++) out[k * 31 + 30] = 0; continue; }
                 if (part_ == 0) {
                     double raw[15];
@@ -690,10 +690,6 @@ __device__ __forceinline__ void ps_eval_body(const Batch &B) {
 }
 
 __global__ __launch_bounds__(256) void ps_eval_kernel(Batch B) { ps_eval_body(B); }
-// VIO_EVAL_OCC = 3 / 4: the same kernel held to 168 / 128 VGPRs (scratch spills in the IMU factor code) for three / four workgroups per
-// SIMD instead of two -- an experiment switch for the occupancy question of DESIGN.md 9
-__global__ __launch_bounds__(256, 3) void ps_eval_kernel_occ3(Batch B) { ps_eval_body(B); }
-__global__ __launch_bounds__(256, 4) void ps_eval_kernel_occ4(Batch B) { ps_eval_body(B); }
 
 // ---------------------------------------------------------------------------------------------------------------- ASM_A
 // grid (NB, S), 512 threads = 8 wavefronts per block; wavefront item w = 8 blockIdx.x + wave over the whole sequence:
@@ -904,8 +900,6 @@ __device__ __forceinline__ void ps_asm_a_body(const Batch &B) {
 }
 
 __global__ __launch_bounds__(512) void ps_asm_a_kernel(Batch B) { ps_asm_a_body(B); }
-// VIO_ASM_A_OCC = 4: the same kernel held to 128 VGPRs (20 bytes of scratch) so that two workgroups share a compute unit
-__global__ __launch_bounds__(512, 4) void ps_asm_a_kernel_occ4(Batch B) { ps_asm_a_body(B); }
 
 // ---------------------------------------------------------------------------------------------------------------- EVAL + ASM_A fused
 // Round 6: evaluation and the first half of the assembly in ONE kernel, so that the residual records (28 doubles per residual: 0.42 MB per
@@ -1283,16 +1277,14 @@ __global__ __launch_bounds__(256) void ps_evalf_kernel(Batch B) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- ASM_B
-// grid (NB, S), 256 threads: one thread per entry (a, b) of H (both triangles, every entry of the P x LW block is written, so no
-// zero-fill pass) and per entry of g: prior block, the (at most two) IMU Gram blocks that contain both columns, then the
-// frame-pair sums -- the same terms in the same order as assemble().  The thread that owns a diagonal entry fixes the Jacobi
-// column scaling the first time round.
-// tri = true (VIO_ASM_B_MODE = 2, round 6): only the entries a >= b are formed (and the gradient); every thread stores its entry and the mirror
-// image.  H's terms are symmetric source by source -- prior_H is stored exactly symmetric, the Gram blocks are read through sym_idx -- and are added
-// in the same order for (a, b) and (b, a), so the mirrored H is the same bits with half the index arithmetic and half the gathers.
-// One entry of H (bcol < LW) or of the gradient (bcol == LW): the prior block, the (at most two) IMU Gram blocks that contain both columns, then the
-// frame-pair sums -- the same terms in the same order as assemble().  Shared by ps_asm_b_body and by the Schur tiles that form S themselves
-// (ps_schur_body, B.form_s).  imu_ok: ps_imu_ok_mask.
+// grid (NB, S), 256 threads: one thread per entry (a, b), a >= b, of H and per entry of g, which stores its entry and the mirror image (every
+// entry of the P x LW block is written, padding columns included, so no zero-fill pass).  H's terms are symmetric source by source -- prior_H is
+// stored exactly symmetric, the Gram blocks are read through sym_idx -- and are added in the same order for (a, b) and (b, a), so the mirrored H
+// is the bits of an H summed entry by entry, with half the index arithmetic and half the gathers.  The thread that owns a diagonal entry fixes
+// the Jacobi column scaling the first time round.
+// ps_h_entry: one entry of H (bcol < LW) or of the gradient (bcol == LW): the prior block, the (at most two) IMU Gram blocks that contain both
+// columns, then the frame-pair sums -- the same terms in the same order as assemble().  Shared by ps_asm_b_body and by the Schur tiles, which sum
+// their own entries of H (ps_schur_body).  imu_ok: ps_imu_ok_mask.
 __device__ __forceinline__ unsigned ps_imu_ok_mask(const Ctx &c, const BeSeq &be) {
     // IMU factors that exist (estimator.cpp:1212-1220 skips pre-integrations longer than 10 s): one lane per factor, then a mask -- looked up per
     // entry it was two dependent global loads (pre_idx, then sum_dt) in front of every IMU term
@@ -1390,7 +1382,7 @@ __device__ __forceinline__ double ps_h_entry(const Ctx &c, const SolveSt &st, co
     return v;
 }
 
-__device__ __forceinline__ void ps_asm_b_body(const Batch &B, int s, int blk, int nb_b, const bool tri = false) {
+__device__ __forceinline__ void ps_asm_b_body(const Batch &B, int s, int blk, int nb_b) {
     const SolveSt &st = B.sst[s];
     if (st.stage != PS_ASM) return;
     Ctx c = make_ctx(B, s);
@@ -1399,29 +1391,26 @@ __device__ __forceinline__ void ps_asm_b_body(const Batch &B, int s, int blk, in
     const bool vext = st.vext != 0;
     const double *pb = c.pairblk, *ib = ps_imu_blk(c);
     const int oE = 15 * W1, oT = 15 * W1 + 6;
-    const int total = P * (LW + 1);   // column LW stands for the gradient entry of the row
     const unsigned imu_ok = ps_imu_ok_mask(c, be);
-    const int ntri = P * (P + 1) / 2, total_t = ntri + P + P * (LW - P);   // tri: lower triangle, gradient, zero padding columns
-    // B.form_s (round 6, windows whose Schur complement stays in HBM): once the column scaling is fixed, S = Sp (H - U) Sp + mu D^2 is formed HERE,
-    // entry by entry as H is summed, instead of by ps_serial's one workgroup per sequence (its "tile load": 39 of 242 us per iteration at W = 20).
+    const int ntri = P * (P + 1) / 2, total = ntri + P + P * (LW - P);   // lower triangle, gradient (bcol == LW stands for the gradient entry of the row), zero padding columns
+    // Once the column scaling is fixed, S = Sp (H - U) Sp + mu D^2 is formed HERE, entry by entry as H is summed, instead of by ps_serial's one
+    // workgroup per sequence (its "tile load": 39 of 242 us per iteration at W = 20).
     // The tiles the landmark rows touch (ps_colmask) belong to their Schur block, which sums their entries of H itself and subtracts U; every
-    // other tile of S is written below.  Same expressions on the same operands as ps_serial's load, hence the same bits.
-    const bool form_s = tri && B.form_s && !st.scale_pending;
+    // other tile of S is written below.  Same expressions on the same operands as ps_serial's own load (first iteration, retries), hence the same bits.
+    const bool form_s = !st.scale_pending;
     const unsigned colmask = ps_colmask(W1, LW, vext);
     const double mu = st.mu;
     const double *spv = c.vec + LW;
-    for (int w = blk * blockDim.x + threadIdx.x; w < (tri ? total_t : total); w += nb_b * blockDim.x) {
+    for (int w = blk * blockDim.x + threadIdx.x; w < total; w += nb_b * blockDim.x) {
         int a, bcol;
-        if (tri) {
-            if (w < ntri) {   // w = a (a + 1) / 2 + b, b <= a: closed form with a one-step correction of the float square root
-                a = (int)((sqrtf(8.0f * (float)w + 1.0f) - 1.0f) * 0.5f);
-                if (a * (a + 1) / 2 > w) a--;
-                if ((a + 1) * (a + 2) / 2 <= w) a++;
-                bcol = w - a * (a + 1) / 2;
-            }
-            else if (w < ntri + P) { a = w - ntri; bcol = LW; }
-            else { const int q = w - ntri - P; a = q / (LW - P); bcol = P + (q - a * (LW - P)); }
-        } else { a = w / (LW + 1); bcol = w - a * (LW + 1); }
+        if (w < ntri) {   // w = a (a + 1) / 2 + b, b <= a: closed form with a one-step correction of the float square root
+            a = (int)((sqrtf(8.0f * (float)w + 1.0f) - 1.0f) * 0.5f);
+            if (a * (a + 1) / 2 > w) a--;
+            if ((a + 1) * (a + 2) / 2 <= w) a++;
+            bcol = w - a * (a + 1) / 2;
+        }
+        else if (w < ntri + P) { a = w - ntri; bcol = LW; }
+        else { const int q = w - ntri - P; a = q / (LW - P); bcol = P + (q - a * (LW - P)); }
         const bool grad = bcol == LW;
         const int b = grad ? -1 : bcol;
         if (!grad && b >= P) { c.H[(size_t)a * LW + b] = 0; continue; }
@@ -1431,7 +1420,7 @@ __device__ __forceinline__ void ps_asm_b_body(const Batch &B, int s, int blk, in
         if (grad) c.vec[a] = v;
         else {
             c.H[(size_t)a * LW + b] = v;
-            if (tri && a != b) c.H[(size_t)b * LW + a] = v;
+            if (a != b) c.H[(size_t)b * LW + a] = v;
             if (form_s) {
                 const double sa = spv[a], sb = spv[b];
                 double sv = sa * sb * (v - 0.0);
@@ -1465,132 +1454,14 @@ __device__ __forceinline__ void ps_asm_b_body(const Batch &B, int s, int blk, in
     }
 }
 
-// Round 5: the same sums organised by BLOCK PAIRS of the tangent space instead of by entries.  The per-entry version above spends ~330 vector
-// instructions per entry on finding out which prior / IMU / frame-pair blocks contain it (9.9 M VALU instructions per launch,
-// profiles/round4_pmc_sq.json) -- 55 % of the solver's thread-time at large batches.  Here one wavefront takes one pair of parameter blocks
-// (pose k: 6 columns, speed-bias k: 9, extrinsic: 6, td: 1; lower triangle + one gradient item per block = 324 items at W = 10): which sources
-// contribute is decided once per item on the scalar unit, a lane only adds (row, column) within the block, and the upper triangle is written
-// as the mirror image.  Same terms in the same order as ps_asm_b_body, hence the same H and g.
-__device__ __forceinline__ void ps_tblock(int q, int W1, int &off, int &sz, int &kind, int &frame) {
-    if (q < W1) { off = 6 * q; sz = 6; kind = 0; frame = q; }
-    else if (q < 2 * W1) { off = 6 * W1 + 9 * (q - W1); sz = 9; kind = 1; frame = q - W1; }
-    else if (q == 2 * W1) { off = 15 * W1; sz = 6; kind = 2; frame = -1; }
-    else { off = 15 * W1 + 6; sz = 1; kind = 3; frame = -1; }
-}
-__device__ __forceinline__ void ps_asm_b_blocks(const Batch &B, int s, int blk, int nb_b) {
-    const SolveSt &st = B.sst[s];
-    if (st.stage != PS_ASM) return;
-    Ctx c = make_ctx(B, s);
-    const BeSeq &be = *c.be;
-    const int W = c.W, W1 = W + 1, P = c.P, LW = c.LW, n = c.NPR;
-    const bool vext = st.vext != 0, relo = st.relo != 0, has_prior = be.has_prior != 0;
-    const double *pb = c.pairblk, *ib = ps_imu_blk(c);
-    const int oE = 15 * W1, oT = oE + 6;
-    const int NBLK = 2 * W1 + 2, NTRI = NBLK * (NBLK + 1) / 2, NITEM = NTRI + NBLK;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    // IMU factors that exist (estimator.cpp:1212-1220 skips pre-integrations longer than 10 s): one lane per factor, then a mask
-    const bool f_ok = lane < W && c.C->c.use_imu && !bf::imu_solver_skips(c.pre[be.pre_idx[min(lane, W - 1) + 1]]);
-    const unsigned imu_ok = (unsigned)__ballot(f_ok);
-    const bool scale_pending = st.scale_pending != 0;
-    for (int item0 = blk * nw + wave; item0 < NITEM; item0 += nb_b * nw) {
-        const int item = __builtin_amdgcn_readfirstlane(item0);
-        const bool grad = item >= NTRI;
-        int br, bc;
-        if (grad) { br = item - NTRI; bc = 0; } else tri_decode(item, br, bc);   // br >= bc
-        int ro, rs, kr, fr, co, cs, kc, fc;
-        ps_tblock(br, W1, ro, rs, kr, fr);
-        ps_tblock(bc, W1, co, cs, kc, fc);
-        if (grad) { cs = 1; kc = 4; fc = -1; }
-        // prior (relocalisation solve: the extrinsic's columns belong to relo_Pose, which the prior knows nothing about)
-        auto prior_base = [&](int kind, int f) -> int {
-            if (kind == 0) return f < W ? 6 * f : -1;
-            if (kind == 1) return f == 0 ? 6 * W : -1;
-            if (kind == 2) return relo ? -1 : 6 * W + 9;
-            return 6 * W + 15;
-        };
-        const int pr = has_prior ? prior_base(kr, fr) : -1, pc = grad ? 0 : (has_prior ? prior_base(kc, fc) : -1);
-        // IMU factors that contain both blocks, even factors first (the order assemble() adds them in)
-        // (of the two factors fr - 1 and fr that touch frame fr one is even, one odd: two fixed slots in that order, no indexed arrays)
-        const int fi0 = (fr & 1) ? fr - 1 : fr, fi1 = (fr & 1) ? fr : fr - 1;
-        auto imu_slot = [&](int i, int &la0, int &lb0) -> bool {
-            if (!(kr <= 1 && (grad || kc <= 1)) || i < 0 || i >= W || !((imu_ok >> i) & 1u)) return false;
-            lb0 = 30;
-            if (!grad) { if (fc != i && fc != i + 1) return false; lb0 = (kc == 0 ? 0 : 6) + (fc == i ? 0 : 15); }
-            la0 = (kr == 0 ? 0 : 6) + (fr == i ? 0 : 15);
-            return true;
-        };
-        int la_0 = 0, lb_0 = 0, la_1 = 0, lb_1 = 0;
-        const bool imu0 = imu_slot(fi0, la_0, lb_0), imu1 = imu_slot(fi1, la_1, lb_1);
-        auto imu_get = [&](int i, int la, int lb) -> double {   // Gram entry (la, lb) of factor i, la, lb in 0 .. 30 (30 = residual column)
-            const double *G = ib + (size_t)i * 768;
-            if (la < lb) { const int x = la; la = lb; lb = x; }
-            return la < 16 ? G[la * 16 + lb] : (lb < 16 ? G[256 + (la - 16) * 16 + lb] : G[512 + (la - 16) * 16 + (lb - 16)]);
-        };
-        // vision: 0 none, 1 one frame pair, 2 one term per other frame of the window, 3 every frame pair
-        const bool vr = kr == 0 || (vext && kr >= 2), vc = grad || kc == 0 || (vext && (kc == 2 || kc == 3));
-        int vmode = 0, vf = -1;
-        if (vr && vc) {
-            if (!grad && kr == 0 && kc == 0 && fr != fc) vmode = 1;
-            else if (kr == 0 || kc == 0) { vmode = 2; vf = kr == 0 ? fr : fc; }
-            else vmode = 3;
-        }
-        const int la_fix = kr == 2 ? 12 : 18, lb_fix = grad ? 19 : (kc == 2 ? 12 : 18);   // local column of a non-pose block in any frame pair
-        for (int e = lane; e < rs * cs; e += 64) {
-            const int r = cs == 6 ? e / 6 : (cs == 9 ? e / 9 : e), cc = e - r * cs, a = ro + r, b = co + cc;   // (constant divisors)
-            double v = 0;
-            if (pr >= 0 && pc >= 0) v = grad ? st.srp[pr + r] : c.prior_H[(pr + r) * n + pc + cc];
-            if (imu0) v += imu_get(fi0, la_0 + r, lb_0 + (grad ? 0 : cc));
-            if (imu1) v += imu_get(fi1, la_1 + r, lb_1 + (grad ? 0 : cc));
-            if (vmode == 1) {
-                const int i = min(fr, fc), j = max(fr, fc);
-                v += pb[(size_t)pair_slot(i, j, W1) * 210 + sym_idx((fr == i ? 0 : 6) + r, (fc == i ? 0 : 6) + cc)];
-            } else if (vmode == 2) {
-                // one term per other frame of the window: all loads issued first, then summed in frame order
-                double pv[VIO_MAXW + 1];
-#pragma unroll
-                for (int o = 0; o <= VIO_MAXW; o++) {
-                    const bool use = o < W1 && o != vf;
-                    const int oo = use ? o : (vf == 0 ? 1 : 0);     // unused slots read a term that exists (and drop it)
-                    const int i = min(vf, oo), j = max(vf, oo), lf = vf == i ? 0 : 6;
-                    const int la = (kr == 0 ? lf : la_fix) + r, lb = (grad ? 19 : (kc == 0 ? lf : lb_fix) + cc);
-                    pv[o] = pb[(size_t)pair_slot(i, j, W1) * 210 + sym_idx(la, lb)];
-                }
-                double sacc = 0;
-#pragma unroll
-                for (int o = 0; o <= VIO_MAXW; o++) if (o < W1 && o != vf) sacc += pv[o];
-                v += sacc;
-            } else if (vmode == 3) {
-                double sacc = 0;
-                const int li = sym_idx(la_fix + r, lb_fix + (grad ? 0 : cc));
-                for (int q = 0; q < W1 * W / 2; q++) sacc += pb[(size_t)q * 210 + li];   // pair slots in (i, j) order
-                v += sacc;
-            }
-            if (grad) c.vec[a] = v;
-            else {
-                c.H[(size_t)a * LW + b] = v;
-                if (br != bc) c.H[(size_t)b * LW + a] = v;
-                else if (a == b && scale_pending) {
-                    bool act = a < oE ? true : (a < oT ? st.ex_active != 0 : st.td_active != 0);
-                    if (!c.C->c.use_imu && (a < 6 || a >= 6 * W1)) act = false;   // VO mode: pose 0 constant, no speed-bias blocks
-                    c.vec[1 * LW + a] = act ? 1.0 / (1.0 + sqrt(v)) : 0.0;   // sp
-                }
-            }
-        }
-    }
-    // padding: columns P .. LW - 1 of H, g / sp beyond P
-    if (blk == 0) {
-        for (int w = threadIdx.x; w < P * (LW - P); w += blockDim.x) { const int a = w / (LW - P), b = P + (w - a * (LW - P)); c.H[(size_t)a * LW + b] = 0; }
-        for (int a = P + threadIdx.x; a < LW; a += blockDim.x) { c.vec[a] = 0; if (scale_pending) c.vec[1 * LW + a] = 0; }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------- SCHUR
 // grid (active tiles, S), 64 threads: one wavefront forms one 16 x 16 lower tile of S = S_p H S_p + mu D^2 - sum_k w_k h_k h_k^T
 // over all landmark rows, operands straight from HBM / L2 in batches of 8 k-steps, into c.Sc in the LDS tile layout.
 #define PS_SCH_U 8
 // U = sum_k hpl_k^T hpl_k w_k, the landmark part of the Schur complement S = Sp (H - U) Sp + mu D^2, for one active 16 x 16 tile on the
 // FP64 matrix cores (one wavefront).  It needs nothing ps_asm_b produces (neither H nor the column scaling Sp), which is why the two run
-// side by side in one launch; ps_serial combines H, U, Sp and mu D^2 while it loads the tiles into LDS.
+// side by side in one launch.  Once the column scaling is fixed the tile also sums its own entries of H and leaves S itself (see below); before that
+// (first iteration, retries) ps_serial combines H, U, Sp and mu D^2 while it loads the tiles.
 __device__ __forceinline__ void ps_schur_body(const Batch &B, int s, int tile_index, double *wk_s) {
     const SolveSt &st = B.sst[s];
     if (st.stage != PS_ASM && st.stage != PS_SCHUR) return;
@@ -1611,9 +1482,9 @@ __device__ __forceinline__ void ps_schur_body(const Batch &B, int s, int tile_in
     const bool first = st.scale_pending != 0;
     v4f64 acc = {0, 0, 0, 0};
     const double *wa = Ws + 16 * ti + li, *wb = Ws + 16 * tj + li;
-    // B.form_s: this block also sums its tile's entries of H (one per thread; ps_asm_b_body skips them) and stores S instead of U -- see
+    // form_s: this block also sums its tile's entries of H (one per thread; ps_asm_b_body skips them) and stores S instead of U -- see
     // ps_asm_b_body.  The gathers are issued ahead of the landmark-row walk below.
-    const bool form_s = B.form_s && st.stage == PS_ASM && !first;
+    const bool form_s = st.stage == PS_ASM && !first;
     double *hbuf = wk_s + ((Kpad + 7) & ~7) + 3 * 256;
     if (form_s) {
         const BeSeq &be = *c.be;
@@ -1723,7 +1594,7 @@ __device__ __forceinline__ void ps_colsum_as_eight_waves(const double *M, int ld
         out_col[a] = sacc;
     }
 }
-// B.gn_ext (round 6): the landmark term of the Gauss-Newton right-hand side, Hpl^T (sl inv gls), needs nothing of this launch's H or of ps_serial's
+// The landmark term of the Gauss-Newton right-hand side, Hpl^T (sl inv gls), needs nothing of this launch's H or of ps_serial's
 // prepare_point beyond what the Schur tiles use (Hll, gl, the landmark scaling and mu) -- one more workgroup of the Schur launch forms it (into the
 // tmpv slot of c.vec) beside the tiles instead of ps_serial's one workgroup per sequence in front of its Cholesky (7 of 93 us per iteration).
 __device__ __forceinline__ void ps_gn_rhs_body(const Batch &B, int s, double *wk_s) {
@@ -1752,14 +1623,14 @@ __device__ __forceinline__ void ps_gn_rhs_body(const Batch &B, int s, double *wk
 }
 
 // one launch: blocks [0, nb_b) sum the entries of H and the gradient, the blocks behind them form the landmark part of the
-// Schur complement tile by tile (and, B.gn_ext, one more the landmark term of the Gauss-Newton right-hand side)
+// Schur complement tile by tile, and one more the landmark term of the Gauss-Newton right-hand side
 // five workgroups per CU (96 VGPRs, two spilled; 30 KB of LDS each): the launch is 2 944 workgroups at S = 64 and ran in three rounds of 1 024 at 112 VGPRs
-__global__ __launch_bounds__(256, 5) void ps_asm_b_schur_kernel(Batch B, int nb_b, int by_blocks) {
+__global__ __launch_bounds__(256, 5) void ps_asm_b_schur_kernel(Batch B, int nb_b) {
     int s, b;
     if (!ps_blk(B, s, b)) return;
     extern __shared__ double ps_wk_s[];
-    if (B.gn_ext && b == nb_b + B.n_schur) ps_gn_rhs_body(B, s, ps_wk_s);
-    else if (b < nb_b) { if (by_blocks == 1) ps_asm_b_blocks(B, s, b, nb_b); else if (by_blocks == 2) ps_asm_b_body(B, s, b, nb_b, true); else ps_asm_b_body(B, s, b, nb_b, false); }
+    if (b == nb_b + B.n_schur) ps_gn_rhs_body(B, s, ps_wk_s);
+    else if (b < nb_b) ps_asm_b_body(B, s, b, nb_b);
     else ps_schur_body(B, s, b - nb_b, ps_wk_s);
 }
 
@@ -1800,8 +1671,8 @@ template <bool BIG, int TB> __device__ __forceinline__ void ps_serial_body(const
     double *hsgl = c.res + (size_t)c.nres_cap * 42 - 4 * (size_t)c.NLs;
     double *yl = hsgl + c.NLs, *ul = yl + c.NLs, *tmpl = ul + c.NLs;
     const int stage0 = st.stage;
-    // (B.form_s: ps_asm_b_schur has left S itself in c.Sc -- whenever it ran at PS_ASM with the column scaling already fixed)
-    const bool s_formed = B.form_s && stage0 == PS_ASM && st.scale_pending == 0;
+    // (ps_asm_b_schur has left S itself in c.Sc whenever it ran at PS_ASM with the column scaling already fixed)
+    const bool s_formed = stage0 == PS_ASM && st.scale_pending == 0;
     double radius = st.radius, mu = st.mu, alpha = st.alpha, dogleg_norm = st.dogleg_norm;
     bool cauchy_valid = st.cauchy_valid != 0;
     int invalid = st.invalid;
@@ -1859,11 +1730,9 @@ template <bool BIG, int TB> __device__ __forceinline__ void ps_serial_body(const
         for (int k = t; k < Kpad; k += nt) {
             double iv = k < Fa ? 1.0 / (Hlls[k] + mu * dgl[k] * dgl[k]) : 0.0;
             inv[k] = iv;
-            if (!B.gn_ext) tmpl[k] = sl[k] * iv * gls[k];
         }
         __syncthreads();
-        // (B.gn_ext: tmpv = Hpl^T (sl inv gls) came in with the vectors, formed by ps_gn_rhs_body in the Schur launch at this mu)
-        if (!B.gn_ext) matvec_pass_2range<TB>(c.Hpl, LW, Fa, P, 6 * W1, 15 * W1, ne_ext, tmpl, nullptr, tmpv, nullptr, work);
+        // (tmpv = Hpl^T (sl inv gls) came in with the vectors, formed by ps_gn_rhs_body in the Schur launch at this mu)
         for (int a = t; a < LW; a += nt) xs[a] = a < P ? gs[a] - sp[a] * tmpv[a] : 0.0;
         __syncthreads();
         PH(49);

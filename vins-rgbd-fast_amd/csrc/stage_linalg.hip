@@ -130,7 +130,7 @@ __global__ __launch_bounds__(512) void be_stage_chol_kernel(int nb, int reps, in
 
 // the streaming factorisation of ps_serial_big (windows beyond 10 keyframes): tiles in HBM / L2, one block column at a time through LDS
 __global__ __launch_bounds__(512) void be_stage_chol_stream_kernel(int nb, int reps, const double *S, const double *rhs, double *Tg, double *Lout, double *xout,
-                                                                    float *ticks, int getenv_mode) {
+                                                                    float *ticks) {
     extern __shared__ __attribute__((aligned(16))) double colbuf[];
     const int t = threadIdx.x, nt = blockDim.x, n = 16 * nb, ntile = nb * (nb + 1) / 2;
     double *T = Tg + (size_t)blockIdx.x * ntile * 256;
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(512) void be_stage_chol_stream_kernel(int nb, int r
         ok = chol_tiles_stream(T, nb, colbuf, &flag, dinv, xs, tm) && ok;
         __syncthreads();
         const long long t1 = (long long)wall_clock64();
-        if (ok) { if (getenv_mode) chol_backward_tiles(T, nb, xs, dinv); else chol_backward_tiles_wave(T, nb, xs, dinv); }   // (VIO_STAGE_BACKWARD_BLOCK: the all-wavefront walk, for comparison)
+        if (ok) chol_backward_tiles_wave(T, nb, xs, dinv);
         __syncthreads();
         const long long t2 = (long long)wall_clock64();
         tf += t1 - t0; tb += t2 - t1;
@@ -193,7 +193,7 @@ static int stage_chol_stream(int nb, int reps, int blocks, const double *S, cons
     HIPCHK(dx.alloc(n)); HIPCHK(dt.alloc(8)); HIPCHK(dT.alloc((size_t)nblk * ntile * 256));
     HIPCHK(dS.upload(S, n * n)); HIPCHK(dr.upload(rhs, n));
     HIPCHK(dL.upload(L_out, n * n));
-    be_stage_chol_stream_kernel<<<nblk, 512, lds>>>(nb, reps, dS, dr, dT, dL, dx, dt, getenv("VIO_STAGE_BACKWARD_BLOCK") ? 1 : 0);
+    be_stage_chol_stream_kernel<<<nblk, 512, lds>>>(nb, reps, dS, dr, dT, dL, dx, dt);
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(dL.download(L_out, n * n)); HIPCHK(dx.download(x_out, n));
     HIPCHK(dt.download(ht, 5));

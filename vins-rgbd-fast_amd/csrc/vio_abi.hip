@@ -492,69 +492,37 @@ int launch_backend(vio_batch *h, vio_batch::Group &g, const uint16_t *d_depth, c
         const bool fuse_only = Bg.fuse > 0 && !C.c.estimate_extrinsic && !C.c.estimate_td && h->relo_frames <= 0 &&
                                (size_t)(C.W + 1) * C.c.max_cnt * 12 / 10 <= (size_t)PS_FUSE_MAXBLK * (PS_FUSE_CAP - C.W);
         Bg.fuse_only = fuse_only ? 1 : 0;
-        auto launch_phased = [&]() {
-            ps_setup_kernel<<<S, 512, 0, st>>>(Bg);
-            const int slots = C.c.max_iterations + h->extra_slots;
-            // XCD-aware block map (ps_blk): every block of a sequence on the XCD its one-block kernels run on
-            const bool xm = h->xcd_map && S >= 8;
-            const int XN = h->xcd_n > 0 ? h->xcd_n : 8;   // (measured with the back-end streams masked to six XCDs: 8 -> +2 %, 6 -> +0.3 %, 3 / 12 -> -1 %: the block -> XCD rotation ignores the mask)
-            const int nb_e = h->ps_eval_blocks, nb_a = h->ps_asm_a_blocks, nb_bs = h->ps_asm_b_blocks + h->ps_schur_tiles + (Bg.gn_ext ? 1 : 0), S8 = XN * ((S + XN - 1) / XN);
-            Batch Be = Bg, Ba = Bg, Bb = Bg;
-            Be.ns = Ba.ns = Bb.ns = S;
-            Be.xcd_n = Ba.xcd_n = Bb.xcd_n = XN;
-            Be.xcd_nb = xm ? nb_e : 0; Ba.xcd_nb = xm ? nb_a : 0; Bb.xcd_nb = xm ? nb_bs : 0;
-            const dim3 g_e = xm ? dim3(S8 * nb_e) : dim3(nb_e, S), g_a = xm ? dim3(S8 * nb_a) : dim3(nb_a, S), g_b = xm ? dim3(S8 * nb_bs) : dim3(nb_bs, S);
-            Batch Bf = Bg;
-            Bf.ns = S; Bf.xcd_n = XN; Bf.xcd_nb = xm ? h->ps_evalf_blocks : 0;
-            const dim3 g_f = xm ? dim3(S8 * h->ps_evalf_blocks) : dim3(h->ps_evalf_blocks, S);
-            for (int k = 0; k < slots; k++) {
-                // fused evaluate + assemble for the solves that qualify (st.fused); ps_eval / ps_asm_a serve the others and idle for these
-                if (Bg.fuse) ps_evalf_kernel<<<g_f, 256, h->lds_ps_evalf, st>>>(Bf);
-                if (!fuse_only) {
-                    // (idle launches are not free here: their workgroups ask for 40 KB of LDS each and queue behind the other stream group's
-                    // fused workgroups, which fill the CUs' LDS -- 15 us per idle launch, measured)
-                    if (h->eval_occ == 4) ps_eval_kernel_occ4<<<g_e, 256, h->lds_ps_eval, st>>>(Be);
-                    else if (h->eval_occ == 3) ps_eval_kernel_occ3<<<g_e, 256, h->lds_ps_eval, st>>>(Be);
-                    else ps_eval_kernel<<<g_e, 256, h->lds_ps_eval, st>>>(Be);
-                    if (h->asm_a_occ4) ps_asm_a_kernel_occ4<<<g_a, 512, 0, st>>>(Ba);
-                    else ps_asm_a_kernel<<<g_a, 512, 0, st>>>(Ba);
-                }
-                ps_asm_b_schur_kernel<<<g_b, 256, (size_t)(C.NL + 16 + (6 * (C.W + 1) + 7 <= 128 ? 8 * 128 : 8 * 192) /* eight compact partial rows of ps_gn_rhs_body (>= the 4 x 256 of a Schur tile) */) * sizeof(double), st>>>(Bb, h->ps_asm_b_blocks, h->asm_b_by_blocks);   // per-row factors + the partial tiles of wavefronts 1 .. 3 + the tile of H (form_s)
-                if (h->serial_big) ps_serial_big_kernel<<<S, 512, h->lds_serial, st>>>(Bg);
-                else ps_serial_kernel_512<<<S, 512, h->lds_serial, st>>>(Bg);
-                // Ceres' projected line search of bounds-constrained solves (one workgroup per sequence, idle otherwise); the candidate of the
-                // last slot is never evaluated, so no search follows it
-                if (h->line_search && k + 1 < slots) ps_ls_kernel<<<S, 256, h->lds_ps_ls, st>>>(Bg);
+        ps_setup_kernel<<<S, 512, 0, st>>>(Bg);
+        const int slots = C.c.max_iterations + h->extra_slots;
+        // XCD-aware block map (ps_blk): every block of a sequence on the XCD its one-block kernels run on
+        const bool xm = h->xcd_map && S >= 8;
+        const int XN = 8;   // XCDs the map assumes (measured with the back-end streams masked to six XCDs: 8 -> +2 %, 6 -> +0.3 %, 3 / 12 -> -1 %: the block -> XCD rotation ignores the mask)
+        const int nb_e = h->ps_eval_blocks, nb_a = h->ps_asm_a_blocks, nb_bs = h->ps_asm_b_blocks + h->ps_schur_tiles + 1 /* ps_gn_rhs_body */, S8 = XN * ((S + XN - 1) / XN);
+        Batch Be = Bg, Ba = Bg, Bb = Bg;
+        Be.ns = Ba.ns = Bb.ns = S;
+        Be.xcd_n = Ba.xcd_n = Bb.xcd_n = XN;
+        Be.xcd_nb = xm ? nb_e : 0; Ba.xcd_nb = xm ? nb_a : 0; Bb.xcd_nb = xm ? nb_bs : 0;
+        const dim3 g_e = xm ? dim3(S8 * nb_e) : dim3(nb_e, S), g_a = xm ? dim3(S8 * nb_a) : dim3(nb_a, S), g_b = xm ? dim3(S8 * nb_bs) : dim3(nb_bs, S);
+        Batch Bf = Bg;
+        Bf.ns = S; Bf.xcd_n = XN; Bf.xcd_nb = xm ? h->ps_evalf_blocks : 0;
+        const dim3 g_f = xm ? dim3(S8 * h->ps_evalf_blocks) : dim3(h->ps_evalf_blocks, S);
+        for (int k = 0; k < slots; k++) {
+            // fused evaluate + assemble for the solves that qualify (st.fused); ps_eval / ps_asm_a serve the others and idle for these
+            if (Bg.fuse) ps_evalf_kernel<<<g_f, 256, h->lds_ps_evalf, st>>>(Bf);
+            if (!fuse_only) {
+                // (idle launches are not free here: their workgroups ask for 40 KB of LDS each and queue behind the other stream group's
+                // fused workgroups, which fill the CUs' LDS -- 15 us per idle launch, measured)
+                ps_eval_kernel<<<g_e, 256, h->lds_ps_eval, st>>>(Be);
+                ps_asm_a_kernel<<<g_a, 512, 0, st>>>(Ba);
             }
-            ps_final_kernel<<<S, 256, 0, st>>>(Bg);
-        };
-        // VIO_GRAPH: the 43 launches of one solve replayed as a hipGraph captured on the group's stream at its first use (the kernel
-        // arguments -- the Batch of the group -- normally do not change from frame to frame)
-        if (h->use_graph && one_seq < 0) {
-            // the capture bakes in the Batch (by value) and the launch knobs: key it on their bytes, so that any setter that touches h->B
-            // (vio_set_tracker_lag, vio_set_fisheye_mask, ...) or a knob makes the next solve re-capture instead of replaying stale arguments
-            uint64_t key = 1469598103934665603ULL;
-            auto mixin = [&](const void *p, size_t nbytes) { const unsigned char *q = (const unsigned char *)p; for (size_t i = 0; i < nbytes; i++) { key ^= q[i]; key *= 1099511628211ULL; } };
-            mixin(&Bg, sizeof(Bg));
-            mixin(&h->line_search, sizeof(h->line_search));
-            mixin(&fuse_only, sizeof(fuse_only));
-            const int knobs[12] = {C.c.max_iterations + h->extra_slots, h->eval_occ, h->asm_a_occ4 ? 1 : 0, h->serial_big ? 1 : 0, h->serial_threads, h->ps_eval_blocks, h->ps_asm_a_blocks,
-                                   h->ps_asm_b_blocks + 1000 * h->asm_b_by_blocks, h->ps_schur_tiles, h->xcd_map, h->xcd_n, (int)h->lds_serial};
-            mixin(knobs, sizeof(knobs));
-            mixin(&h->lds_ps_eval, sizeof(h->lds_ps_eval));
-            if (g.solve_graph && g.solve_graph_key != key) { (void)hipGraphExecDestroy(g.solve_graph); g.solve_graph = nullptr; }
-            g.solve_graph_key = key;
-            if (!g.solve_graph) {
-                hipGraph_t gr = nullptr;
-                HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-                launch_phased();
-                HIPCHK(hipStreamEndCapture(st, &gr));
-                HIPCHK(hipGraphInstantiate(&g.solve_graph, gr, nullptr, nullptr, 0));
-                (void)hipGraphDestroy(gr);
-            }
-            HIPCHK(hipGraphLaunch(g.solve_graph, st));
-        } else
-            launch_phased();
+            ps_asm_b_schur_kernel<<<g_b, 256, (size_t)(C.NL + 16 + (6 * (C.W + 1) + 7 <= 128 ? 8 * 128 : 8 * 192) /* eight compact partial rows of ps_gn_rhs_body (>= the 4 x 256 of a Schur tile) */) * sizeof(double), st>>>(Bb, h->ps_asm_b_blocks);   // per-row factors + the partial tiles of wavefronts 1 .. 3 + the tile of H
+            if (h->serial_big) ps_serial_big_kernel<<<S, 512, h->lds_serial, st>>>(Bg);
+            else ps_serial_kernel_512<<<S, 512, h->lds_serial, st>>>(Bg);
+            // Ceres' projected line search of bounds-constrained solves (one workgroup per sequence, idle otherwise); the candidate of the
+            // last slot is never evaluated, so no search follows it
+            if (h->line_search && k + 1 < slots) ps_ls_kernel<<<S, 256, h->lds_ps_ls, st>>>(Bg);
+        }
+        ps_final_kernel<<<S, 256, 0, st>>>(Bg);
     } else if (be_threads <= 512) be_solve_kernel_512<<<S, be_threads, h->lds_solve, st>>>(Bg);
     else be_solve_kernel<<<S, be_threads, h->lds_solve, st>>>(Bg);
     if (prof) PEV(h, 10);
@@ -720,10 +688,8 @@ static int build_devcfg(const vio_config *cfg, int imu_capacity, DevCfg &C) {
 // contiguous ranges = whole XCDs.  The wide front-end kernels of frame f+1 then overlap the latency-bound solver kernels of frame f, and
 // keeping them on their own XCDs leaves the solver's L2 slices and dispatchers alone (measured: +5 %; stream priorities and an
 // interleaved mask did nothing).  VIO_FE_CUS = n (default 64, 0 = no partition): front-end streams use CUs [0, n), back-end streams
-// the rest; VIO_BE_CU_SPLIT = 1: the back-end streams of the groups share [n, 256) in equal contiguous parts; VIO_BE_CU_ALL = 1: back-end
-// on all CUs.  With lag 0 the front-end is on the critical path itself and gets the whole device.
+// the rest.  With lag 0 the front-end is on the critical path itself and gets the whole device.
 static int create_group_streams(vio_batch *h, vio_batch::Group &g, bool partitioned) {
-    if (g.solve_graph) { (void)hipGraphExecDestroy(g.solve_graph); g.solve_graph = nullptr; }   // captured on the stream that goes away
     stream_release(h, g.stream);
     stream_release(h, g.fe_stream);
     // the partition is sized from the device: a quarter of its compute units (64 of the MI355X's 256 = two XCDs) for the front-end by
@@ -746,16 +712,9 @@ static int create_group_streams(vio_batch *h, vio_batch::Group &g, bool partitio
         h->fe_partitioned = true;
         const int nw = (n_cu + 31) / 32;
         std::vector<uint32_t> mfe(nw, 0u), mbe(nw, 0u);
-        const int ng = (int)h->groups.size(), gi = (int)(&g - &h->groups[0]);
-        const bool split = env_int("VIO_BE_CU_SPLIT", 0) != 0 && ng > 1 && (n_cu - fe_cus) / ng >= 1;
-        const int per = (n_cu - fe_cus) / ng;
-        const int b0 = split ? fe_cus + gi * per : fe_cus, b1 = split ? (gi == ng - 1 ? n_cu : b0 + per) : n_cu;
-        for (int q = 0; q < n_cu; q++) {
-            if (q < fe_cus) mfe[q >> 5] |= 1u << (q & 31);
-            if (q >= b0 && q < b1) mbe[q >> 5] |= 1u << (q & 31);
-        }
+        for (int q = 0; q < n_cu; q++) (q < fe_cus ? mfe : mbe)[q >> 5] |= 1u << (q & 31);
         e_fe = hipExtStreamCreateWithCUMask(&g.fe_stream, (uint32_t)nw, mfe.data());
-        e_be = getenv("VIO_BE_CU_ALL") ? hipStreamCreate(&g.stream) : hipExtStreamCreateWithCUMask(&g.stream, (uint32_t)nw, mbe.data());
+        e_be = hipExtStreamCreateWithCUMask(&g.stream, (uint32_t)nw, mbe.data());
     } else {
         e_fe = hipStreamCreate(&g.fe_stream);
         e_be = hipStreamCreate(&g.stream);
@@ -766,11 +725,9 @@ static int create_group_streams(vio_batch *h, vio_batch::Group &g, bool partitio
     return VIO_OK;
 }
 
-// marg_exact: the largest block whose eigen-decomposition runs LDS-resident (DevCfg::MXL), and the two eigen-solver knobs
+// marg_exact: the largest block whose eigen-decomposition runs LDS-resident (DevCfg::MXL)
 static void size_marg_exact(vio_batch *h) {
     h->hc.MXL = 0;
-    h->hc.eig_one_wave = env_int("VIO_EIG_ONE_WAVE", 0) != 0;
-    h->hc.eig_jacobi = env_int("VIO_MARG_EIG_JACOBI", 0) != 0;
     if (h->hc.MX > 0) {
         // marg_exact: the eigen-decompositions of the literal marginalisation run LDS-resident for blocks up to MXL -- whatever the kernel's
         // static LDS leaves of the workgroup's share (matrix with an odd leading dimension + the solver's vectors, be_kernels.hip
@@ -782,7 +739,6 @@ static void size_marg_exact(vio_batch *h) {
             const long avail = (long)cap - (long)fa.sharedSizeBytes - 256;
             int m = 0;
             while (m < 128 && (long)marg_exact_lds_bytes(m + 1) <= avail) m++;
-            m = std::min(m, std::max(0, env_int("VIO_MARG_EIG_LDS", m)));   // 0: the round-4 HBM Jacobi everywhere (A/B timing)
             h->hc.MXL = m;
         }
     }
@@ -791,21 +747,16 @@ static void size_marg_exact(vio_batch *h) {
 // the launch knobs of the environment, read once per handle
 static void read_knobs(vio_batch *h) {
     h->be_threads = std::min(1024, std::max(64, env_int("VIO_BE_THREADS", h->be_threads) & ~63));
-    h->asm_b_by_blocks = std::max(0, std::min(2, env_int("VIO_ASM_B_MODE", h->asm_b_by_blocks)));
     // (round 6: 12 for windows up to W = 10 -- with the mirrored assembly and the Schur tiles summing their own entries a launch of 24 left two entries per
     //  thread, and fewer, longer workgroups fill the back-end's CUs in fewer rounds: 56.5 -> 57.1 k at 128 sequences, 76.5 -> 78.0 k at 512; W = 20: 24 stays,
     //  12 / 16 / 48 measured 11.8 / 12.0 / 12.2 k against 12.2 k)
     h->ps_asm_b_blocks = h->hc.W <= 10 ? 12 : 24;
     h->ps_asm_b_blocks = std::max(1, std::min(256, env_int("VIO_ASM_B_BLOCKS", h->ps_asm_b_blocks)));
-    h->eval_occ = env_int("VIO_EVAL_OCC", h->eval_occ);
-    h->use_graph = env_int("VIO_GRAPH", h->use_graph) != 0;
     h->xcd_map = env_int("VIO_XCD_MAP", h->xcd_map);
     h->fe_xcd_map = env_int("VIO_FE_XCD_MAP", h->fe_xcd_map);
-    h->xcd_n = env_int("VIO_XCD_N", h->xcd_n);
     h->feed_throttle = env_int("VIO_FEED_THROTTLE", h->feed_throttle) != 0;
     h->uploads_in_flight = env_int("VIO_UPLOADS_IN_FLIGHT", h->uploads_in_flight) == 1 ? 1 : 2;
     h->extra_slots = std::max(1, env_int("VIO_EXTRA_SLOTS", h->extra_slots));
-    h->asm_a_occ4 = env_int("VIO_ASM_A_OCC", 0) >= 4;
     // (VIO_SERIAL_THREADS = 1024 is gone: the 1024-thread build of ps_serial had been producing wrong steps since round 4 -- 2.1 iterations per solve,
     // metres of ATE, found in round 6 by a knob sweep -- while bench.py's `valid` only looked at the solver flags; never the default, no test ran it)
     h->marg_threads = std::min(512, std::max(64, env_int("VIO_MARG_THREADS", h->marg_threads) & ~63));
@@ -865,11 +816,7 @@ static int size_launches(vio_batch *h) {
             const size_t nb = (size_t)C.LW >> 4, tiles = nb * (nb + 1) / 2 * 256;
             const size_t wk = std::max(tiles <= 16896 ? tiles : (2 * nb + 1) * 256, (size_t)16 * 336);   // (streaming: two block columns + the look-ahead tile, chol_tiles_stream)
             h->serial_big = tiles > 16896;
-            // the Schur-complement launch leaves S itself behind (ps_asm_b_body; VIO_FORM_S = 0: ps_serial combines H, U, Sp and mu D^2 as in rounds 2 - 5).
-            // W = 20: ps_serial_big 242 -> 213 us per iteration; W = 10: +0.6 % frames/s at 128 sequences, -0.5 % at 512
-            h->B.form_s = env_int("VIO_FORM_S", 1) != 0 && h->asm_b_by_blocks == 2;
             h->lds_serial = ((size_t)C.LW + 2 + wk + 2 + (size_t)14 /* PS_LVEC */ * C.LW) * 8 + 16;   // + the step's vectors (be_phased.h)
-            if (getenv("VIO_SERIAL_LDS") && (size_t)atol(getenv("VIO_SERIAL_LDS")) > h->lds_serial) h->lds_serial = (size_t)atol(getenv("VIO_SERIAL_LDS"));   // experiment: a larger request keeps other workgroups off the CU
             (void)raise_lds_limit(h->serial_big ? (const void *)ps_serial_big_kernel : (const void *)ps_serial_kernel_512, h->lds_serial);
         }
         {
@@ -900,8 +847,6 @@ static int size_launches(vio_batch *h) {
             (void)raise_lds_limit((const void *)ps_ls_kernel, h->lds_ps_ls);
             // reference_quirks bit 3 (tests) / VIO_LINE_SEARCH=0 (measurement): the clamp-only treatment of the inverse-depth bound, no search launches
             h->line_search = !(C.c.reference_quirks & VIO_QUIRK_BOUND_CLAMP_ONLY) && env_int("VIO_LINE_SEARCH", 1) != 0;
-            (void)raise_lds_limit((const void *)ps_eval_kernel_occ3, h->lds_ps_eval);
-            (void)raise_lds_limit((const void *)ps_eval_kernel_occ4, h->lds_ps_eval);
             B.eval_rpt = std::max(1, std::min(4, env_int("VIO_EVAL_RPT", 2)));
             h->ps_eval_blocks = (int)std::min<size_t>(PS_MAX_EVAL_BLOCKS, (size_t)C.W * C.NP / (256 * (size_t)B.eval_rpt) + 4);
             h->ps_asm_a_blocks = (int)((W1 * (W1 - 1) / 2 + C.W + 32 + 7) / 8);   // pair items (i < j), IMU items, PS_ROW_WAVES = 32 landmark-row wavefronts
@@ -912,7 +857,6 @@ static int size_launches(vio_batch *h) {
             }
             h->ps_schur_tiles = nact;
             h->B.n_schur = nact;
-            h->B.gn_ext = env_int("VIO_GN_EXT", 1) != 0;
         }
     }
     {
@@ -1022,7 +966,6 @@ void vio_destroy(vio_batch *h) {
     int caller_dev = -1;   // (not a DevGuard: the handle dies inside this function)
     const bool dev_switched = h->device >= 0 && hipGetDevice(&caller_dev) == hipSuccess && caller_dev != h->device && hipSetDevice(h->device) == hipSuccess;
     (void)hipDeviceSynchronize();
-    for (auto &g : h->groups) if (g.solve_graph) (void)hipGraphExecDestroy(g.solve_graph);
     for (void *p : h->allocs) (void)hipFree(p);
     for (void *p : h->pinned) (void)hipHostFree(p);
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);

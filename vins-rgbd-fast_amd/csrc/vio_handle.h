@@ -34,8 +34,6 @@ struct vio_batch {
         hipEvent_t ev_solve = nullptr, ev_fe = nullptr, ev_be = nullptr, ev_ingest = nullptr;
         hipStream_t copy_stream = nullptr;   // host -> HBM uploads of vio_feed (on_device == 0), beside the kernels of the previous frame
         hipStream_t copy_stream2 = nullptr;  // the depth images on a stream of their own: two DMA engines per group (one stream moves ~25 GB/s from page-locked memory)
-        hipGraphExec_t solve_graph = nullptr;   // VIO_GRAPH: setup + iteration slots + final of this group as one graph launch
-        uint64_t solve_graph_key = 0;           // hash of the arguments the capture baked in (Batch by value + launch knobs)
         // vio_feed uploads from host buffers: one event pair per staging buffer (g.flip), so that TWO uploads may be in flight -- the call that
         // reuses a staging buffer waits for the upload of two calls ago, not for the previous one (round 5; vio_host_buffers_done)
         hipEvent_t ev_up_gray[2] = {nullptr, nullptr}, ev_up_depth[2] = {nullptr, nullptr};
@@ -61,15 +59,10 @@ struct vio_batch {
     std::vector<Group> groups;
     int tracker_lag = 0;              // vio_set_tracker_lag
     int extra_slots = 2;              // VIO_EXTRA_SLOTS: iteration slots beyond max_iterations (1 carries the last evaluation, the second absorbs one Cholesky retry / invalid step)
-    int xcd_n = 0;                    // VIO_XCD_N: override of the XCD count the map assumes (0: 8)
-    bool use_graph = false;           // VIO_GRAPH: replay the solve chain of a group as a hipGraph (launch_backend)
     int xcd_map = 1;                  // VIO_XCD_MAP: XCD-aware block map of the multi-block ps_* kernels (be_phased.h ps_blk)
     int fe_xcd_map = 1;               // VIO_FE_XCD_MAP: the same idea for fe_lk (needs the front-end on every XCD: off under a CU partition)
     bool fe_partitioned = false;      // the front-end streams carry a CU mask (VIO_FE_CUS > 0 with tracker lag 1)
     int ps_asm_b_blocks = 24;         // workgroups per sequence that sum the entries of H (VIO_ASM_B_BLOCKS)
-    int asm_b_by_blocks = 2;          // VIO_ASM_B_MODE: 2 (default since round 6) = one thread per entry a >= b of H, mirror image stored too (same bits as 0, +5 % frames/s); 0 = one thread per entry of H; 1 = H summed by pairs of parameter blocks (round 5: same bits, 1 - 2 % slower)
-    int serial_threads = 512;         // ps_serial block size (VIO_SERIAL_THREADS: 512 or 1024).  Round 3: equal speed (36.2 k vs 36.4 k frames/s); the 512-thread
-                                      // build has 256 VGPRs per lane and no scratch, the 1024-thread one spills 21 registers since the matrix-core diagonal block
     hipStream_t stream = nullptr;     // = groups[0].stream (returned by vio_get_stream; IMU scatter runs here)
     hipStream_t fe_stream = nullptr;  // = groups[0].fe_stream
     hipEvent_t ev[4];
@@ -151,8 +144,6 @@ struct vio_batch {
     PreAhead *d_ahead = nullptr;
     // VIO_SOLVE_MODE: 0 = persistent kernel (one workgroup per sequence for the whole solve), 1 = phased solver (be_phased.h, default)
     int solve_mode = 1;
-    bool asm_a_occ4 = false;          // VIO_ASM_A_OCC=4
-    int eval_occ = 0;                 // VIO_EVAL_OCC=3|4
     bool serial_big = false;          // the window's Schur complement does not fit LDS: ps_serial_big_kernel (HBM-resident tiles, streaming Cholesky)
     size_t lds_ps_eval = 0;
     int ps_eval_blocks = 0, ps_asm_a_blocks = 0, ps_schur_tiles = 0;
@@ -366,7 +357,7 @@ static_assert(sizeof(vio_calibration) % alignof(vio_camera) == 0, "camera table 
     SEQ(SCRATCH, res, D.nres * 42) SEQ(SCRATCH, res_pair, 1) SEQ(SCRATCH, res_lm, D.nres) SEQ(SCRATCH, res_k, D.nres)                           \
     SEQ(SCRATCH, pair_start, D.npair + 1) SEQ(SCRATCH, pair_list, D.nres) SEQ(SCRATCH, pairblk, D.npair * 210)                                  \
     SEQ(SCRATCH, ls_scratch, D.ls_bytes) SEQ(SCRATCH, pairpart, D.fuse_rows * PS_FUSE_MAXPAIRS * PS_FUSE_MAXBLK * 210)                          \
-    DOC("gW gP gLW gNL gNP gNRES gNPRIOR gMX") DOC("gn_ext n_schur form_s fuse fuse_only")                                                      \
+    DOC("gW gP gLW gNL gNP gNRES gNPRIOR gMX") DOC("n_schur fuse fuse_only")                                                                    \
     SEQ(SCRATCH, imu_raw, D.W * 15 * 31)                                                                                                        \
     SEQ(SCRATCH, margA, D.mq * D.mq) SEQ(SCRATCH, margB, D.mq) SEQ(SCRATCH, margV, D.n * D.n) SEQ(SCRATCH, margW, (D.n + 16) * (D.n + 16))      \
     SEQ(SCRATCH, margE, 3 * D.MX * D.MX + D.n * D.MX) /* marg_exact = 1 only */                                                                 \

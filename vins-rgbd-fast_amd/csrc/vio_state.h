@@ -65,9 +65,7 @@ struct DevCfg {
     int pyr_bytes;
     int lk_level;       // pyramid depth LK really uses (vio_lk_effective_level of c.lk_max_level): the levels built and tracked
     int MX;             // marg_exact: largest marginalised block (15 + landmarks starting in frame 0) the scratch margE is sized for (0 = off)
-    int MXL;            // marg_exact: largest block whose eigen-decomposition runs LDS-resident (Householder + implicit QL); larger ones use the HBM Jacobi
-    int eig_jacobi;     // VIO_MARG_EIG_JACOBI: the eigen-decompositions of the literal marginalisation that do not fit LDS by cyclic Jacobi sweeps over HBM (rounds 3 - 5) instead of sym_eig_hbm
-    int eig_one_wave;   // VIO_EIG_ONE_WAVE: the Householder tridiagonalisation of the LDS-resident eigen-decompositions on ONE wavefront (no workgroup barriers) instead of the whole workgroup
+    int MXL;            // marg_exact: largest block whose eigen-decomposition runs LDS-resident (Householder + implicit QL); larger ones run the same on the matrix in HBM (sym_eig_hbm)
     // estimate_extrinsic = 2 handles only (nullptr otherwise): calibration state [S] and pair history of every sequence (here rather than in
     // Batch, which every kernel takes by value; only be_ingest<true> reads them)
     ExSeq *exc;
@@ -264,8 +262,7 @@ struct Batch {
     double *pairpart;                 // fused kernel: [S][PS_FUSE_MAXPAIRS][PS_FUSE_MAXBLK][210] partial Gram blocks of frame pairs whose residuals span chunks
     // the dimensions make_ctx needs, as kernel arguments (scalar registers) instead of a dependent load from *cfg at the top of every workgroup
     int gW, gP, gLW, gNL, gNP, gNRES, gNPRIOR, gMX;
-    int gn_ext, n_schur;   // one more workgroup of the Schur launch (behind its n_schur tiles) forms the landmark term of the Gauss-Newton right-hand side (VIO_GN_EXT)
-    int form_s;   // ps_asm_b_schur forms S = Sp (H - U) Sp + mu D^2 itself (windows on ps_serial_big, VIO_FORM_S)
+    int n_schur;   // Schur tiles of ps_asm_b_schur; one more workgroup of the launch, behind them, forms the landmark term of the Gauss-Newton right-hand side
     int fuse;                         // VIO_FUSE (default 0, off): solves that qualify run ps_evalf_kernel instead of ps_eval + ps_asm_a; value = chunks the grid covers
     int fuse_only;                    // this launch sequence carries no ps_eval / ps_asm_a (every solve of the handle's configuration qualifies)
     double *imu_raw;                  // [S][W][15*31] raw / whitened IMU Jacobians + residual
