@@ -19,7 +19,7 @@ using namespace dm;
 #define PH_INIT long long ph_t0 = (s == 0 && threadIdx.x == 0) ? VIO_CLOCK() : 0
 #define PH(k) do { if (s == 0 && threadIdx.x == 0) { long long n_ = VIO_CLOCK(); B.timings[k] += (float)(n_ - ph_t0); ph_t0 = n_; } } while (0)
 #else
-#define PH_INIT do {} while (0)
+#define PH_INIT long long ph_t0 = 0   // (never read: the functions that tick take it as a parameter in both builds)
 #define PH(k) do {} while (0)
 #endif
 
@@ -1033,6 +1033,36 @@ __device__ __forceinline__ int prior_map(int a, int W) {
     return 15 * (W + 1) + 6;
 }
 
+// Frame-pair geometry of the evaluation point X: a table of 32-double records (be_factors.h PairGeo: A1, A2, M, t) and, as record nrec, ric.
+// The one place that fills such a table; the callers differ in how a record is indexed only: pair(p, i, j) names the frames of record p and
+// says whether the record is wanted (a pair without residuals is left as it is).  Called by every thread of the workgroup (nt of them); ends
+// with the barrier behind which the table may be read.
+template <class Pair>
+__device__ __forceinline__ void stage_pair_geo(const Params &X, double *geo, const int nrec, const int nt, Pair pair) {
+    for (int p = threadIdx.x; p <= nrec; p += nt) {
+        if (p == nrec) { stm(geo + (size_t)p * 32, q2R(mkq(X.ex[6], X.ex[3], X.ex[4], X.ex[5]))); continue; }
+        int i, j;
+        if (!pair(p, i, j)) continue;
+        bf::PairGeo g;
+        bf::pair_geo(&X.pose[i * 7], &X.pose[j * 7], X.ex, g);
+        double *o = geo + (size_t)p * 32;
+        for (int q = 0; q < 9; q++) { o[q] = g.A1[q]; o[9 + q] = g.A2[q]; o[18 + q] = g.M[q]; }
+        o[27] = g.t[0]; o[28] = g.t[1]; o[29] = g.t[2];
+    }
+    __syncthreads();
+}
+// record p = i W1 + j of the square table (be_solve's evaluate, ps_eval): the pairs i < j that have residuals
+__device__ __forceinline__ bool pair_of_square(const Ctx &c, const int W1, const int p, int &i, int &j) {
+    i = p / W1; j = p - i * W1;
+    return i < j && c.pair_start[p + 1] != c.pair_start[p];
+}
+// where a projection record keeps its weighted residual: behind the two Jacobian rows of the 42-double layout (vext, relocalisation), in
+// the last column of each row of the compact 28-double one
+__device__ __forceinline__ void rec_put_wr(double *out, const bool compact, const double wgt, const double *rr) {
+    out[compact ? 13 : 40] = wgt * rr[0];
+    out[compact ? 27 : 41] = wgt * rr[1];
+}
+
 // evaluate every residual at X. withJ: store weighted Jacobians/residuals for assembly. Returns total cost.
 // vext: the extrinsic and / or td block is a variable of this solve.  Otherwise the residual records are written in the compact
 // layout (28 doubles: two rows of [pose_i(6) pose_j(6) inv_depth r]) and no Jacobian is evaluated for the constant blocks.
@@ -1077,21 +1107,7 @@ __device__ __forceinline__ double evaluate(const Ctx &c, const Params &X, const 
     // per-lane gathers from HBM those were a third of the cache-line lookups that bound this loop.
     {
         const int W1 = W + 1;
-        for (int p = t; p <= W1 * W1; p += nt) {
-            if (p == W1 * W1) {
-                m3 ric = q2R(mkq(X.ex[6], X.ex[3], X.ex[4], X.ex[5]));
-                stm(geo + (size_t)p * 32, ric);
-                continue;
-            }
-            int i = p / W1, j = p - i * W1;
-            if (!(i < j) || c.pair_start[p + 1] == c.pair_start[p]) continue;
-            bf::PairGeo g;
-            bf::pair_geo(&X.pose[i * 7], &X.pose[j * 7], X.ex, g);
-            double *o = geo + (size_t)p * 32;
-            for (int q = 0; q < 9; q++) { o[q] = g.A1[q]; o[9 + q] = g.A2[q]; o[18 + q] = g.M[q]; }
-            o[27] = g.t[0]; o[28] = g.t[1]; o[29] = g.t[2];
-        }
-        __syncthreads();
+        stage_pair_geo(X, geo, W1 * W1, nt, [&](const int p, int &i, int &j) { return pair_of_square(c, W1, p, i, j); });
         PH(41);
         if (be.has_prior) {
             // The prior is kept as the quadratic form (A, b, c0) = (J^T J, J^T r, |r|^2) of the reference's linearised factor:
@@ -1117,13 +1133,13 @@ __device__ __forceinline__ double evaluate(const Ctx &c, const Params &X, const 
                 bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, c.K->tr, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
                                          cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
-                if (withJ) { out[40] = wgt * rr[0]; out[41] = wgt * rr[1]; }
+                if (withJ) rec_put_wr(out, false, wgt, rr);
             } else {
                 double *out = c.res + (size_t)r * 28;
                 bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, c.K->tr, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
                                          cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt, 14, false);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
-                if (withJ) { out[13] = wgt * rr[0]; out[27] = wgt * rr[1]; }
+                if (withJ) rec_put_wr(out, true, wgt, rr);
             }
             cost += 0.5 * log(1.0 + sq);
         }
@@ -2656,15 +2672,7 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
         F0k = F0c;
         // frame-pair form like the solver (be_factors.h eval_projection_pair): the geometry of the pairs (0, k) once, in LDS
         __shared__ double mgeo[(VIO_MAXW + 1) * 32 + 16];
-        if (t >= 1 && t <= W) {
-            bf::PairGeo g;
-            bf::pair_geo(&X.pose[0], &X.pose[t * 7], X.ex, g);
-            double *o = mgeo + (size_t)(t - 1) * 32;
-            for (int q = 0; q < 9; q++) { o[q] = g.A1[q]; o[9 + q] = g.A2[q]; o[18 + q] = g.M[q]; }
-            o[27] = g.t[0]; o[28] = g.t[1]; o[29] = g.t[2];
-        }
-        if (t == 0) stm(mgeo + (size_t)W * 32, q2R(mkq(X.ex[6], X.ex[3], X.ex[4], X.ex[5])));
-        __syncthreads();
+        stage_pair_geo(X, mgeo, W, nt, [](const int p, int &i, int &j) { i = 0; j = p + 1; return true; });
         for (int w = t; w < F0c * per; w += nt) {
             int li = w / per, k = w - li * per + 1;
             int slot = list0[li];

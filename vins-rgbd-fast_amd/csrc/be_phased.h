@@ -12,7 +12,7 @@
 
 namespace {
 
-#define PS_LS_HEAD_DOUBLES (((int)(sizeof(Params) / sizeof(double)) + 1 & ~1) + 176)   // ps_line_search: evaluation point + scalar workspace + partial costs ahead of the roles' region
+#define PS_LS_HEAD_DOUBLES (((int)(sizeof(Params) / sizeof(double)) + 1 & ~1) + 176)   // ps_ls_kernel: evaluation point + scalar workspace + partial costs ahead of the roles' region
 #define PS_LVEC 14   // P-sized vectors ps_serial keeps in LDS (kernels.h ps_serial_lds_bytes sizes the launch with it)
 __device__ __forceinline__ bool ps_active(const SolveSt &st) { return st.stage != PS_IDLE && st.stage != PS_DONE; }
 __device__ __forceinline__ double *ps_imu_blk(const Ctx &c) { return c.pairblk + (size_t)((c.W + 1) * c.W / 2) * 210; }  // W x 768 doubles behind the pair blocks
@@ -295,99 +295,111 @@ __device__ __forceinline__ bool ps_blk(const Batch &B, int &s, int &b) {
     return r < B.ns;
 }
 
-// ONE evaluation role of a sequence ("block b" of ps_eval's grid) on 256 threads: b = 0 the prior, 1 / 2 the IMU factors (one work type per
-// wavefront), b >= 3 the projection residuals [256 rpt (b - 3), 256 rpt (b - 2)).  Returns the calling thread's share of the cost (the caller
-// block-sums it).  t = thread index within the role, act = the thread takes part: ps_eval runs a role per workgroup (all 256 threads active);
-// the line search of a bounds-constrained solve (ps_line_search, inside ps_serial's 512-thread workgroup) runs the roles one after the other on
-// its first 256 threads -- the barriers are unconditional, inactive threads only pass through them -- and gets the same bits.  LS = true adds
-// the directional derivative gradient . delta of the role's factors to gd (the IMU factors' share is formed by the caller from c.imu_raw)
-// and leaves the prior's vectors st.srp / st.sdx alone (they belong to the point ps_asm_b assembles).
+// The prior at X, on the calling workgroup's 256 threads: gradient q = b + A dx and cost 1/2 c0 + dx^T b + 1/2 dx^T A dx.  Threads t < n
+// (n = c.NPR prior rows) get their row's q and d = dx[t]; every thread's share of the cost is added to `cost` (the caller block-sums it).
+// dxs: 5 n + 1 doubles of workgroup-visible staging (dx, then the partial sums).  The one loop that reads prior_H by columns in the solver:
+// the bits of the cost and of q depend on its column order and on the order the partials are added in, and the trust-region test
+// (ps_eval / ps_evalf) and the line search (ps_ls) must see the same ones.
+__device__ __forceinline__ void ps_prior(const Batch &B, const int s, const Ctx &c, const Params &X, double *dxs, long long &ph_t0, double &cost, double &q, double &d) {
+    const int t = threadIdx.x, nt = 256, n = c.NPR;
+    double *pacc = dxs + ((n + 1) & ~1);
+    prior_dx(c, X, dxs, true);
+    PH(40);
+    // one thread per row, A read by columns (it is stored exactly symmetric), dx from the staging; up to four threads per row when they fit
+    // (n <= 64; three at W = 10), each over its share of the columns, every load of a thread in flight at once: the partials took 28 us of a
+    // 57 us launch as a runtime-bound loop with one load per iteration, 15 us in batches of eight
+    const int nch = max(1, min(4, nt / n));
+    if (t < nch * n) {
+        const int ch = t / n, row = t - ch * n;
+        const int per = (n + nch - 1) / nch, j0 = ch * per, j1 = min(n, j0 + per);
+        constexpr int MAXJ = 32;   // columns per trip (26 per thread at W = 10: one trip; eight per trip made 17 dependent round trips of the 136 columns at W = 20: 21 us)
+        double acc = 0;
+        for (int j = j0; j < j1; j += MAXJ) {
+            double hv[MAXJ];
+#pragma unroll
+            for (int u = 0; u < MAXJ; u++) hv[u] = c.prior_H[(size_t)min(j + u, j1 - 1) * n + row];
+#pragma unroll
+            for (int u = 0; u < MAXJ; u++) if (j + u < j1) acc += hv[u] * dxs[j + u];
+        }
+        pacc[ch * n + row] = acc;
+    }
+    __syncthreads();
+    PH(44);
+    if (t < n) {
+        double acc = pacc[t];
+        for (int ch = 1; ch < nch; ch++) acc += pacc[ch * n + t];   // (fixed order)
+        const double b0 = c.prior_r[t];
+        d = dxs[t]; q = b0 + acc;
+        cost += 0.5 * d * (b0 + q);
+    }
+    if (t == 0) cost += 0.5 * c.be->prior_c0;
+}
+
+// The pre-integration headers of the window's W IMU factors (state, Jacobian, whitening matrix: the first VIO_PREINT_HDR doubles of PreInt)
+// into the staging `pl`, VIO_PREINT_HDR + 1 doubles apart, on 256 threads; ends with the barrier behind which they may be read
+__device__ __forceinline__ void ps_stage_headers(const Ctx &c, double *pl) {
+    const int t = threadIdx.x, nt = 256, W = c.W;
+    constexpr int PH_LD = VIO_PREINT_HDR + 1;
+    // (ten loads in flight per thread and trip: the 19 loads a thread owns at W = 10 are two round trips instead of five)
+    for (int q0 = t; q0 < W * PH_LD; q0 += 10 * nt) {
+        double v[10];
+#pragma unroll
+        for (int u = 0; u < 10; u++) {
+            const int q = min(q0 + u * nt, W * PH_LD - 1), i = q / PH_LD, e = min(q - i * PH_LD, VIO_PREINT_HDR - 1);
+            v[u] = ((const double *)&c.pre[c.be->pre_idx[i + 1]])[e];
+        }
+#pragma unroll
+        for (int u = 0; u < 10; u++) if (q0 + u * nt < W * PH_LD) pl[q0 + u * nt] = v[u];
+    }
+    __syncthreads();
+}
+
+// ONE evaluation role of a sequence ("block b" of ps_eval's grid) on the calling workgroup's 256 threads: b = 0 the prior, 1 / 2 the IMU
+// factors (one work type per wavefront), b >= 3 the projection residuals [256 rpt (b - 3), 256 rpt (b - 2)).  Writes the
+// factors' records and returns the calling thread's share of the cost (the caller block-sums it).  The only text of these factors in the phased
+// solver: ps_eval_kernel runs one role per workgroup (LS = false), ps_ls_kernel -- the line search of a bounds-constrained solve, one
+// workgroup per sequence -- runs the roles one after the other (LS = true), and the step is accepted on the two sums having the same bits.
+// LS = true also adds the directional derivative gradient . delta of the role's factors to gd (the IMU factors' share is formed by the
+// caller from c.imu_raw) and leaves the prior's vectors st.srp / st.sdx alone (they belong to the point ps_asm_b assembles).
+// smem: the role's staging (ps_eval_lds_bytes: LDS in ps_eval, HBM in ps_ls); ph_t0: the caller's PH_INIT.
 template <bool LS>
 __device__ __forceinline__ double ps_eval_role(const Batch &B, const int s, const Ctx &c, SolveSt &st, const Params &X, const double *feat, const bool withJ,
-                                               const int b, const int t, const bool act, unsigned char *smem, const double *dlt, const double *lstl,
-                                               const double *lsl, double &gd) {
-    const int nt = 256;
+                                               const int b, unsigned char *smem, long long ph_t0, const double *dlt, const double *lstl, const double *lsl,
+                                               double &gd) {
+    const int t = threadIdx.x;
     const BeSeq &be = *c.be;
     const vio_config &cfg = c.C->c;
     const double cal_tr = c.K->tr;   // the sequence's rolling-shutter readout (Batch::cal)
     const bool vext = st.vext != 0;
-    const int W = c.W, W1 = W + 1, n = c.NPR;
+    const int W = c.W, W1 = W + 1;
     double cost = 0;
-    PH_INIT;
     if (b == 0) {
         if (be.has_prior) {
-            // prior gradient q = b + A dx and cost dx^T b + 1/2 dx^T A dx: one thread per row, A read by columns (it is stored exactly
-            // symmetric), dx from LDS
-            // (three threads per row, each over a third of the columns, partial sums added in a fixed order)
-            double *dxs = (double *)smem, *pacc = dxs + ((n + 1) & ~1);
+            double q = 0, d = 0;
             PH(45);
-            prior_dx(c, X, dxs, true);
-            PH(40);
-            // four threads per row when they fit (n <= 64), every load of a thread in flight at once: the partials took 28 us of a 57 us
-            // launch as a runtime-bound loop with one load per iteration, 15 us in batches of eight
-            const int nch = max(1, min(4, nt / n));
-            if (act && t < nch * n) {
-                const int ch = t / n, row = t - ch * n;
-                const int per = (n + nch - 1) / nch, j0 = ch * per, j1 = min(n, j0 + per);
-                constexpr int MAXJ = 32;   // columns per thread on the fast path (26 at W = 10 with three threads per row)
-                double acc = 0;
-                if (j1 - j0 <= MAXJ) {
-                    double hv[MAXJ];
-#pragma unroll
-                    for (int u = 0; u < MAXJ; u++) hv[u] = c.prior_H[(size_t)min(j0 + u, n - 1) * n + row];
-#pragma unroll
-                    for (int u = 0; u < MAXJ; u++) if (j0 + u < j1) acc += hv[u] * dxs[j0 + u];
-                } else
-                    for (int j = j0; j < j1; j += MAXJ) {   // larger windows: the same batches, several trips (eight loads per trip made 17 dependent round trips of the 136 columns at W = 20: 21 us)
-                        double hv[MAXJ];
-#pragma unroll
-                        for (int u = 0; u < MAXJ; u++) hv[u] = c.prior_H[(size_t)min(j + u, j1 - 1) * n + row];
-#pragma unroll
-                        for (int u = 0; u < MAXJ; u++) if (j + u < j1) acc += hv[u] * dxs[j + u];
-                    }
-                pacc[ch * n + row] = acc;
-            }
-            __syncthreads();
-            PH(44);
-            if (act && t < n) {
-                double acc = pacc[t];
-                for (int ch = 1; ch < nch; ch++) acc += pacc[ch * n + t];
-                const double b0 = c.prior_r[t], d = dxs[t], q = b0 + acc;
-                cost += 0.5 * d * (b0 + q);
+            ps_prior(B, s, c, X, (double *)smem, ph_t0, cost, q, d);
+            if (t < c.NPR) {
                 if (LS) {
                     // (relocalisation solve: the extrinsic's columns are lent to relo_Pose, the prior does not act on them -- ps_asm_b)
                     const int a = prior_map(t, W);
                     if (!(st.relo && a >= 15 * W1 && a < 15 * W1 + 6)) gd += q * dlt[a];
                 } else { st.srp[t] = q; st.sdx[t] = d; }
             }
-            if (act && t == 0) cost += 0.5 * be.prior_c0;
         }
     } else if (b <= 2) {
-        // IMU factors: pre-integration headers (state, Jacobian, whitening matrix: the first VIO_PREINT_HDR doubles of PreInt) staged in
-        // LDS, four loads in flight per thread
+        // IMU factors from the staged headers
         double *pl = (double *)smem;
         constexpr int PH_LD = VIO_PREINT_HDR + 1;
-        // (ten loads in flight per thread and trip: the 19 loads a thread owns at W = 10 are two round trips instead of five)
-        for (int q0 = act ? t : W * PH_LD; q0 < W * PH_LD; q0 += 10 * nt) {
-            double v[10];
-#pragma unroll
-            for (int u = 0; u < 10; u++) {
-                const int q = min(q0 + u * nt, W * PH_LD - 1), i = q / PH_LD, e = min(q - i * PH_LD, VIO_PREINT_HDR - 1);
-                v[u] = ((const double *)&c.pre[be.pre_idx[i + 1]])[e];
-            }
-#pragma unroll
-            for (int u = 0; u < 10; u++) if (q0 + u * nt < W * PH_LD) pl[q0 + u * nt] = v[u];
-        }
-        __syncthreads();
+        ps_stage_headers(c, pl);
         if (b == 1) PH(46);
         const v3 G = ld3(be.g);
         const int part_ = (b == 1 ? 0 : 4) + (t >> 6), i0 = t & 63;   // block 1: types 0 .. 3 on its four wavefronts, block 2: type 4
-        if (act && part_ <= 4 && !(b == 2 && (t >> 6) > 0))
+        if (part_ <= 4 && !(b == 2 && (t >> 6) > 0))
             for (int i = i0; i < W; i += 64) {
                 const int j = i + 1;
                 const PreInt &p = *(const PreInt *)(pl + (size_t)i * PH_LD);   // only the header fields are read
                 double *__restrict__ out = c.imu_raw + (size_t)i * 15 * 31;
-                // bf::imu_work_item, written out: the call costs this kernel's register-capped variant (ps_ls_kernel) spills
+                // bf::imu_work_item, written out: the call costs this function's register-capped instance (ps_ls_kernel) spills
                 if (!cfg.use_imu || bf::imu_solver_skips(p)) { if (part_ == 0) for (int k = 0; k < 15; k++) out[k * 31 + 30] = 0; continue; }
                 if (part_ == 0) {
                     double raw[15];
@@ -404,23 +416,13 @@ __device__ __forceinline__ double ps_eval_role(const Batch &B, const int s, cons
     } else {
         double *geo = (double *)smem;
         const int rpt = B.eval_rpt, r0 = 256 * rpt * (b - 3), nres = st.nres;
-        for (int p = act ? t : W1 * W1 + 1; p <= W1 * W1; p += nt) {
-            if (p == W1 * W1) { stm(geo + (size_t)p * 32, q2R(mkq(X.ex[6], X.ex[3], X.ex[4], X.ex[5]))); continue; }
-            const int i = p / W1, j = p - i * W1;
-            if (!(i < j) || c.pair_start[p + 1] == c.pair_start[p]) continue;
-            bf::PairGeo g;
-            bf::pair_geo(&X.pose[i * 7], &X.pose[j * 7], X.ex, g);
-            double *o = geo + (size_t)p * 32;
-            for (int q = 0; q < 9; q++) { o[q] = g.A1[q]; o[9 + q] = g.A2[q]; o[18 + q] = g.M[q]; }
-            o[27] = g.t[0]; o[28] = g.t[1]; o[29] = g.t[2];
-        }
-        __syncthreads();
+        stage_pair_geo(X, geo, W1 * W1, 256, [&](const int p, int &i, int &j) { return pair_of_square(c, W1, p, i, j); });
         const double *ricm = geo + (size_t)W1 * W1 * 32;
         // (round 5: rpt residuals per thread -- with two, the 7 projection workgroups of a sequence become 4 and a 64-sequence launch fits the
         // device's wave slots at this kernel's 216 VGPRs in one round instead of two)
         for (int u = 0; u < rpt; u++) {
             const int r = r0 + t + 256 * u;
-            if (!act || r >= nres) break;
+            if (r >= nres) break;
             const int slot = c.res_lm[r], k = c.res_k[r];   // k = 0: the landmark's relocalisation factor
             const int imu_i = c.lm_start[slot], imu_j = imu_i + (k > 0 ? k : 1);
             const bf::PairGeo &g = *(const bf::PairGeo *)(geo + (size_t)(imu_i * W1 + imu_j) * 32);
@@ -428,13 +430,16 @@ __device__ __forceinline__ double ps_eval_role(const Batch &B, const int s, cons
             if (k == 0) {
                 // relocalisation factor (estimator.cpp:1336-1340): ProjectionFactor(first observation, matched point of the old keyframe)
                 // on (para_Pose[start], relo_Pose, ex, inverse depth).  Its record carries d r / d relo_Pose in the extrinsic's columns
-                // (lent to relo_Pose for this solve) and zeros in the pose_j columns.
+                // (lent to relo_Pose for this solve) and zeros in the pose_j columns.  Two calls, NOT one with `withJ ? J : nullptr`: through that
+                // select J stays a stack object -- 336 bytes of private segment for the whole of ps_eval_kernel, on its rarest path
+                // 
                 double *out = c.res + (size_t)r * 42;
                 double J[40], oj[VIO_OBS_D];
                 const double *oi = obs_ptr(c, slot, imu_i);
                 for (int q = 0; q < VIO_OBS_D; q++) oj[q] = oi[q];
                 oj[0] = c.relo_xy[2 * slot]; oj[1] = c.relo_xy[2 * slot + 1]; oj[2] = 1.0;
-                bf::eval_projection(cfg, &X.pose[imu_i * 7], X.relo, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, oi, oj, false, rr, withJ ? J : nullptr);
+                if (withJ) bf::eval_projection(cfg, &X.pose[imu_i * 7], X.relo, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, oi, oj, false, rr, J);
+                else bf::eval_projection(cfg, &X.pose[imu_i * 7], X.relo, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, oi, oj, false, rr, nullptr);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
                 wgt = sqrt(1.0 / (1.0 + sq));
                 if (withJ) {
@@ -443,7 +448,7 @@ __device__ __forceinline__ double ps_eval_role(const Batch &B, const int s, cons
                         out[a * 20 + 18] = 0.0;
                         out[a * 20 + 19] = wgt * J[a * 20 + 19];
                     }
-                    out[40] = wgt * rr[0]; out[41] = wgt * rr[1];
+                    rec_put_wr(out, false, wgt, rr);
                 }
             } else if (vext) {
                 double *out = c.res + (size_t)r * 42;
@@ -451,7 +456,7 @@ __device__ __forceinline__ double ps_eval_role(const Batch &B, const int s, cons
                                          cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
                 if (withJ) {
-                    out[40] = wgt * rr[0]; out[41] = wgt * rr[1];
+                    rec_put_wr(out, false, wgt, rr);
                     // the extrinsic itself is constant while its columns serve relo_Pose: no Jacobian for it (Ceres evaluates none either)
                     if (st.relo) for (int d = 0; d < 6; d++) { out[12 + d] = 0.0; out[32 + d] = 0.0; }
                 }
@@ -460,7 +465,7 @@ __device__ __forceinline__ double ps_eval_role(const Batch &B, const int s, cons
                 bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
                                          cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt, 14, false);
                 sq = rr[0] * rr[0] + rr[1] * rr[1];
-                if (withJ) { out[13] = wgt * rr[0]; out[27] = wgt * rr[1]; }
+                if (withJ) rec_put_wr(out, true, wgt, rr);
             }
             cost += 0.5 * log(1.0 + sq);
             if (LS) {
@@ -497,13 +502,7 @@ __device__ __forceinline__ void ps_eval_body(const Batch &B) {
     if (st.stage != PS_EVAL_X0 && st.stage != PS_EVAL_C) return;
     if (st.fused || b >= st.n_eval_blocks) return;   // (fused solves are evaluated by ps_evalf_kernel)
     Ctx c = make_ctx(B, s);
-    const BeSeq &be = *c.be;
-    const vio_config &cfg = c.C->c;
-    const double cal_tr = c.K->tr;   // the sequence's rolling-shutter readout (Batch::cal)
     const bool cand = st.stage == PS_EVAL_C;
-    const double *feat = cand ? c.cfeat : c.feat;
-    const bool withJ = st.eval_with_J != 0, vext = st.vext != 0;
-    const int W = c.W, W1 = W + 1, n = c.NPR;
     __shared__ double sred[64];
     // the evaluation point in LDS: the factor code reads its parameters many times between stores to HBM (which the compiler must
     // assume to alias them), and every such re-read would be a dependent global load
@@ -513,158 +512,10 @@ __device__ __forceinline__ void ps_eval_body(const Batch &B) {
         for (int k = t; k < (int)(sizeof(Params) / sizeof(double)); k += nt) ((double *)&X)[k] = src[k];
     }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double cost = 0;
     PH_INIT;
     __syncthreads();
-    if (b == 0) {
-        if (be.has_prior) {
-            // prior gradient q = b + A dx and cost dx^T b + 1/2 dx^T A dx: one thread per row, A read by columns (it is stored exactly
-            // symmetric), dx from LDS
-            // (three threads per row, each over a third of the columns, partial sums added in a fixed order)
-            double *dxs = (double *)smem, *pacc = dxs + ((n + 1) & ~1);
-            PH(45);
-            prior_dx(c, X, dxs, true);
-            PH(40);
-            // four threads per row when they fit (n <= 64), every load of a thread in flight at once: the partials took 28 us of a 57 us
-            // launch as a runtime-bound loop with one load per iteration, 15 us in batches of eight
-            const int nch = max(1, min(4, nt / n));
-            if (t < nch * n) {
-                const int ch = t / n, row = t - ch * n;
-                const int per = (n + nch - 1) / nch, j0 = ch * per, j1 = min(n, j0 + per);
-                constexpr int MAXJ = 32;   // columns per thread on the fast path (26 at W = 10 with three threads per row)
-                double acc = 0;
-                if (j1 - j0 <= MAXJ) {
-                    double hv[MAXJ];
-#pragma unroll
-                    for (int u = 0; u < MAXJ; u++) hv[u] = c.prior_H[(size_t)min(j0 + u, n - 1) * n + row];
-#pragma unroll
-                    for (int u = 0; u < MAXJ; u++) if (j0 + u < j1) acc += hv[u] * dxs[j0 + u];
-                } else
-                    for (int j = j0; j < j1; j += MAXJ) {   // larger windows: the same batches, several trips (eight loads per trip made 17 dependent round trips of the 136 columns at W = 20: 21 us)
-                        double hv[MAXJ];
-#pragma unroll
-                        for (int u = 0; u < MAXJ; u++) hv[u] = c.prior_H[(size_t)min(j + u, j1 - 1) * n + row];
-#pragma unroll
-                        for (int u = 0; u < MAXJ; u++) if (j + u < j1) acc += hv[u] * dxs[j + u];
-                    }
-                pacc[ch * n + row] = acc;
-            }
-            __syncthreads();
-            PH(44);
-            if (t < n) {
-                double acc = pacc[t];
-                for (int ch = 1; ch < nch; ch++) acc += pacc[ch * n + t];
-                const double b0 = c.prior_r[t], d = dxs[t], q = b0 + acc;
-                st.srp[t] = q;
-                st.sdx[t] = d;
-                cost += 0.5 * d * (b0 + q);
-            }
-            if (t == 0) cost += 0.5 * be.prior_c0;
-        }
-    } else if (b <= 2) {
-        // IMU factors: pre-integration headers (state, Jacobian, whitening matrix: the first VIO_PREINT_HDR doubles of PreInt) staged in
-        // LDS, four loads in flight per thread
-        double *pl = (double *)smem;
-        constexpr int PH_LD = VIO_PREINT_HDR + 1;
-        // (ten loads in flight per thread and trip: the 19 loads a thread owns at W = 10 are two round trips instead of five)
-        for (int q0 = t; q0 < W * PH_LD; q0 += 10 * nt) {
-            double v[10];
-#pragma unroll
-            for (int u = 0; u < 10; u++) {
-                const int q = min(q0 + u * nt, W * PH_LD - 1), i = q / PH_LD, e = min(q - i * PH_LD, VIO_PREINT_HDR - 1);
-                v[u] = ((const double *)&c.pre[be.pre_idx[i + 1]])[e];
-            }
-#pragma unroll
-            for (int u = 0; u < 10; u++) if (q0 + u * nt < W * PH_LD) pl[q0 + u * nt] = v[u];
-        }
-        __syncthreads();
-        if (b == 1) PH(46);
-        const v3 G = ld3(be.g);
-        const int part_ = (b == 1 ? 0 : 4) + (t >> 6), i0 = t & 63;   // block 1: types 0 .. 3 on its four wavefronts, block 2: type 4
-        if (part_ <= 4 && !(b == 2 && (t >> 6) > 0))
-            for (int i = i0; i < W; i += 64) {
-                const int j = i + 1;
-                const PreInt &p = *(const PreInt *)(pl + (size_t)i * PH_LD);   // only the header fields are read
-                double *__restrict__ out = c.imu_raw + (size_t)i * 15 * 31;
-                // bf::imu_work_item, written out: the call costs this kernel's register-capped variant (ps_ls_kernel) spills
-                if (!cfg.use_imu || bf::imu_solver_skips(p)) { if (part_ == 0) for (int k = 0; k < 15; k++) out[k * 31 + 30] = 0; continue; }
-                if (part_ == 0) {
-                    double raw[15];
-                    bf::imu_raw_residual(p, G, &X.pose[i * 7], &X.sb[i * 9], &X.pose[j * 7], &X.sb[j * 9], raw);
-                    for (int r = 0; r < 15; r++) {
-                        double sacc = 0;
-                        for (int k = 0; k <= r; k++) sacc += p.sqrt_info[r * 15 + k] * raw[k];
-                        out[r * 31 + 30] = sacc;
-                        cost += 0.5 * sacc * sacc;
-                    }
-                } else if (withJ)
-                    bf::imu_raw_jacobian_part(p, G, &X.pose[i * 7], &X.sb[i * 9], &X.pose[j * 7], &X.sb[j * 9], part_ - 1, out, 31);
-            }
-    } else {
-        double *geo = (double *)smem;
-        const int rpt = B.eval_rpt, r0 = 256 * rpt * (b - 3), nres = st.nres;
-        for (int p = t; p <= W1 * W1; p += nt) {
-            if (p == W1 * W1) { stm(geo + (size_t)p * 32, q2R(mkq(X.ex[6], X.ex[3], X.ex[4], X.ex[5]))); continue; }
-            const int i = p / W1, j = p - i * W1;
-            if (!(i < j) || c.pair_start[p + 1] == c.pair_start[p]) continue;
-            bf::PairGeo g;
-            bf::pair_geo(&X.pose[i * 7], &X.pose[j * 7], X.ex, g);
-            double *o = geo + (size_t)p * 32;
-            for (int q = 0; q < 9; q++) { o[q] = g.A1[q]; o[9 + q] = g.A2[q]; o[18 + q] = g.M[q]; }
-            o[27] = g.t[0]; o[28] = g.t[1]; o[29] = g.t[2];
-        }
-        __syncthreads();
-        const double *ricm = geo + (size_t)W1 * W1 * 32;
-        // (round 5: rpt residuals per thread -- with two, the 7 projection workgroups of a sequence become 4 and a 64-sequence launch fits the
-        // device's wave slots at this kernel's 216 VGPRs in one round instead of two)
-        for (int u = 0; u < rpt; u++) {
-            const int r = r0 + t + 256 * u;
-            if (r >= nres) break;
-            const int slot = c.res_lm[r], k = c.res_k[r];   // k = 0: the landmark's relocalisation factor
-            const int imu_i = c.lm_start[slot], imu_j = imu_i + (k > 0 ? k : 1);
-            const bf::PairGeo &g = *(const bf::PairGeo *)(geo + (size_t)(imu_i * W1 + imu_j) * 32);
-            double rr[2], wgt = 1.0, sq;
-            if (k == 0) {
-                // relocalisation factor (estimator.cpp:1336-1340): ProjectionFactor(first observation, matched point of the old keyframe)
-                // on (para_Pose[start], relo_Pose, ex, inverse depth).  Its record carries d r / d relo_Pose in the extrinsic's columns
-                // (lent to relo_Pose for this solve) and zeros in the pose_j columns.
-                double *out = c.res + (size_t)r * 42;
-                double J[40], oj[VIO_OBS_D];
-                const double *oi = obs_ptr(c, slot, imu_i);
-                for (int q = 0; q < VIO_OBS_D; q++) oj[q] = oi[q];
-                oj[0] = c.relo_xy[2 * slot]; oj[1] = c.relo_xy[2 * slot + 1]; oj[2] = 1.0;
-                bf::eval_projection(cfg, &X.pose[imu_i * 7], X.relo, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, oi, oj, false, rr, withJ ? J : nullptr);
-                sq = rr[0] * rr[0] + rr[1] * rr[1];
-                wgt = sqrt(1.0 / (1.0 + sq));
-                if (withJ) {
-                    for (int a = 0; a < 2; a++) {
-                        for (int d = 0; d < 6; d++) { out[a * 20 + d] = wgt * J[a * 20 + d]; out[a * 20 + 6 + d] = 0.0; out[a * 20 + 12 + d] = wgt * J[a * 20 + 6 + d]; }
-                        out[a * 20 + 18] = 0.0;
-                        out[a * 20 + 19] = wgt * J[a * 20 + 19];
-                    }
-                    out[40] = wgt * rr[0]; out[41] = wgt * rr[1];
-                }
-            } else if (vext) {
-                double *out = c.res + (size_t)r * 42;
-                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
-                                         cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt);
-                sq = rr[0] * rr[0] + rr[1] * rr[1];
-                if (withJ) {
-                    out[40] = wgt * rr[0]; out[41] = wgt * rr[1];
-                    // the extrinsic itself is constant while its columns serve relo_Pose: no Jacobian for it (Ceres evaluates none either)
-                    if (st.relo) for (int d = 0; d < 6; d++) { out[12 + d] = 0.0; out[32 + d] = 0.0; }
-                }
-            } else {
-                double *out = c.res + (size_t)r * 28;
-                bf::eval_projection_pair(cfg, g, ricm, X.ex, feat[c.lm_pidx[slot]], X.td, cal_tr, obs_ptr(c, slot, imu_i), obs_ptr(c, slot, imu_j),
-                                         cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt, 14, false);
-                sq = rr[0] * rr[0] + rr[1] * rr[1];
-                if (withJ) { out[13] = wgt * rr[0]; out[27] = wgt * rr[1]; }
-            }
-            cost += 0.5 * log(1.0 + sq);
-        }
-    }
-    if (b == 0) PH(62); else if (b == 1) PH(63); else if (b == 3) PH(14);
+    double gd_unused = 0;
+    double cost = ps_eval_role<false>(B, s, c, st, X, cand ? c.cfeat : c.feat, st.eval_with_J != 0, b, smem, ph_t0, nullptr, nullptr, nullptr, gd_unused);
     cost = block_sum(cost, sred);
     // Hand-over of the partial cost to the block that finishes last WITHOUT __threadfence(): on gfx950 that fence is `buffer_wbl2 sc1` +
     // `buffer_inv sc1` -- a write-back AND an invalidate of the XCD's whole L2, 448 + 64 of them per 64-sequence launch, each one throwing out
@@ -956,49 +807,16 @@ __global__ __launch_bounds__(256) void ps_evalf_kernel(Batch B) {
     PH_INIT;
     __syncthreads();
     if (b == 0) {
-        // ---- prior gradient q = b + A dx and cost dx^T b + 1/2 dx^T A dx (the code of ps_eval's block 0), and the zero Gram blocks of frame pairs
-        // without residuals (ps_asm_b reads every pair)
-        double *dxs = (double *)smem, *pacc = dxs + ((n + 1) & ~1);
+        // ---- the prior (ps_prior, as ps_eval's block 0), and the zero Gram blocks of frame pairs without residuals (ps_asm_b reads every pair)
         if (withJ)
             for (int p = wave; p < W1 * W1; p += NW) {
                 const int i = p / W1, j = p - i * W1;
                 if (i < j && c.pair_start[p + 1] == c.pair_start[p]) { double *o = c.pairblk + (size_t)pair_slot(i, j, W1) * 210; for (int e = lane; e < 210; e += 64) o[e] = 0; }
             }
         if (be.has_prior) {
-            prior_dx(c, X, dxs, true);
-            const int nch = max(1, min(4, nt / n));
-            if (t < nch * n) {
-                // up to four threads per row, each over a share of the columns, every load of a thread in flight at once
-                const int ch = t / n, row = t - ch * n;
-                const int per = (n + nch - 1) / nch, j0 = ch * per, j1 = min(n, j0 + per);
-                constexpr int MAXJ = 32;
-                double acc = 0;
-                if (j1 - j0 <= MAXJ) {
-                    double hv[MAXJ];
-#pragma unroll
-                    for (int u = 0; u < MAXJ; u++) hv[u] = c.prior_H[(size_t)min(j0 + u, n - 1) * n + row];
-#pragma unroll
-                    for (int u = 0; u < MAXJ; u++) if (j0 + u < j1) acc += hv[u] * dxs[j0 + u];
-                } else
-                    for (int j = j0; j < j1; j += 8) {
-                        double hv[8];
-#pragma unroll
-                        for (int u = 0; u < 8; u++) hv[u] = c.prior_H[(size_t)min(j + u, j1 - 1) * n + row];
-#pragma unroll
-                        for (int u = 0; u < 8; u++) if (j + u < j1) acc += hv[u] * dxs[j + u];
-                    }
-                pacc[ch * n + row] = acc;
-            }
-            __syncthreads();
-            if (t < n) {
-                double acc = pacc[t];
-                for (int ch = 1; ch < nch; ch++) acc += pacc[ch * n + t];
-                const double b0 = c.prior_r[t], d = dxs[t], q = b0 + acc;
-                st.srp[t] = q;
-                st.sdx[t] = d;
-                cost += 0.5 * d * (b0 + q);
-            }
-            if (t == 0) cost += 0.5 * be.prior_c0;
+            double q = 0, d = 0;
+            ps_prior(B, s, c, X, (double *)smem, ph_t0, cost, q, d);
+            if (t < n) { st.srp[t] = q; st.sdx[t] = d; }
         }
         PH(62);
     } else if (b == 1) {
@@ -1007,17 +825,7 @@ __global__ __launch_bounds__(256) void ps_evalf_kernel(Batch B) {
         double *pl = (double *)smem;
         constexpr int PH_LD = VIO_PREINT_HDR + 1;
         double *rawl = pl + (size_t)W * PH_LD;                               // [W][15 x 31] raw Jacobians | whitened residual
-        for (int q0 = t; q0 < W * PH_LD; q0 += 10 * nt) {   // (ten loads in flight per thread and trip)
-            double v[10];
-#pragma unroll
-            for (int u = 0; u < 10; u++) {
-                const int q = min(q0 + u * nt, W * PH_LD - 1), i = q / PH_LD, e = min(q - i * PH_LD, VIO_PREINT_HDR - 1);
-                v[u] = ((const double *)&c.pre[be.pre_idx[i + 1]])[e];
-            }
-#pragma unroll
-            for (int u = 0; u < 10; u++) if (q0 + u * nt < W * PH_LD) pl[q0 + u * nt] = v[u];
-        }
-        __syncthreads();
+        ps_stage_headers(c, pl);
         {
             const v3 G = ld3(be.g);
             const int wt = wave;
@@ -1072,19 +880,13 @@ __global__ __launch_bounds__(256) void ps_evalf_kernel(Batch B) {
             oi_p = obs_ptr(c, slot_r, imu_i); oj_p = obs_ptr(c, slot_r, imu_i + k_r);
         }
         const int npairs = W1 * W / 2;
-        for (int q = t; q <= npairs; q += nt) {
-            if (q == npairs) { stm(geo + (size_t)q * 32, q2R(mkq(X.ex[6], X.ex[3], X.ex[4], X.ex[5]))); continue; }
-            if (((fis_early(st, pb, q) >> 16) & 0x3FF) == 0) continue;   // (only the pairs this chunk evaluates)
-            int i = 0, rem = q;
-            while (rem >= W1 - 1 - i) { rem -= W1 - 1 - i; i++; }
-            const int j = i + 1 + rem;
-            bf::PairGeo g;
-            bf::pair_geo(&X.pose[i * 7], &X.pose[j * 7], X.ex, g);
-            double *o = geo + (size_t)q * 32;
-            for (int e = 0; e < 9; e++) { o[e] = g.A1[e]; o[9 + e] = g.A2[e]; o[18 + e] = g.M[e]; }
-            o[27] = g.t[0]; o[28] = g.t[1]; o[29] = g.t[2];
-        }
-        __syncthreads();
+        stage_pair_geo(X, geo, npairs, nt, [&](const int q, int &i, int &j) {   // record = pair slot (i < j); only the pairs this chunk evaluates
+            if (((fis_early(st, pb, q) >> 16) & 0x3FF) == 0) return false;
+            i = 0; j = q;
+            while (j >= W1 - 1 - i) { j -= W1 - 1 - i; i++; }
+            j += i + 1;
+            return true;
+        });
         const double *ricm = geo + (size_t)npairs * 32;
         if (t < nin) {
             const int imu_j = imu_i + k_r;
@@ -1093,7 +895,7 @@ __global__ __launch_bounds__(256) void ps_evalf_kernel(Batch B) {
             double *out = rec + (size_t)t * 28;
             bf::eval_projection_pair(cfg, g, ricm, X.ex, inv_dep, X.td, cal_tr, oi_p, oj_p, cfg.estimate_td != 0, rr, withJ ? out : nullptr, true, &wgt, 14, false);
             const double sq = rr[0] * rr[0] + rr[1] * rr[1];
-            if (withJ) { out[13] = wgt * rr[0]; out[27] = wgt * rr[1]; }
+            if (withJ) rec_put_wr(out, true, wgt, rr);
             cost += 0.5 * log(1.0 + sq);
         }
         PH(14);
@@ -1935,7 +1737,7 @@ __global__ __launch_bounds__(256, 2) void ps_ls_kernel(Batch B) {   // (held to 
     ps_sel_rows(B, c, st.rowbuf);
     const BeSeq &be = *c.be;
     const vio_config &cfg = c.C->c;
-    // the evaluation roles of ps_eval_role's layout -- prior, IMU, IMU, then 256 eval_rpt projection residuals each -- counted from the residual
+    // the evaluation roles in ps_eval's layout -- prior, IMU, IMU, then 256 eval_rpt projection residuals each -- counted from the residual
     // list, NOT st.n_eval_blocks: a fused solve sets that from its own chunking (2 + chunks of PS_FUSE_CAP - W residuals), which in this layout
     // covers only part of the projection residuals (none with one chunk).  The handle's eligibility (W NP / 256 + 4 <= PS_MAX_EVAL_BLOCKS)
     // keeps the count within part[] / lpart's 64 slots; the min() only guards the arrays
@@ -1949,7 +1751,6 @@ __global__ __launch_bounds__(256, 2) void ps_ls_kernel(Batch B) {   // (held to 
     unsigned char *role_smem = B.ls_scratch + (size_t)s * ps_eval_lds_bytes(c.W);
     const double *stl = c.lvec + 4 * (size_t)c.NLs, *sl = c.lvec;
     const double *delta = c.vec + 8 * (size_t)c.LW;   // the unscaled tangent step ps_serial left in slot 8 of the step vectors
-    const bool act = true;
     double g0 = 0, dmax = 0;
     for (int a = t; a < P; a += nt) { const double d = delta[a]; g0 += d * c.vec[a]; dmax = fmax(dmax, fabs(d)); }   // initial_gradient = gradient . delta
     for (int k = t; k < Fa; k += nt) { const double d = stl[k] * sl[k]; g0 += d * c.gl[k]; dmax = fmax(dmax, fabs(d)); }
@@ -1964,7 +1765,8 @@ __global__ __launch_bounds__(256, 2) void ps_ls_kernel(Batch B) {   // (held to 
         __syncthreads();
         double gd = 0;
         for (int vb = 0; vb < nblk; vb++) {
-            double cost = ps_eval_role<true>(B, s, c, st, X, c.cfeat, true, vb, t, act, role_smem, delta, stl, sl, gd);
+            PH_INIT;
+            double cost = ps_eval_role<true>(B, s, c, st, X, c.cfeat, true, vb, role_smem, ph_t0, delta, stl, sl, gd);
             cost = block_sum(cost, sred);
             if (t == 0) lpart[vb] = cost;
             __threadfence_block();
