@@ -651,6 +651,24 @@ int vio_stage_schur(int variant, int nb, int nt, int Kpad, unsigned colmask, con
 /* be_marg's truncated pseudo-inverse (be_linalg.h marg_pinv15, n <= 15): Pinv of the symmetrised A with eigenvalues <= 1e-8 dropped; path_out = 0 if
  * the certified inverse served (every eigenvalue provably above 1e-6), 1 if the Jacobi eigen-decomposition did. */
 int vio_stage_pinv15(int n, const double *A, double *Pinv, int *path_out);
+/* One part of the literal marginalisation (vio_config.marg_exact = 1 / 2; be_kernels.hip marg_exact_finish, marg_literal_prior, marg_certificate) on
+ * caller-supplied data, as be_marg_exact_kernel runs it: one workgroup of nt threads (256 or 512), the same dynamic LDS.  md = 6 or 15 (pose /
+ * pose + speed-bias of frame 0), F0 = 0 .. 480 landmarks in the marginalised block (m = md + F0), n = 1 .. 6 VIO_MAXW + 16 kept parameters.
+ * mxl: the largest block whose eigen-decomposition runs LDS-resident; 0 = what a handle chooses (DevCfg::MXL), 1 .. 128 forces the switch to the
+ * HBM solver at that size.  All matrices row-major.
+ *   part 0  marg_exact_finish.  In: A (mq x mq, mq = md + n, nothing eliminated; only its md x md block is symmetrised), b (mq), Cl (F0 x ldc, the
+ *           landmarks' coupling rows, columns indexed like A's; ldc >= mq), Hll = d (F0), gl (F0), second_new (recorded in dbg[2]).
+ *           Out: Ainv_out = A_mm^+ (m x m), Ar_out (n x n), br_out (n), and everything part 1 returns.
+ *   part 1  marg_literal_prior.  In: A = A_r (n x n), b = b_r (n).  Out: J_out (n x n, row k = sqrt(lambda_k) v_k^T or zero), rf_out (n), H_out = J^T J
+ *           (n x n), r_out = J^T rf (n), scal2_out[0] = |rf|^2.
+ *   part 2  marg_certificate.  In: A = Pinv (md x md), pinv_direct, second_new, Cl (F0 x ldc, ldc >= md), Hll = 1 / d or 0 (F0).
+ *           Out: info8_out[2] = certified, scal2_out[1] = the bound on |A_mm^-1|_F.
+ * Pointers a part does not use may be NULL.  info8_out: [0] the effective mxl, [1] 1 if the guard words around every array the kernel may write
+ * kept their values, [2] certified (part 2), [3] [4] [5] BeSeq::dbg[0], [2], [4] after the call (-1 = not written; part 0 writes 0, second_new, m).
+ * VIO_EINVAL for any other argument and when the kernel's LDS would not fit a workgroup. */
+int vio_stage_marg_literal(int part, int md, int F0, int n, int ldc, int nt, int mxl, int pinv_direct, int second_new, const double *A, const double *b,
+                           const double *Cl, const double *Hll, const double *gl, double *Ainv_out, double *Ar_out, double *br_out, double *J_out,
+                           double *rf_out, double *H_out, double *r_out, double *scal2_out, int *info8_out);
 
 #ifdef __cplusplus
 }

@@ -439,10 +439,28 @@ def table_full(P):
     return st
 
 
+def w20_moving(P):
+    """window_size 20, the largest: n = 6 W + 16 = 136 prior parameters, beyond the 128 the LDS-resident eigen-solver of the literal marginalisation
+    covers.  W + 14 moving frames; not in CASES (the per-case suites run windows of 4 and 10), generated once per process like them"""
+    if "w20_moving" not in _built:
+        W = 20
+        cfg, sc, stamps = _moving(P, W + 14, window_size=W, speed=2.5)
+        _built["w20_moving"] = Stream("w20_moving", cfg, sc, stamps, about="a 20-frame window: the HBM branch of the literal prior")
+        _built["w20_moving"].frames()
+    return _built["w20_moving"]
+
+
 CASES = dict(standstill=standstill, standstill_short=standstill_short, imu_counts=imu_counts, imu_65=imu_65, hash_chain=hash_chain,
              reappear=reappear, thin=thin, depth_edges=depth_edges, short_tracks=short_tracks, table_full=table_full, w10_td=w10_td)
 PARITY_CASES = tuple(c for c in CASES if c not in ("imu_65", "table_full"))
 _built = {}
+
+
+def anchored(rec):
+    """landmarks of a frame's table that start in frame 0 with at least two observations: what the NEXT frame's MARGIN_OLD marginalisation
+    eliminates (in_problem), if they are not dynamic"""
+    lm = rec["lm"]
+    return int(np.count_nonzero((lm[:, 1] == 0) & (lm[:, 2] >= 2) & (lm[:, 6] == 0))) if len(lm) else 0
 
 
 def build(name, P):

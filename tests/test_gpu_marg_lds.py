@@ -165,11 +165,7 @@ def _run(P, st, upto):
     return out, cap
 
 
-def _anchored(rec):
-    """landmarks of a frame's table that start in frame 0 with at least two observations: what the NEXT frame's MARGIN_OLD marginalisation
-    eliminates (in_problem), if they are not dynamic"""
-    lm = rec["lm"]
-    return int(np.count_nonzero((lm[:, 1] == 0) & (lm[:, 2] >= 2) & (lm[:, 6] == 0))) if len(lm) else 0
+_anchored = BC.anchored
 
 
 def _reaches(name, st, ref, cap):

@@ -396,6 +396,88 @@ int vio_stage_rodrigues(int mode, int n, const double *in, double *out) {
     return VIO_OK;
 }
 
+// The literal marginalisation, one part at a time (kernels.h MargLiteralStage).  One scratch allocation holds every array the device code reads or
+// writes, each followed (the first also preceded) by MARG_STAGE_GUARD guard words; the whole allocation starts out as guard words, so an output the
+// kernel did not write shows as such.
+#define MARG_STAGE_GUARD 32
+int vio_stage_marg_literal(int part, int md, int F0, int n, int ldc, int nt, int mxl, int pinv_direct, int second_new, const double *A, const double *b,
+                           const double *Cl, const double *Hll, const double *gl, double *Ainv_out, double *Ar_out, double *br_out, double *J_out,
+                           double *rf_out, double *H_out, double *r_out, double *scal2_out, int *info8_out) {
+    if (part < 0 || part > 2 || (md != 6 && md != 15) || F0 < 0 || F0 > 480 || n < 1 || n > 6 * VIO_MAXW + 16 || (nt != 256 && nt != 512) || mxl < 0 ||
+        mxl > 128 || !A || !scal2_out || !info8_out)
+        return VIO_EINVAL;
+    const size_t m = (size_t)md + F0, mq = (size_t)md + n, N = (size_t)n;
+    if (part == 0 && (!b || ldc < (int)mq || (F0 > 0 && (!Cl || !Hll || !gl)) || !Ainv_out || !Ar_out || !br_out)) return VIO_EINVAL;
+    if (part == 1 && !b) return VIO_EINVAL;
+    if (part <= 1 && (!J_out || !rf_out || !H_out || !r_out)) return VIO_EINVAL;
+    if (part == 2 && (ldc < md || (F0 > 0 && (!Cl || !Hll)))) return VIO_EINVAL;
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    const int mxl_eff = mxl > 0 ? mxl : marg_exact_mxl(dev);
+    const size_t lds = std::max(marg_exact_lds_bytes(mxl_eff), marg_exact_hbm_lds_bytes());
+    if (!lds_fits((const void *)be_stage_marg_literal_kernel, lds, "be_stage_marg_literal")) return VIO_EINVAL;
+    // segment sizes in doubles (0 where the part does not touch the array)
+    enum { S_A, S_B, S_CL, S_HLL, S_GL, S_MARGE, S_MARGV, S_MARGW, S_VEC, S_PJ, S_PH, S_PR, S_PRF, S_SCAL, S_COUNT };
+    size_t sz[S_COUNT] = {0}, off[S_COUNT];
+    const bool lm = part != 1 && F0 > 0;
+    sz[S_A] = part == 0 ? mq * mq : part == 2 ? (size_t)md * md : 0;
+    sz[S_B] = part == 0 ? mq : 0;
+    sz[S_CL] = lm ? (size_t)F0 * ldc : 0; sz[S_HLL] = lm ? (size_t)F0 : 0; sz[S_GL] = lm && part == 0 ? (size_t)F0 : 0;
+    sz[S_MARGE] = part == 0 ? 3 * m * m + N * m : 0;   // as the handle sizes it, MX = m
+    if (part <= 1) { sz[S_MARGV] = N * N; sz[S_MARGW] = (N + 16) * (N + 16); sz[S_VEC] = N; sz[S_PJ] = N * N; sz[S_PH] = N * N; sz[S_PR] = N; sz[S_PRF] = N; }
+    sz[S_SCAL] = 2;
+    size_t total = MARG_STAGE_GUARD;
+    for (int k = 0; k < S_COUNT; k++) { off[k] = total; total += sz[k] + MARG_STAGE_GUARD; }
+    const double gval = -1.2345678901234567e300;
+    std::vector<double> hb(total, gval);
+    auto put = [&](int seg, const double *src, size_t count) { if (count) memcpy(&hb[off[seg]], src, count * sizeof(double)); };
+    if (part == 0) { put(S_A, A, mq * mq); put(S_B, b, mq); put(S_GL, gl, sz[S_GL]); }
+    if (part == 1) { put(S_MARGV, A, N * N); put(S_VEC, b, N); }
+    if (part == 2) put(S_A, A, (size_t)md * md);
+    put(S_CL, Cl, sz[S_CL]); put(S_HLL, Hll, sz[S_HLL]);
+    DevCfg hc;
+    memset(&hc, 0, sizeof(hc));
+    hc.MX = part == 0 ? (int)m : 0; hc.MXL = mxl_eff;
+    std::vector<BeSeq> hbe(1);
+    memset(hbe.data(), 0, sizeof(BeSeq));
+    for (int k = 0; k < 16; k++) hbe[0].dbg[k] = -1;
+    int hinfo[4] = {0, -1, -1, -1};
+    DevBuf<double> dbuf;
+    DevBuf<DevCfg> dcfg;
+    DevBuf<BeSeq> dbe;
+    DevBuf<int> dinfo;
+    HIPCHK(dbuf.alloc(total)); HIPCHK(dcfg.alloc(1)); HIPCHK(dbe.alloc(1)); HIPCHK(dinfo.alloc(4));
+    HIPCHK(dbuf.upload(hb.data(), total)); HIPCHK(dcfg.upload(&hc, 1)); HIPCHK(dbe.upload(hbe.data(), 1)); HIPCHK(dinfo.upload(hinfo, 4));
+    MargLiteralStage a;
+    memset(&a, 0, sizeof(a));
+    double *d = dbuf;
+    a.cfg = dcfg; a.be = dbe; a.info = dinfo;
+    a.A = d + off[S_A]; a.b = d + off[S_B]; a.Cl = d + off[S_CL]; a.Hll = d + off[S_HLL]; a.gl = d + off[S_GL];
+    a.margE = d + off[S_MARGE]; a.margV = d + off[S_MARGV]; a.margW = d + off[S_MARGW]; a.vec = d + off[S_VEC];
+    a.prior_J = d + off[S_PJ]; a.prior_H = d + off[S_PH]; a.prior_r = d + off[S_PR]; a.prior_rf = d + off[S_PRF]; a.scal = d + off[S_SCAL];
+    a.part = part; a.md = md; a.F0 = F0; a.n = n; a.ldc = ldc; a.pinv_direct = pinv_direct; a.second_new = second_new;
+    (void)raise_lds_limit((const void *)be_stage_marg_literal_kernel, lds);
+    be_stage_marg_literal_kernel<<<1, nt, lds>>>(a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<double> in(hb);
+    HIPCHK(dbuf.download(hb.data(), total)); HIPCHK(dinfo.download(hinfo, 4));
+    int good = 1;
+    for (size_t q = 0; q < MARG_STAGE_GUARD; q++) if (memcmp(&hb[q], &gval, sizeof(double)) != 0) good = 0;
+    for (int k = 0; k < S_COUNT; k++)
+        for (size_t q = 0; q < MARG_STAGE_GUARD; q++) if (memcmp(&hb[off[k] + sz[k] + q], &gval, sizeof(double)) != 0) good = 0;
+    // the inputs the device code only reads
+    for (int k : {(int)S_A, (int)S_B, (int)S_CL, (int)S_HLL, (int)S_GL})
+        if (sz[k] && memcmp(&hb[off[k]], &in[off[k]], sz[k] * sizeof(double)) != 0) good = 0;
+    auto get = [&](double *dst, size_t from, size_t count) { if (dst && count) memcpy(dst, &hb[from], count * sizeof(double)); };
+    if (part == 0) { get(Ainv_out, off[S_MARGE] + 2 * m * m, m * m); get(Ar_out, off[S_MARGV], N * N); get(br_out, off[S_VEC], N); }
+    if (part <= 1) { get(J_out, off[S_PJ], N * N); get(rf_out, off[S_PRF], N); get(H_out, off[S_PH], N * N); get(r_out, off[S_PR], N); }
+    scal2_out[0] = hb[off[S_SCAL]]; scal2_out[1] = hb[off[S_SCAL] + 1];
+    info8_out[0] = mxl_eff; info8_out[1] = good; info8_out[2] = hinfo[0]; info8_out[3] = hinfo[1]; info8_out[4] = hinfo[2]; info8_out[5] = hinfo[3];
+    info8_out[6] = 0; info8_out[7] = 0;
+    return VIO_OK;
+}
+
 int vio_stage_projection(const vio_config *cfg, const double *pose_i, const double *pose_j, const double *ex, double inv_dep, double td,
                          const double *obs_i, const double *obs_j, int use_td, double *r2, double *J46) {
     return stage_projection_impl(cfg, pose_i, pose_j, ex, inv_dep, td, obs_i, obs_j, use_td, 0, r2, J46);

@@ -2315,8 +2315,9 @@ __device__ __forceinline__ void solve_body(const Batch &B, int s, int *scratch, 
 // | inverse depths of the landmarks that start in frame 0] (md = 6 and F0 = 0 for MARGIN_SECOND_NEW).  Both eigen-decompositions are Householder
 // tridiagonalisation + implicit QL: LDS-resident where the block fits (sym_eig_lds), on the matrix in HBM scratch otherwise (sym_eig_hbm).
 // LDS layout of the literal marginalisation's eigen-decompositions: the matrix (ld = n | 1: conflict-free column access), then d / e / g and
-// the per-wavefront partial sums of sym_eig_tridiag_mt.  Host side: marg_exact_lds_bytes (vio_abi.hip) sizes the launch with the same formula.
+// the per-wavefront partial sums of sym_eig_tridiag_mt.  Host side: marg_exact_lds_bytes (kernels.h) sizes the launch with the same formula.
 #define MARG_EIG_AUX_DOUBLES (11 * EIG_LD)
+static_assert(MARG_EXACT_HBM_LDS_DOUBLES == SYM_EIG_HBM_LDS_DOUBLES, "kernels.h marg_exact_hbm_lds_bytes: the host sizes sym_eig_hbm's LDS");
 // Symmetric eigen-decomposition in LDS: A (n x n, ld) -> eigenvectors in place (columns), eigenvalues in d.  Householder tridiagonalisation over
 // the whole workgroup + implicit QL on one wavefront (be_linalg.h; the same pair be_prior_factor_kernel runs).  n <= 128 (tridiag_ql_wave).
 __device__ __forceinline__ void sym_eig_lds(double *Al, int n, int ld, double *aux) {
@@ -2506,6 +2507,45 @@ __device__ __noinline__ void marg_exact_finish(const Ctx &c, BeSeq &be, double *
     if (VIO_TIMERS && t == 0) be.dbg[9] = (int)(VIO_CLOCK() - tx0);
     if (t == 0) { be.dbg[0] = 0; be.dbg[2] = second_new ? 1 : 0; be.dbg[4] = m; }
     if (VIO_TIMERS && t == 0) be.dbg[10] = (int)(VIO_CLOCK() - tx0);
+}
+
+// The certificate of marg_exact = 2 (marg_body): |A_mm^-1|_F <= |S^-1|_F + 2 |T|_F + |D^-1|_F + |D^-1 B|_F |T|_F with A_mm = [[P, B^T], [B, D]],
+// S = P - B^T D^-1 B (Pinv = S^-1, md x md, LDS), T = S^-1 B^T D^-1; it needs D invertible (every landmark's d > eps) and the direct inverse of S.
+// Cl: the rows B (F0k x ldc), Hll: 1 / d.  The whole workgroup calls it; the answer (and *bound_out, if asked for) is thread 0's.
+__device__ __forceinline__ bool marg_certificate(const double *Pinv, int md, int pinv_direct, bool second_new, const double *Cl, int ldc, const double *Hll,
+                                                 int F0k, double *sred, double *bound_out) {
+    const int t = threadIdx.x, nt = blockDim.x;
+    __shared__ int cert_bad;
+    if (t == 0) cert_bad = pinv_direct ? 0 : 1;
+    __syncthreads();
+    double n_t = 0, n_d = 0, n_db = 0;
+    if (!second_new) {
+        for (int li = t; li < F0k; li += nt) {
+            const double dinv = Hll[li];             // 1 / d, or 0 where d <= eps (pseudo-inverse of the diagonal block)
+            if (!(dinv > 0.0)) cert_bad = 1;         // (benign race: every writer stores 1)
+            n_d += dinv * dinv;
+            for (int a = 0; a < md; a++) {
+                double tt = 0;
+                for (int bq = 0; bq < md; bq++) tt += Pinv[a * md + bq] * Cl[(size_t)li * ldc + bq];
+                tt *= dinv;
+                n_t += tt * tt;
+                const double db = dinv * Cl[(size_t)li * ldc + a];
+                n_db += db * db;
+            }
+        }
+    }
+    block_sum3(n_t, n_d, n_db, sred);
+    double n_s = 0;
+    for (int w = t; w < md * md; w += nt) n_s += Pinv[w] * Pinv[w];
+    n_s = block_sum(n_s, sred);
+    __syncthreads();
+    bool certified = false;
+    if (t == 0) {
+        const double bound = sqrt(n_s) + 2.0 * sqrt(n_t) + sqrt(n_d) + sqrt(n_db) * sqrt(n_t);
+        certified = !cert_bad && isfinite(bound) && bound > 0.0 && 1.0 / bound > 1e-7;   // ten times the cut
+        if (bound_out) *bound_out = bound;
+    }
+    return certified;
 }
 
 template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem_marg) {
@@ -2952,37 +2992,8 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
     __syncthreads();
     PH(21);
     if (lit2) {
-        // certificate: |A_mm^-1|_F <= |S^-1|_F + 2 |T|_F + |D^-1|_F + |D^-1 B|_F |T|_F with A_mm = [[P, B^T], [B, D]], S = P - B^T D^-1 B (the
-        // block A15 above), T = S^-1 B^T D^-1; it needs D invertible (every landmark's d > eps) and the direct inverse of S
-        __shared__ int cert_bad;
-        if (t == 0) cert_bad = pinv_direct ? 0 : 1;
-        __syncthreads();
-        double n_t = 0, n_d = 0, n_db = 0;
-        if (!second_new) {
-            const double *Cl = c.Hpl;
-            const int ldc = c.LW;
-            for (int li = t; li < F0k; li += nt) {
-                const double dinv = c.Hll[li];           // 1 / d, or 0 where d <= eps (pseudo-inverse of the diagonal block)
-                if (!(dinv > 0.0)) cert_bad = 1;         // (benign race: every writer stores 1)
-                n_d += dinv * dinv;
-                for (int a = 0; a < md; a++) {
-                    double tt = 0;
-                    for (int bq = 0; bq < md; bq++) tt += Pinv[a * md + bq] * Cl[(size_t)li * ldc + bq];
-                    tt *= dinv;
-                    n_t += tt * tt;
-                    const double db = dinv * Cl[(size_t)li * ldc + a];
-                    n_db += db * db;
-                }
-            }
-        }
-        block_sum3(n_t, n_d, n_db, sred);
-        double n_s = 0;
-        for (int w = t; w < md * md; w += nt) n_s += Pinv[w] * Pinv[w];
-        n_s = block_sum(n_s, sred);
-        __syncthreads();
+        const bool certified = marg_certificate(Pinv, md, pinv_direct, second_new, c.Hpl, c.LW, c.Hll, F0k, sred, nullptr);
         if (t == 0) {
-            const double bound = sqrt(n_s) + 2.0 * sqrt(n_t) + sqrt(n_d) + sqrt(n_db) * sqrt(n_t);
-            const bool certified = !cert_bad && isfinite(bound) && bound > 0.0 && 1.0 / bound > 1e-7;   // ten times the cut
             be.dbg[11] = certified ? 1 : 0;
             if (!certified) be.dbg[12] += 1;
         }
@@ -3389,6 +3400,30 @@ __global__ __launch_bounds__(256) void be_dyn_finalize_kernel(Batch B, int seq, 
     }
     __syncthreads();
     triangulate_with_depth(c, be.n_lm);
+}
+
+// stage test of the literal marginalisation (kernels.h MargLiteralStage): marg_exact_finish / marg_literal_prior / marg_certificate as be_marg_exact_kernel
+// calls them -- one workgroup of 256 or 512 threads, the dynamic LDS sized by the host with the production formulas, a Ctx that holds what they read
+__global__ __launch_bounds__(512) void be_stage_marg_literal_kernel(MargLiteralStage a) {
+    const int t = threadIdx.x, nt = blockDim.x;
+    __shared__ double sred[64];
+    __shared__ double Pinv[225];
+    Ctx c = {};
+    c.C = a.cfg; c.be = a.be; c.NPR = a.n; c.LW = a.ldc;
+    c.Hpl = a.Cl; c.Hll = a.Hll; c.gl = a.gl; c.vec = a.vec;
+    c.margE = a.margE; c.margV = a.margV; c.margW = a.margW;
+    c.prior_J = a.prior_J; c.prior_H = a.prior_H; c.prior_r = a.prior_r; c.prior_rf = a.prior_rf;
+    BeSeq &be = *c.be;
+    if (a.part == 0) marg_exact_finish(c, be, a.A, a.b, a.md, a.md + a.n, a.n, c.Hpl, a.ldc, a.F0, a.second_new != 0, sred);
+    else if (a.part == 1) marg_literal_prior(c, be, c.margV, c.vec, a.n, c.margW, sred);
+    else {
+        for (int w = t; w < a.md * a.md; w += nt) Pinv[w] = a.A[w];
+        __syncthreads();
+        const bool certified = marg_certificate(Pinv, a.md, a.pinv_direct, a.second_new != 0, c.Hpl, a.ldc, c.Hll, a.F0, sred, a.scal + 1);
+        if (t == 0) a.info[0] = certified ? 1 : 0;
+    }
+    __syncthreads();
+    if (t == 0) { a.scal[0] = be.prior_c0; a.info[1] = be.dbg[0]; a.info[2] = be.dbg[2]; a.info[3] = be.dbg[4]; }
 }
 
 // stage test of the device solvePnP: par6 = (rvec, tvec) in / out; trace4 (may be null) = outer iterations, lambda escalations, final

@@ -97,6 +97,27 @@ __global__ void be_solve_kernel_512(Batch B);
 __global__ void be_marg_kernel(Batch B);       // reduced system, frame blocks and landmark tables in LDS (vio_batch::marg_lds)
 __global__ void be_marg_hbm_kernel(Batch B);   // the same stage with them in HBM scratch: windows whose system does not fit, VIO_MARG_LDS = 0
 __global__ void be_marg_exact_kernel(Batch B);
+// dynamic LDS of be_marg_exact_kernel's LDS-resident eigen-decomposition of an m x m block (be_kernels.hip marg_exact_finish / marg_literal_prior)
+static inline size_t marg_exact_lds_bytes(int m) { return ((size_t)m * (m | 1) + 11 * (size_t)(6 * VIO_MAXW + 16)) * 8 + 64; }
+// ... and of the blocks that do not fit: sym_eig_hbm's vectors (be_linalg.h SYM_EIG_HBM_LDS_DOUBLES; be_kernels.hip asserts the two agree)
+#define MARG_EXACT_HBM_LDS_DOUBLES (7 * 512)
+static inline size_t marg_exact_hbm_lds_bytes() { return (size_t)MARG_EXACT_HBM_LDS_DOUBLES * 8 + 64; }
+// vio_stage_marg_literal: one part of the literal marginalisation (be_kernels.hip) on caller-supplied data, one workgroup.  Every array is a
+// segment of one scratch allocation of the host side (abi_stage.hip), which puts guard words between them; the kernel fills a Ctx from them.
+//   part 0  marg_exact_finish:   A (mq x mq, mq = md + n), b (mq), Cl (F0 x ldc), Hll = d (F0), gl (F0) -> margE (A_mm^+, A_rm A_mm^+), margV = A_r,
+//                                vec = b_r, the prior
+//   part 1  marg_literal_prior:  margV = A_r (n x n), vec = b_r -> prior_J, prior_rf, prior_H, prior_r, BeSeq::prior_c0
+//   part 2  marg_certificate:    A = Pinv (md x md), Cl, Hll = 1 / d or 0 -> info[0] = certified, scal[1] = the bound
+struct MargLiteralStage {
+    const DevCfg *cfg;   // MX, MXL
+    BeSeq *be;
+    double *A, *b, *Cl, *Hll, *gl;
+    double *margE, *margV, *margW, *vec, *prior_J, *prior_H, *prior_r, *prior_rf;
+    double *scal;        // [0] BeSeq::prior_c0, [1] the certificate's bound
+    int *info;           // [0] certified, [1 ..] BeSeq::dbg[0], [2], [4]
+    int part, md, F0, n, ldc, pinv_direct, second_new;
+};
+__global__ void be_stage_marg_literal_kernel(MargLiteralStage a);
 // phased solver (be_phased.h)
 __global__ void ps_setup_kernel(Batch B);
 __global__ void ps_eval_kernel(Batch B);

@@ -33,9 +33,6 @@ static size_t ingest_lds_bytes(const DevCfg &C, bool excalib) {
     return excalib ? std::max(ht, (size_t)4 * C.NP * sizeof(double) + 16) : ht;
 }
 
-// dynamic LDS of be_marg_exact_kernel's LDS-resident eigen-decomposition of an m x m block (be_kernels.hip marg_exact_finish)
-static size_t marg_exact_lds_bytes(int m) { return ((size_t)m * (m | 1) + 11 * (size_t)(6 * VIO_MAXW + 16)) * 8 + 64; }
-
 // Pending IMU samples arrive grouped by sequence (counting sort on the host keeps the push order inside a sequence): sample i of
 // sequence s = seq_of[i] is the (i - off[s])-th new sample of that sequence.  One thread per sample; the ring counters are advanced
 // by imu_commit_kernel afterwards (same stream), so every thread of the scatter sees the old count.
@@ -727,21 +724,7 @@ static int create_group_streams(vio_batch *h, vio_batch::Group &g, bool partitio
 
 // marg_exact: the largest block whose eigen-decomposition runs LDS-resident (DevCfg::MXL)
 static void size_marg_exact(vio_batch *h) {
-    h->hc.MXL = 0;
-    if (h->hc.MX > 0) {
-        // marg_exact: the eigen-decompositions of the literal marginalisation run LDS-resident for blocks up to MXL -- whatever the kernel's
-        // static LDS leaves of the workgroup's share (matrix with an odd leading dimension + the solver's vectors, be_kernels.hip
-        // MARG_EIG_AUX_DOUBLES), and never beyond the 128 rows tridiag_ql_wave covers
-        hipFuncAttributes fa;
-        int cap = 0;
-        if (hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) != hipSuccess || cap <= 0) cap = 160 * 1024;
-        if (hipFuncGetAttributes(&fa, (const void *)be_marg_exact_kernel) == hipSuccess) {
-            const long avail = (long)cap - (long)fa.sharedSizeBytes - 256;
-            int m = 0;
-            while (m < 128 && (long)marg_exact_lds_bytes(m + 1) <= avail) m++;
-            h->hc.MXL = m;
-        }
-    }
+    h->hc.MXL = h->hc.MX > 0 ? marg_exact_mxl(h->device) : 0;
 }
 
 // the launch knobs of the environment, read once per handle
@@ -863,7 +846,7 @@ static int size_launches(vio_batch *h) {
         size_t nbq = ((size_t)C.NPRIOR + 15) >> 4;
         h->lds_marg = std::max(std::max((size_t)nbq * (nbq + 1) / 2 * 2048, (size_t)2 * C.NPRIOR * 15 * 8), (size_t)PREINT_MANY_LDS_DOUBLES * 8) + 64;   // (the last: F / V of a chunk of the pre-integration merge)  // lower 16x16 tiles of the new prior (Cholesky for its constant term); before that T1 and A_mr
         if (C.MXL > 0) h->lds_marg = std::max(h->lds_marg, marg_exact_lds_bytes(C.MXL));
-        if (C.MX > 0) h->lds_marg = std::max(h->lds_marg, (size_t)7 * 512 * 8 + 64);   // sym_eig_hbm's vectors (SYM_EIG_HBM_LDS_DOUBLES)
+        if (C.MX > 0) h->lds_marg = std::max(h->lds_marg, marg_exact_hbm_lds_bytes());   // sym_eig_hbm's vectors (SYM_EIG_HBM_LDS_DOUBLES)
         {
             // VIO_MARG_LDS: the reduced system (A, b, b_r) behind the overlay region, where the kernel's static LDS leaves room for it and the
             // landmark tables of the window slide fit in A's place; otherwise (and for marg_exact) the HBM form with today's request

@@ -208,6 +208,20 @@ inline bool lds_fits(const void *fn, size_t dynamic_bytes, const char *name) {
     return false;
 }
 
+// marg_exact: the eigen-decompositions of the literal marginalisation run LDS-resident for blocks up to MXL (DevCfg::MXL) -- whatever
+// be_marg_exact_kernel's static LDS leaves of the workgroup's share (matrix with an odd leading dimension + the solver's vectors, be_kernels.hip
+// MARG_EIG_AUX_DOUBLES), and never beyond the 128 rows tridiag_ql_wave covers.  0 when the kernel's attributes cannot be read.
+inline int marg_exact_mxl(int device) {
+    hipFuncAttributes fa;
+    int cap = 0;
+    if (hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || cap <= 0) cap = 160 * 1024;
+    if (hipFuncGetAttributes(&fa, (const void *)be_marg_exact_kernel) != hipSuccess) return 0;
+    const long avail = (long)cap - (long)fa.sharedSizeBytes - 256;
+    int m = 0;
+    while (m < 128 && (long)marg_exact_lds_bytes(m + 1) <= avail) m++;
+    return m;
+}
+
 // A handle owns its device: entry points may be called from any host thread with any device current (one host thread per GPU
 // in one process, or a caller that moves between devices); the guard makes h->device current for the call and restores the caller's on return.
 struct DevGuard {
