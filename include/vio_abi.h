@@ -473,6 +473,11 @@ int vio_debug_snapshot_layout(vio_batch *h, int i, char *name64, int32_t *kind, 
  * sequences; per_seq (may be NULL): the same pair for every sequence, [S][2].  All zero on a handle created with VIO_PREINT_AHEAD=0.
  * Waits for all work of the handle. */
 int vio_debug_preint_ahead(vio_batch *h, int64_t *out2, int64_t *per_seq);
+/* Debug: the marginalisations that ran as two launches (VIO_MARG_SPLIT: be_marg_pre_kernel with the window slide, then be_marg_alg_kernel beside the
+ * next frame's be_ingest and ps_setup) since creation, summed over the sequences in *total; per_seq (may be NULL): the count of every sequence, [S].
+ * All zero on a handle that keeps the one be_marg launch (VIO_MARG_SPLIT=0, tracker lag 0, marg_exact, VO, dynamic_init, windows whose reduced
+ * system does not fit LDS).  Waits for all work of the handle. */
+int vio_debug_marg_split(vio_batch *h, int64_t *total, int64_t *per_seq);
 /* FeatureTracker public vectors after readImage (estimator_nodelet.cpp:337-343): returns count */
 int vio_get_tracks(vio_batch *h, int seq, int cap, int32_t *ids, int32_t *track_cnt, float *cur_pts_xy, float *cur_un_pts_xy,
                    float *pts_velocity_xy);

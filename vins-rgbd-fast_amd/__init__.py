@@ -697,6 +697,14 @@ class VioBatch:
         self._chk(self.L.vio_debug_preint_ahead(self.h, o.ctypes.data, ps.ctypes.data), "vio_debug_preint_ahead")
         return ps if per_seq else (int(o[0]), int(o[1]))
 
+    def marg_split_stats(self, per_seq=False):
+        """Marginalisations that ran as be_marg_pre + be_marg_alg (VIO_MARG_SPLIT) since creation, summed over the sequences; per_seq=True: an
+        [S] array instead.  Waits for the handle."""
+        o, ps = np.zeros(1, np.int64), np.zeros(self.S, np.int64)
+        self.L.vio_debug_marg_split.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.L.vio_debug_marg_split(self.h, o.ctypes.data, ps.ctypes.data), "vio_debug_marg_split")
+        return ps if per_seq else int(o[0])
+
     def ex_calibration(self, seq=0, history=False):
         """estimate_extrinsic = 2 (InitialEXRotation): dict(state = 2 calibrating / 1 calibrated / 0 not a mode-2 handle, pairs, success_frame
         (frames_processed after the frame that succeeded, -1 while calibrating), ric (3 x 3, current estimate), sv (4 singular values of the last

@@ -534,6 +534,22 @@ int vio_debug_preint_ahead(vio_batch *h, int64_t *out2, int64_t *per_seq) {
     return VIO_OK;
 }
 
+// debug: per sequence, the marginalisations that ran as be_marg_pre + be_marg_alg (VIO_MARG_SPLIT; MargSnap::frames); returns their sum in *total
+int vio_debug_marg_split(vio_batch *h, int64_t *total, int64_t *per_seq) {
+    VIO_ENTER(h, VIO_NO_SEQ, true);
+    if (!total) return VIO_EINVAL;
+    *total = 0;
+    if (per_seq) memset(per_seq, 0, (size_t)h->S * sizeof(int64_t));
+    if (!h->d_msnap) return VIO_OK;
+    for (int s = 0; s < h->S; s++) {
+        unsigned long long n = 0;
+        HIPCHK(hipMemcpy(&n, (const unsigned char *)(h->d_msnap + s) + offsetof(MargSnap, frames), sizeof(n), hipMemcpyDeviceToHost));
+        *total += (int64_t)n;
+        if (per_seq) per_seq[s] = (int64_t)n;
+    }
+    return VIO_OK;
+}
+
 // debug: accumulated in-kernel phase ticks (100 MHz) of sequence 0; reset != 0 clears them
 int vio_debug_phases(vio_batch *h, float *out128, int reset) {
     VIO_ENTER(h, VIO_NO_SEQ, true);

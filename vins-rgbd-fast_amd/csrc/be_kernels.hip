@@ -1924,7 +1924,10 @@ __device__ __forceinline__ void solve_epilogue(Ctx &c, const Params &X, double c
 
 // LDSA: the reduced system A, b, b_r and the frame blocks G_j live in the dynamic LDS (kernels.h marg_resident_lds_bytes) instead of c.margA / margB /
 // margV / vec / pairblk; LT: the window slide works on LDS copies of the landmark tables.  Compile-time, so that every loop addresses one address space.
-template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem_marg);
+// PART (kernels.h MargSnap): 0 = the whole stage, 1 = what must precede the window slide (be_marg_pre_kernel), 2 = the algebra from the hand-over
+// record (be_marg_alg_kernel); msnap / mlist: that record and the list of this sequence (PART != 0)
+template <bool EXACT, bool LDSA, int PART = 0> __device__ void marg_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem_marg,
+                                                                         MargSnap *msnap = nullptr, int *mlist = nullptr);
 template <bool LT> __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, unsigned char *smem_marg);
 
 // solve -> marginalise -> window slide for one sequence per workgroup (1024 threads); fusing the three stages makes the
@@ -1958,6 +1961,25 @@ __global__ __launch_bounds__(512) void be_marg_kernel(Batch B) {
     marg_body<false, true>(B, s, scratch, sred, smem);
     __syncthreads();
     finish_body<true>(B, s, scratch, pw, smem);
+}
+// VIO_MARG_SPLIT (kernels.h): the same stage as two launches.  The first holds whatever touches window state the next frame's be_ingest / ps_setup
+// share -- they follow it on the front-end stream, beside the second, which is the algebra and nothing else.
+__global__ __launch_bounds__(512) void be_marg_pre_kernel(Batch B, MargSnap *snap, int *mlist) {
+    const int s = blockIdx.x + B.s0;
+    __shared__ int scratch[2 * 512 + 8];
+    __shared__ double sred[64];
+    __shared__ PreWork pw;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    marg_body<false, true, 1>(B, s, scratch, sred, smem, snap + s, mlist + (size_t)s * 2 * B.gNL);
+    __syncthreads();
+    finish_body<true>(B, s, scratch, pw, smem);
+}
+__global__ __launch_bounds__(512) void be_marg_alg_kernel(Batch B, MargSnap *snap, const int *mlist) {
+    const int s = blockIdx.x + B.s0;
+    __shared__ int scratch[2 * 512 + 8];
+    __shared__ double sred[64];
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    marg_body<false, true, 2>(B, s, scratch, sred, smem, snap + s, const_cast<int *>(mlist) + (size_t)s * 2 * B.gNL);
 }
 // the same stage with the reduced system, the frame blocks and the landmark tables in HBM scratch (rounds 1 - 6): windows whose system does not fit
 // the workgroup's LDS (W = 12 and up) and VIO_MARG_LDS = 0
@@ -2548,14 +2570,21 @@ __device__ __forceinline__ bool marg_certificate(const double *Pinv, int md, int
     return certified;
 }
 
-template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem_marg) {
+template <bool EXACT, bool LDSA, int PART> __device__ void marg_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem_marg,
+                                                                     MargSnap *msnap, int *mlist) {
     static_assert(!(EXACT && LDSA), "the literal marginalisation keeps its system in HBM");
+    static_assert(PART == 0 || !EXACT, "the split runs the default marginalisation only");
     const int t = threadIdx.x, nt = blockDim.x;
     Ctx c = make_ctx(B, s);
     const DevCfg &C = *B.cfg;
     const vio_config &cfg = C.c;
     BeSeq &be = *c.be;
-    if (!be.do_marg || be.rebooted || be.frame_count < c.W) return;
+    // PART 2 decides nothing itself: the guards below were taken by PART 1, before the slide and the next frame's be_ingest rewrote what they read
+    if constexpr (PART == 2) { if (!msnap->active) return; }
+    else {
+        if (PART == 1 && t == 0) msnap->active = 0;
+        if (!be.do_marg || be.rebooted || be.frame_count < c.W) return;
+    }
     const int W = c.W, W1 = W + 1, n = c.NPR;
     const double eps = 1e-8;
     __shared__ Params X;
@@ -2564,8 +2593,8 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
     __shared__ int pp[VIO_MAXW * 3 + 10], qq[VIO_MAXW * 3 + 10];
     __shared__ double A15[225], V15[225], Pinv[225];
     __shared__ int newpresent[VIO_MAXW + 3];
-    const bool second_new = be.marginalization_flag != 0;
-    if (second_new && !(be.has_prior && be.prior_present[W - 1])) return;
+    const bool second_new = PART == 2 ? msnap->second_new != 0 : be.marginalization_flag != 0;
+    if (PART != 2 && second_new && !(be.has_prior && be.prior_present[W - 1])) return;
     // marg_exact: MarginalizationInfo::marginalize followed literally (marginalization_factor.cpp:281-315) -- the full m x m block of
     // pose 0, speed-bias 0 AND the landmarks that start in frame 0 goes through one truncated eigen-decomposition, and the new prior is
     // rebuilt from the truncated factors of the reduced system.  A parity instrument (one workgroup), not the hot path.
@@ -2582,6 +2611,10 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
     PH_INIT;
     const long long tk0 = VIO_CLOCK();
     // vector2double
+    constexpr int NX = (int)(offsetof(Params, relo) / sizeof(double));   // what a MargSnap carries of X
+    if constexpr (PART == 2) {
+        for (int k = t; k < NX; k += nt) ((double *)&X)[k] = ((const double *)&msnap->X)[k];
+    } else {
     if (t <= W) {
         int i = t;
         X.pose[i * 7 + 0] = be.Ps[i][0]; X.pose[i * 7 + 1] = be.Ps[i][1]; X.pose[i * 7 + 2] = be.Ps[i][2];
@@ -2595,9 +2628,22 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
         X.ex[3] = q.x; X.ex[4] = q.y; X.ex[5] = q.z; X.ex[6] = q.w;
         X.td = be.td;
     }
+    }
     if (t < W + 3) newpresent[t] = 0;
     __syncthreads();
-    if (t <= W) for (int k = 0; k < 7; k++) be.para_Pose[t][k] = X.pose[t * 7 + k];   // (the marginalisation's vector2double: see solve_epilogue)
+    if (PART != 2 && t <= W) for (int k = 0; k < 7; k++) be.para_Pose[t][k] = X.pose[t * 7 + k];   // (the marginalisation's vector2double: see solve_epilogue)
+    if constexpr (PART == 1) {
+        // the hand-over record: the slots of X the window fills (the rest of the LDS image is never read: every loop over frames stops at W)
+        for (int k = t; k < NX; k += nt) {
+            const bool set = k < (W + 1) * 7 || (k >= (VIO_MAXW + 1) * 7 && k < (VIO_MAXW + 1) * 7 + (W + 1) * 9) || k >= (VIO_MAXW + 1) * 16;
+            ((double *)&msnap->X)[k] = set ? ((const double *)&X)[k] : 0.0;
+        }
+        if (t == 0) {
+            msnap->second_new = second_new ? 1 : 0; msnap->pre1 = be.pre_idx[1]; msnap->F0c = 0;
+            for (int k = 0; k < 3; k++) msnap->g[k] = be.g[k];
+            msnap->active = 1;
+        }
+    }
     // reduced system over q = [m-block (md) | kept block (n)]
     const int md = second_new ? 6 : 15;
     const int mq = md + n;
@@ -2606,11 +2652,12 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
     double *const Ares = (double *)(smem_marg + marg_overlay_bytes(n, W, true));
     double *A = LDSA ? Ares : c.margA, *b = LDSA ? Ares + (size_t)(n + 15) * (n + 15) : c.margB;
     double *Gj = LDSA ? ovl : c.pairblk;   // frame blocks, W x 210
+    // index maps (canonical kept layout: pose slots 0..W-1, sb, ex, td)
+    const int rS = md + 6 * W, rE = md + 6 * W + 9, rT = md + 6 * W + 15;
+    if constexpr (PART != 1) {
     for (int i = t; i < mq * mq; i += nt) A[i] = 0;
     for (int i = t; i < mq; i += nt) b[i] = 0;
     __syncthreads();
-    // index maps (canonical kept layout: pose slots 0..W-1, sb, ex, td)
-    const int rS = md + 6 * W, rE = md + 6 * W + 9, rT = md + 6 * W + 15;
     // prior
     if (be.has_prior) {
         prior_dx(c, X, sdx);
@@ -2658,17 +2705,20 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
         }
         __syncthreads();
     }
+    }
     PH(16);
     if (!second_new) {
+        if constexpr (PART != 1) {
         // IMU factor (0,1)
-        PreInt &p1 = c.pre[be.pre_idx[1]];
+        PreInt &p1 = c.pre[PART == 2 ? msnap->pre1 : be.pre_idx[1]];
+        const v3 grav = PART == 2 ? ld3(msnap->g) : ld3(be.g);
         if (cfg.use_imu && bf::imu_marg_uses(p1)) {
             double *Jw = Gj;                // 15x30 whitened (the frame blocks' place, before they exist)
             double *raw = c.imu_raw;        // 15x31
             // five work types (whitened residual + four Jacobian column groups), each on its own wavefront, like evaluate()
             if ((t & 63) == 0) for (int part = t >> 6; part < 5; part += nt >> 6) {
                 double unused = 0;   // (the marginalisation has no use for the cost)
-                bf::imu_work_item(p1, false, ld3(be.g), &X.pose[0], &X.sb[0], &X.pose[7], &X.sb[9], part, true, raw, unused);
+                bf::imu_work_item(p1, false, grav, &X.pose[0], &X.sb[0], &X.pose[7], &X.sb[9], part, true, raw, unused);
             }
             __syncthreads();
             for (int w = t; w < 450; w += nt) {
@@ -2694,22 +2744,31 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
             if (t == 0) { newpresent[0] = 1; newpresent[W] = 1; }
             __syncthreads();
         }
+        }
         PH(17);
         // projection factors of landmarks first observed in frame 0; each landmark is eliminated on the fly:
         // contribution = J_q^T J_q - c c^T / d  with c = J_q^T J_l, d = J_l^T J_l (pseudo-inverse: dropped if d <= eps)
+        // (split: the list and each entry's observation count live in the marginalisation's own array -- pair_list and the landmark tables are
+        //  the next frame's by the time PART 2 reads them)
+        int *const list0 = PART ? mlist : c.pair_list;
+        const int *const lno0 = PART ? mlist + c.NL : nullptr;
+        auto lm_no0 = [&](int li) -> int { if constexpr (PART == 2) return lno0[li]; else return c.lm_nobs[list0[li]]; };
+        const int per = W;  // max residuals per landmark
+        int F0c;
+        if constexpr (PART != 2) {
         int nlm = be.n_lm;
         int *flag = c.lm_tmp, *offs = c.res_k;
         for (int k = t; k < nlm; k += nt) { int slot = c.lm_order[k]; flag[k] = (in_problem(c, slot) && c.lm_start[slot] == 0) ? 1 : 0; }
         __syncthreads();
         int F0 = block_scan_flags(flag, nlm, offs, scratch);
-        int *list0 = c.pair_list;
         for (int k = t; k < nlm; k += nt) if (flag[k]) list0[offs[k]] = c.lm_order[k];
         __syncthreads();
         // per landmark: evaluate residuals with loss correction, store J (2x20) r (2) per residual into c.res (cap checked)
-        const int per = W;  // max residuals per landmark
-        int F0c = min(F0, c.nres_cap / per);
+        F0c = min(F0, c.nres_cap / per);
+        } else F0c = msnap->F0c;
         if (exact) { F0c = min(F0c, min(C.MX - 15, 480)); F0x = F0c; }
         F0k = F0c;
+        if constexpr (PART != 2) {
         // frame-pair form like the solver (be_factors.h eval_projection_pair): the geometry of the pairs (0, k) once, in LDS
         __shared__ double mgeo[(VIO_MAXW + 1) * 32 + 16];
         stage_pair_geo(X, mgeo, W, nt, [](const int p, int &i, int &j) { i = 0; j = p + 1; return true; });
@@ -2728,7 +2787,13 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
             out[41] = wgt * rr[1];
         }
         __syncthreads();
+        }
         PH(18);
+        if constexpr (PART == 1) {
+            for (int li = t; li < F0c; li += nt) mlist[c.NL + li] = c.lm_nobs[list0[li]];
+            if (t == 0) msnap->F0c = F0c;
+        }
+        if constexpr (PART != 1) {
         // column map of a residual's 19 non-landmark columns into q: pose0 -> 0..5, pose_k -> md+6(k-1), ex, td
         // accumulate A_qq and b_q: thread per (a,b) over the union index set is irregular; use per-landmark dense rows:
         // c_l (mq), d_l, b_l, then A -= c c^T/d after adding the plain J^T J per residual.
@@ -2744,7 +2809,7 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
             for (int li0 = 0; li0 < F0c; li0 += ngrp) {
                 const int li = li0 + grp;
                 const bool act = li < F0c;
-                const int no = act ? c.lm_nobs[list0[li]] : 0;
+                const int no = act ? lm_no0(li) : 0;
                 double cm[13], dsum = 0, bsum = 0;
 #pragma unroll
                 for (int q = 0; q < 13; q++) cm[q] = 0;
@@ -2917,12 +2982,15 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
             }
         }
         for (int li = t; li < F0c; li += nt) {   // every writer stores the same value
-            int no = c.lm_nobs[list0[li]];
+            int no = lm_no0(li);
             for (int k = 1; k < no; k++) newpresent[k - 1] = 1;
             if (no > 1) { newpresent[W + 1] = 1; if (cfg.estimate_td) newpresent[W + 2] = 1; }
         }
         __syncthreads();
+        }
     }
+    if constexpr (PART == 1) return;   // (the window slide follows: be_marg_pre_kernel)
+    else {
     if (VIO_TIMERS && s == 0 && t == 0 && !second_new) B.timings[31] += 1.0f;
     PH(20);
     if (exact) marg_exact_finish(c, be, A, b, md, mq, n, c.Hpl, c.LW, F0x, second_new, sred);
@@ -3073,7 +3141,9 @@ template <bool EXACT, bool LDSA> __device__ void marg_body(const Batch &B, int s
     __syncthreads();
     if (t < W + 3) be.prior_present[t] = newpresent[t];
     if (t == 0) { be.has_prior = 1; be.dbg[3] = (int)(VIO_CLOCK() - tk0); }
+    if (PART == 2 && t == 0) msnap->frames++;
     PH(23);
+    }
 }
 
 // Estimator::setReloFrame (estimator.cpp:1728-1747) for sequence seq; the match points are already in B.relo_mp.  par = stamp, index,

@@ -97,6 +97,27 @@ __global__ void be_solve_kernel_512(Batch B);
 __global__ void be_marg_kernel(Batch B);       // reduced system, frame blocks and landmark tables in LDS (vio_batch::marg_lds)
 __global__ void be_marg_hbm_kernel(Batch B);   // the same stage with them in HBM scratch: windows whose system does not fit, VIO_MARG_LDS = 0
 __global__ void be_marg_exact_kernel(Batch B);
+// VIO_MARG_SPLIT: be_marg_kernel cut along its phase boundary, so that the next frame's be_ingest and ps_setup can run beside the algebra.
+//   be_marg_pre_kernel  everything that reads or writes window state shared with the next frame: the marginalisation's vector2double, the list of the
+//                       landmarks that start in frame 0 and their projection records (into Batch::res), then the window slide (finish_body)
+//   be_marg_alg_kernel  the algebra, from what the first one left in a MargSnap, the list, the records and the OLD prior: prior part, IMU factor, landmark
+//                       rows, frame blocks, rank update, elimination of the m-block, the new prior.  It reads nothing finish_body, be_ingest or ps_setup
+//                       write and writes nothing those two read.
+// Same device code (marg_body), same operands in the same order: the pair leaves the bits be_marg_kernel leaves.
+// One sequence's hand-over record.  Like PreAhead a per-call buffer of the handle (vio_batch::d_msnap), dead once be_marg_alg has run: in no table, in
+// no snapshot.  The list (mlist: [S][2][NL] integers, vio_batch::d_mlist) holds the slots of the landmarks that start in frame 0, then each entry's
+// observation count as it was before the slide.
+struct MargSnap {
+    Params X;                   // the window as the solve left it (relo is not carried)
+    double g[3];
+    int active;                 // this frame marginalises (be_marg_kernel's guards, taken before the slide)
+    int second_new;             // marginalization_flag != 0
+    int pre1;                   // pre_idx[1] before the slide: the pre-integration between frames 0 and 1
+    int F0c;                    // landmarks in the list (0 for MARGIN_SECOND_NEW)
+    unsigned long long frames;  // marginalisations of this sequence that took the split path (vio_debug_marg_split)
+};
+__global__ void be_marg_pre_kernel(Batch B, MargSnap *snap, int *mlist);
+__global__ void be_marg_alg_kernel(Batch B, MargSnap *snap, const int *mlist);
 // dynamic LDS of be_marg_exact_kernel's LDS-resident eigen-decomposition of an m x m block (be_kernels.hip marg_exact_finish / marg_literal_prior)
 static inline size_t marg_exact_lds_bytes(int m) { return ((size_t)m * (m | 1) + 11 * (size_t)(6 * VIO_MAXW + 16)) * 8 + 64; }
 // ... and of the blocks that do not fit: sym_eig_hbm's vectors (be_linalg.h SYM_EIG_HBM_LDS_DOUBLES; be_kernels.hip asserts the two agree)

@@ -239,7 +239,10 @@ int flush_imu_backend(vio_batch *h) {
         if (h->p_seq.empty()) return VIO_OK;
     }
     hipStream_t st = h->groups[0].stream;
-    for (auto &g : h->groups) HIPCHK(hipStreamWaitEvent(st, g.ev_fe, 0));
+    for (auto &g : h->groups) {
+        HIPCHK(hipStreamWaitEvent(st, g.ev_fe, 0));
+        if (g.have_ingest_ev) HIPCHK(hipStreamWaitEvent(st, g.ev_ingest, 0));   // (be_ingest, the last reader of the rings, may have run on the front-end stream: VIO_MARG_SPLIT)
+    }
     bool launched = false;
     int rc = flush_imu(h, st, &launched);
     if (rc != VIO_OK || !launched) return rc;
@@ -447,19 +450,31 @@ int dynamic_init_step(vio_batch *h, int s, const IngestSrc &src, bool *finalize)
     return VIO_OK;
 }
 
+// VIO_MARG_SPLIT: whether a vio_feed call of this handle takes the split order (vio_handle.h marg_split; size_launches has settled the rest)
+static bool split_feed(const vio_batch *h) {
+    return h->marg_split && h->tracker_lag == 1 && h->solve_mode == 1 && h->hc.MX == 0 && h->marg_lds && !h->hc.c.dynamic_init && !h->dyn_active;
+}
+
 // one_seq >= 0: only that sequence (vio_process_obs), otherwise every sequence of the group
-int launch_backend(vio_batch *h, vio_batch::Group &g, const uint16_t *d_depth, const IngestSrc &src, int one_seq = -1) {
+// split (vio_feed only, split_feed above): be_ingest and ps_setup of this frame run on the group's front-end stream, behind the previous frame's window
+// slide (ev_slide) and beside its be_marg_alg; the back-end stream joins at the first solver slot (ev_setup) and cuts this frame's marginalisation
+// in two in turn
+int launch_backend(vio_batch *h, vio_batch::Group &g, const uint16_t *d_depth, const IngestSrc &src, int one_seq = -1, bool split = false) {
     const DevCfg &C = h->hc;
     const int S = one_seq >= 0 ? 1 : g.n;
     hipStream_t st = g.stream;
+    hipStream_t st_in = split ? g.fe_stream : st;   // be_ingest and ps_setup
     Batch Bg = h->B;
     Bg.s0 = one_seq >= 0 ? one_seq : g.s0;
     const bool prof = one_seq < 0;
-    if (prof) PEV(h, 8);
-    if (C.exc) be_ingest_kernel<true><<<S, 256, ingest_lds_bytes(C, true), st>>>(Bg, d_depth, (size_t)C.c.width * C.c.height, src);
-    else be_ingest_kernel<false><<<S, 256, ingest_lds_bytes(C, false), st>>>(Bg, d_depth, (size_t)C.c.width * C.c.height, src);
-    if (prof) PEV(h, 9);
-    if (one_seq < 0) { (void)hipEventRecord(g.ev_ingest, st); g.have_ingest_ev = true; }  // tracker lag 1: the next frame's front-end starts here
+    if (split && g.have_slide_ev) HIPCHK(hipStreamWaitEvent(st_in, g.ev_slide, 0));
+    if (split && g.depth_wait) HIPCHK(hipStreamWaitEvent(st_in, g.depth_wait, 0));
+    g.depth_wait = nullptr;
+    if (prof) PEV_ON(h, 8, st_in);
+    if (C.exc) be_ingest_kernel<true><<<S, 256, ingest_lds_bytes(C, true), st_in>>>(Bg, d_depth, (size_t)C.c.width * C.c.height, src);
+    else be_ingest_kernel<false><<<S, 256, ingest_lds_bytes(C, false), st_in>>>(Bg, d_depth, (size_t)C.c.width * C.c.height, src);
+    if (prof) PEV_ON(h, 9, st_in);
+    if (one_seq < 0) { (void)hipEventRecord(g.ev_ingest, st_in); g.have_ingest_ev = true; }  // tracker lag 1: the next frame's front-end starts here
     if (h->dyn_active || (C.c.dynamic_init && one_seq >= 0)) {
         // some sequence of this handle is still INITIAL under static_init: 0: the host collects its image frame / runs the
         // initialisation between the two halves of the back-end (once per sequence; the steady state below never synchronises)
@@ -489,7 +504,8 @@ int launch_backend(vio_batch *h, vio_batch::Group &g, const uint16_t *d_depth, c
         const bool fuse_only = Bg.fuse > 0 && !C.c.estimate_extrinsic && !C.c.estimate_td && h->relo_frames <= 0 &&
                                (size_t)(C.W + 1) * C.c.max_cnt * 12 / 10 <= (size_t)PS_FUSE_MAXBLK * (PS_FUSE_CAP - C.W);
         Bg.fuse_only = fuse_only ? 1 : 0;
-        ps_setup_kernel<<<S, 512, 0, st>>>(Bg);
+        ps_setup_kernel<<<S, 512, 0, st_in>>>(Bg);
+        if (split) { HIPCHK(hipEventRecord(g.ev_setup, st_in)); HIPCHK(hipStreamWaitEvent(st, g.ev_setup, 0)); }
         const int slots = C.c.max_iterations + h->extra_slots;
         // XCD-aware block map (ps_blk): every block of a sequence on the XCD its one-block kernels run on
         const bool xm = h->xcd_map && S >= 8;
@@ -533,9 +549,19 @@ int launch_backend(vio_batch *h, vio_batch::Group &g, const uint16_t *d_depth, c
         HIPCHK(hipEventRecord(h->ev_state, st));
         h->state_pending = true;
     }
-    if (C.MX > 0) be_marg_exact_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);   // vio_config.marg_exact (parity instrument)
-    else if (h->marg_lds) be_marg_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);  // marginalisation + window slide (be_finish is fused into it)
-    else be_marg_hbm_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);
+    if (split) {
+        // the window slide first, then the algebra: the next frame's be_ingest (on fe_stream) waits for the first only
+        be_marg_pre_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg, h->d_msnap, h->d_mlist);
+        HIPCHK(hipEventRecord(g.ev_slide, st));
+        be_marg_alg_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg, h->d_msnap, h->d_mlist);
+    } else {
+        if (C.MX > 0) be_marg_exact_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);   // vio_config.marg_exact (parity instrument)
+        else if (h->marg_lds) be_marg_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);  // marginalisation + window slide (be_finish is fused into it)
+        else be_marg_hbm_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);
+        // (a later split frame of this handle orders its be_ingest behind this one's slide all the same; a handle that never splits records nothing)
+        if (h->marg_split) HIPCHK(hipEventRecord(g.ev_slide, st));
+    }
+    g.have_slide_ev = h->marg_split;
     if (prof) PEV(h, 11);
     HIPCHK(hipGetLastError());
     return VIO_OK;
@@ -745,6 +771,9 @@ static void read_knobs(vio_batch *h) {
     h->marg_threads = std::min(512, std::max(64, env_int("VIO_MARG_THREADS", h->marg_threads) & ~63));
     h->marg_lds = env_int("VIO_MARG_LDS", 1) != 0;
     h->preint_ahead = env_int("VIO_PREINT_AHEAD", 1) != 0;
+    // (default: on for handles of up to 128 sequences, like the front-end CU partition below -- beyond that the device is full, nothing idles beside
+    //  be_marg_alg and the extra launch costs 0.5 % at S = 512: profiles/marg_split_ab_runs.txt)
+    h->marg_split = env_int("VIO_MARG_SPLIT", h->S <= 128 ? 1 : 0) != 0;
     h->B.flags = env_int("VIO_FLAGS", 0);
 }
 
@@ -765,7 +794,7 @@ static int create_groups(vio_batch *h) {
         g.s0 = k * per;
         g.n = std::min(per, n_seq - g.s0);
         VIO_TRY(create_group_streams(h, g, /*partitioned=*/false));
-        for (hipEvent_t *e : {&g.ev_solve, &g.ev_fe, &g.ev_be, &g.ev_ingest}) VIO_TRY(new_event(h, e));
+        for (hipEvent_t *e : {&g.ev_solve, &g.ev_fe, &g.ev_be, &g.ev_ingest, &g.ev_slide, &g.ev_setup}) VIO_TRY(new_event(h, e));
     }
     h->stream = h->groups[0].stream; h->fe_stream = h->groups[0].fe_stream;
     return new_event(h, &h->ev_imu);
@@ -864,6 +893,17 @@ static int size_launches(vio_batch *h) {
     (void)raise_lds_limit((const void *)be_marg_kernel, (size_t)(h->lds_marg));
     (void)raise_lds_limit((const void *)be_marg_exact_kernel, (size_t)(h->lds_marg));
     (void)raise_lds_limit((const void *)be_marg_hbm_kernel, (size_t)(h->lds_marg));
+    // VIO_MARG_SPLIT: the two halves of be_marg_kernel, with its dynamic LDS each; only where that kernel itself is what the handle launches
+    h->marg_split = h->marg_split && h->marg_lds && h->d_msnap && h->d_mlist && h->solve_mode == 1;
+    if (h->marg_split) {
+        (void)raise_lds_limit((const void *)be_marg_pre_kernel, (size_t)(h->lds_marg));
+        (void)raise_lds_limit((const void *)be_marg_alg_kernel, (size_t)(h->lds_marg));
+        hipFuncAttributes fa;
+        int cap = 0;
+        if (hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) != hipSuccess || cap <= 0) cap = 160 * 1024;
+        for (const void *k : {(const void *)be_marg_pre_kernel, (const void *)be_marg_alg_kernel})
+            if (hipFuncGetAttributes(&fa, k) != hipSuccess || fa.sharedSizeBytes + h->lds_marg > (size_t)cap) h->marg_split = false;
+    }
     const bool excalib = C.c.estimate_extrinsic == 2;
     const void *ingest = excalib ? (const void *)be_ingest_kernel<true> : (const void *)be_ingest_kernel<false>;
     (void)raise_lds_limit(ingest, ingest_lds_bytes(C, excalib));
@@ -902,6 +942,9 @@ static int handle_init(vio_batch *h, int n_seq) {
     VIO_TRY(dev_alloc(h, &h->d_stamps, S)); VIO_TRY(dev_alloc(h, &h->d_modes, S)); VIO_TRY(dev_alloc(h, &h->d_rrel, S * 9)); VIO_TRY(dev_alloc(h, &h->d_r9, 16));
     VIO_TRY(dev_alloc(h, &h->d_in_n, S)); VIO_TRY(dev_alloc(h, &h->d_in_stamps, S)); VIO_TRY(dev_alloc(h, &h->d_in_ids, S * NP)); VIO_TRY(dev_alloc(h, &h->d_in_obs, S * NP * 7));
     if (h->preint_ahead && C.c.use_imu) VIO_TRY(dev_alloc(h, &h->d_ahead, S));   // (zeroed: no record is valid, the counters start at 0)
+    // VIO_MARG_SPLIT: the hand-over between be_marg_pre and be_marg_alg (zeroed: the counters start at 0).  VO handles keep the one kernel: their
+    // be_ingest borrows Batch::res, where the records wait for be_marg_alg
+    if (h->marg_split && C.c.use_imu && C.MX == 0 && !C.c.dynamic_init) { VIO_TRY(dev_alloc(h, &h->d_msnap, S)); VIO_TRY(dev_alloc(h, &h->d_mlist, S * 2 * (size_t)C.NL)); }
     B.gW = h->hc.W; B.gP = h->hc.P; B.gLW = h->hc.LW; B.gNL = h->hc.NL; B.gNP = h->hc.NP; B.gNRES = h->hc.NRES; B.gNPRIOR = h->hc.NPRIOR; B.gMX = h->hc.MX;
     HIPCHK(hipMemcpy(B.cfg, &h->hc, sizeof(DevCfg), hipMemcpyHostToDevice));
     VIO_TRY(create_groups(h));
@@ -996,7 +1039,9 @@ static int note_stage_read(vio_batch *h, hipEvent_t &ev, bool &have, hipStream_t
 }
 
 static int stage_inputs(vio_batch *h, vio_batch::Group &g, const uint8_t *gray, const uint16_t *depth, const double *stamps, int on_device,
-                        const uint8_t **dg, const uint16_t **dd, bool overlap = false) {
+                        const uint8_t **dg, const uint16_t **dd, bool overlap = false, bool ingest_on_fe = false) {
+    // ingest_on_fe (VIO_MARG_SPLIT): be_ingest, the reader of the depth image, runs on the front-end stream in this call, behind the front-end
+    // kernels -- which must not wait for the depth upload: launch_backend puts the wait in front of be_ingest (Group::depth_wait)
     // every group uploads its own slice on its own streams: in order with the kernels that consume it, no cross-group hazard
     const DevCfg &C = h->hc;
     size_t HW = (size_t)C.c.width * C.c.height, S = h->S, s0 = g.s0, n = g.n;
@@ -1065,7 +1110,8 @@ static int stage_inputs(vio_batch *h, vio_batch::Group &g, const uint8_t *gray, 
             if (g.have_rd_depth[p]) HIPCHK(hipStreamWaitEvent(cs2, g.ev_rd_depth[p], 0));
             HIPCHK(hipMemcpyAsync(buf + s0 * HW, depth + s0 * HW, n * HW * 2, hipMemcpyHostToDevice, cs2));
             HIPCHK(hipEventRecord(g.ev_up_depth[p], cs2));
-            HIPCHK(hipStreamWaitEvent(g.stream, g.ev_up_depth[p], 0));
+            if (ingest_on_fe) g.depth_wait = g.ev_up_depth[p];
+            else HIPCHK(hipStreamWaitEvent(g.stream, g.ev_up_depth[p], 0));
         } else
             HIPCHK(hipMemcpyAsync(buf + s0 * HW, depth + s0 * HW, n * HW * 2, hipMemcpyHostToDevice, g.stream));
         *dd = buf;
@@ -1152,7 +1198,8 @@ int vio_feed_modes(vio_batch *h, const uint8_t *gray, const uint16_t *depth_mm, 
         VIO_TRY(fe_wait(h, g));
         const uint8_t *dg = nullptr;
         const uint16_t *dd = nullptr;
-        VIO_TRY(stage_inputs(h, g, gray, depth_mm, nullptr, on_device, &dg, &dd, /*overlap=*/true));
+        const bool split = split_feed(h);
+        VIO_TRY(stage_inputs(h, g, gray, depth_mm, nullptr, on_device, &dg, &dd, /*overlap=*/true, split));
         const double tt1 = feed_trace ? now_us() : 0;
         VIO_TRY(stage_side_ring(h, g, stamps, modes));
         if (g.s0 == 0) HIPCHK(hipEventRecord(h->ev[0], g.fe_stream));
@@ -1172,7 +1219,7 @@ int vio_feed_modes(vio_batch *h, const uint8_t *gray, const uint16_t *depth_mm, 
             src.ahead = h->d_ahead;
         }
         VIO_TRY(be_wait(g));
-        VIO_TRY(launch_backend(h, g, dd, src));
+        VIO_TRY(launch_backend(h, g, dd, src, -1, split));
         if (!on_device) {
             VIO_TRY(note_stage_read(h, g.ev_rd_depth[g.flip], g.have_rd_depth[g.flip], g.stream));
             g.flip ^= 1;

@@ -48,6 +48,11 @@ struct vio_batch {
         hipEvent_t ev_host_fe = nullptr, ev_host_be = nullptr;
         bool host_fe_pending = false, host_be_pending = false;
         bool have_solve_ev = false, have_ingest_ev = false;
+        // ev_slide: the window slide of the last frame has run (recorded behind the kernel that holds finish_body, whichever it is); ev_setup: be_ingest
+        // and ps_setup of a frame that ran them on fe_stream (VIO_MARG_SPLIT) are done
+        hipEvent_t ev_slide = nullptr, ev_setup = nullptr;
+        bool have_slide_ev = false;
+        hipEvent_t depth_wait = nullptr;   // the depth upload this call's be_ingest on fe_stream still has to wait for (stage_inputs -> launch_backend)
         // vio_feed: stamps / frame modes of a call bounce through a library-owned page-locked ring, so the caller's arrays are free when the
         // call returns although the copies only run when fe_stream gets to them (tracker lag 1 holds that stream behind be_ingest)
         static constexpr int kSideRing = 16;
@@ -142,6 +147,14 @@ struct vio_batch {
     // d_ahead: the [S] records, a per-call buffer like d_stamps (allocated at vio_create where the knob is on and the handle has an IMU)
     bool preint_ahead = true;
     PreAhead *d_ahead = nullptr;
+    // VIO_MARG_SPLIT (default 1): vio_feed launches the marginalisation as be_marg_pre_kernel + be_marg_alg_kernel (kernels.h) and runs the NEXT frame's
+    // be_ingest and ps_setup on the group's front-end stream behind the first of them (Group::ev_slide), beside the second; the back-end stream picks
+    // the frame up at its first solver slot (Group::ev_setup).  Taken where the phased solver, the default marginalisation in LDS, an IMU, tracker lag 1
+    // and a whole-group feed come together and the handle does not initialise dynamically (vio_abi.hip split_feed); 0 = the one be_marg launch and the
+    // one-stream order everywhere.  d_msnap / d_mlist: the hand-over between the two kernels, per-call buffers like d_ahead.
+    bool marg_split = true;
+    MargSnap *d_msnap = nullptr;
+    int *d_mlist = nullptr;
     // VIO_SOLVE_MODE: 0 = persistent kernel (one workgroup per sequence for the whole solve), 1 = phased solver (be_phased.h, default)
     int solve_mode = 1;
     bool serial_big = false;          // the window's Schur complement does not fit LDS: ps_serial_big_kernel (HBM-resident tiles, streaming Cholesky)
@@ -166,6 +179,7 @@ struct vio_batch {
 };
 #define VIO_NK 10  // kernels per vio_feed: fe_begin pyrdown predict lk select fast add | be_ingest solve marg(+finish)
 #define VIO_NEV 12 // events per step: 0..7 bracket the front-end kernels on fe_stream, 8..11 the back-end kernels on stream
+#define PEV_ON(h, k, strm) do { if (g.s0 == 0 && (h)->prof_cur >= 0 && (h)->prof_cur < (h)->prof_steps) (void)hipEventRecord((h)->pev[(size_t)(h)->prof_cur * VIO_NEV + (k)], (strm)); } while (0)   // the same, on the stream the bracketed kernel runs on
 #define PEV(h, k) do { if (g.s0 == 0 && (h)->prof_cur >= 0 && (h)->prof_cur < (h)->prof_steps) (void)hipEventRecord((h)->pev[(size_t)(h)->prof_cur * VIO_NEV + (k)], (k) <= 7 ? g.fe_stream : g.stream); } while (0)
 
 // an integer knob from the environment (clamps stay with the caller)
