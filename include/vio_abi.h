@@ -349,6 +349,24 @@ int vio_get_latest_odometry_all(vio_batch *h, double *out, int on_device);
  * The bytes copied back grow with S * cap, whatever n_rows turns out to be: a poller sets cap near the rows it expects per poll.
  * INITIAL sequences and VO mode apply no sample: n_rows[s] = 0.  Samples the ring has overwritten (imu_capacity) are not applied. */
 int vio_get_imu_rate_odometry(vio_batch *h, const double *since, int cap, int32_t *n_rows, double *out, int on_device);
+/* pubPointCloud (visualization.cpp:328-407) and pubKeyframe (visualization.cpp:454-520) for every sequence: one launch and one copy for
+ * the whole batch, where vio_get_landmarks_ex + vio_get_window + vio_get_extrinsic take about a dozen copies per sequence.  Every list is
+ * in the order of f_manager.feature (the order of vio_get_landmarks).
+ *   counts     [S][4] host: n_cloud, n_margin, n_kf, kf_valid.  The full numbers, which may exceed cap.  kf_valid = 1 where the sequence is
+ *              NON_LINEAR, the last frame was processed and its marginalization_flag is MARGIN_OLD: the frames for which pubKeyframe
+ *              publishes.  n_kf = 0 otherwise.
+ *   kf_pose    [S][8]: Headers[W-2], Ps[W-2], Q(w, x, y, z) of Rs[W-2], the bits of row W-2 of vio_get_window.  Rows of sequences with
+ *              kf_valid = 0 are left untouched.
+ *   cloud      [S][cap][3]: the world point of every landmark pubPointCloud keeps (not dynamic, n_obs >= 2, start_frame < W-2, not
+ *              start_frame > 3W/4, solve_flag 1)
+ *   margin     [S][cap][3]: pubPointCloud's margin cloud (the same first tests, then start_frame 0, n_obs <= 2, solve_flag 1)
+ *   kf_points  [S][cap][8]: per landmark that spans window frame W-2 with start_frame < W-2 and solve_flag 1, dynamic or not: the world
+ *              point, then x, y, u, v of its observation in frame W-2 and its feature id
+ * Rows beyond min(count, cap) are left untouched.  Any of cloud, margin, kf_points may be NULL: that list is only counted; cap == 0 counts
+ * everything.  on_device != 0: kf_pose and the three lists are HBM addresses on the handle's device and only counts comes back to the host.
+ * The bytes copied back grow with S * cap whatever the counts turn out to be.  Reads only; waits for all work of the handle. */
+#define VIO_PUBLISH_BLOCK 256   /* landmarks per step of the list walk (the workgroup size of the launch) */
+int vio_publish_all(vio_batch *h, int cap, int32_t *counts, double *kf_pose, double *cloud, double *margin, double *kf_points, int on_device);
 /* Estimator::setReloFrame(frame_stamp, frame_index, match_points, relo_t, relo_r) (estimator.h:48-49, estimator.cpp:1728-1747) for
  * sequence seq: the window frame stamped frame_stamp has been matched with an old keyframe (pose relo_t / relo_r in the loop-closed
  * world, relo_r row-major); match_points[n][3] = (x, y) normalised point of the old keyframe and the feature id it matched (z), in
@@ -613,6 +631,17 @@ int vio_stage_projection_pair(const vio_config *cfg, const double *pose_i, const
  * (marginalization_factor.cpp:374-393), one thread per input: plus7[i] = Plus(x7[i], d6[i]); dx6[i] = (x - x0, 2 vec(q0^-1 q), negated unless
  * the scalar part of q0^-1 q is >= 0) for x = x7[i], x0 = x07[i].  Poses are (x y z qx qy qz qw). */
 int vio_stage_pose_ops(int n, const double *x7, const double *d6, const double *x07, double *plus7, double *dx6);
+/* The device routine behind vio_publish_all on the tables of one synthetic sequence.  tables: lm_order, lm_id, lm_start, lm_nobs, lm_solve_flag,
+ * lm_dyn ([NL] int32 each, lm_order = the live slots in list order), lm_depth [NL], lm_obs [NL][W+1][9] (x y z u v vx vy cur_td depth, the row of
+ * window frame f at (f + ring_base) % (W+1)), Ps [W+1][3], Rs [W+1][9] row-major, Headers [W+1], ric [9], tic [3]; flags3 = solver_flag,
+ * marginalization_flag, processed.  counts4, kf_pose8, cloud [cap][3], margin [cap][3], kf_points [cap][8] are in and out: they travel to the
+ * device as passed in and come back whole, so what the kernel did not write is what the caller put there.  Lists may be NULL as above. */
+typedef struct vio_publish_tables {
+    const int32_t *lm_order, *lm_id, *lm_start, *lm_nobs, *lm_solve_flag, *lm_dyn;
+    const double *lm_depth, *lm_obs, *Ps, *Rs, *Headers, *ric, *tic;
+} vio_publish_tables;
+int vio_stage_publish(int NL, int W, int n_lm, int ring_base, const vio_publish_tables *tables, const int32_t *flags3, int cap, int32_t *counts4,
+                      double *kf_pose8, double *cloud, double *margin, double *kf_points);
 /* The dense solve at the bottom of every trust-region step (Ceres DENSE_SCHUR on the reduced camera system, estimator.cpp:1251-1263;
  * Eigen LLT underneath) through the LDS-tile Cholesky of the solve kernels: S [16 nb][16 nb] row-major symmetric positive definite
  * (nb <= 11; 12 <= nb <= 24 or blocks = -7: the streaming factorisation of windows beyond 10 keyframes, tiles in HBM -- usec5 is then

@@ -228,9 +228,43 @@ class Estimator {
         }
         return out;
     }
+    // the margin cloud of pubPointCloud (visualization.cpp:368-406): xyz per landmark that starts in frame 0 with at most two
+    // observations; computed on the device (vio_publish_all), one copy
+    std::vector<double> marginCloud() {
+        int32_t counts[4];
+        const int cap = landmarkCapacity();
+        std::vector<double> out(3 * (size_t)cap);
+        check(vio_publish_all(h_, cap, counts, nullptr, nullptr, out.data(), nullptr, 0), "vio_publish_all");
+        out.resize(3 * (size_t)(counts[1] < cap ? counts[1] : cap));
+        return out;
+    }
+    // what pubKeyframe publishes (visualization.cpp:454-520): valid on the MARGIN_OLD frames of a NON_LINEAR estimator; pose = stamp,
+    // P(3), Q(w, x, y, z) of window frame WINDOW_SIZE - 2 (keyframe_pose); points = rows of 8: the world point, then x, y, u, v of the
+    // landmark's observation in that frame and its feature id (keyframe_point with its channels)
+    struct Keyframe {
+        bool valid;
+        double pose[8];
+        std::vector<double> points;
+    };
+    Keyframe keyframe() {
+        Keyframe kf;
+        int32_t counts[4];
+        const int cap = landmarkCapacity();
+        std::memset(kf.pose, 0, sizeof(kf.pose));
+        kf.points.resize(8 * (size_t)cap);
+        check(vio_publish_all(h_, cap, counts, kf.pose, nullptr, nullptr, kf.points.data(), 0), "vio_publish_all");
+        kf.valid = counts[3] != 0;
+        kf.points.resize(8 * (size_t)(counts[2] < cap ? counts[2] : cap));
+        return kf;
+    }
     vio_batch *handle() { return h_; }
 
   private:
+    int landmarkCapacity() {
+        int32_t c[3];
+        check(vio_get_capacity(h_, c), "vio_get_capacity");
+        return c[1];
+    }
     friend class FeatureTracker;
     static void check(int rc, const char *what) {
         if (rc < 0) throw std::runtime_error(std::string(what) + ": " + vio_last_error());

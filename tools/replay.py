@@ -10,7 +10,9 @@ setting); --gt then applies to the first recording.
 
     --save-at FRAME --snapshot FILE   (one recording) write the sequence's snapshot after frame FRAME to FILE, the replay's own state to FILE.json
     --resume FILE                     (one recording) restore FILE and continue behind the saved frame; --out then holds the rows from there on
-    --imu-rate-out FILE               (one recording) the IMU-rate poses (pubLatestOdometry: one row per IMU sample, the layout of --out)"""
+    --imu-rate-out FILE               (one recording) the IMU-rate poses (pubLatestOdometry: one row per IMU sample, the layout of --out)
+    --keyframes-out DIR               one kf_<slot>_<stamp ns>.npz per published keyframe (pubKeyframe: pose row and rows of 8, dataio.PublicationWriter)
+    --cloud-out FILE                  the last point cloud and margin cloud of every slot (pubPointCloud), one .npz"""
 import argparse
 import importlib
 import os
@@ -33,6 +35,8 @@ def parse_args(argv=None):
     ap.add_argument("--snapshot", default=None, help="snapshot file to write (its sidecar FILE.json holds the frame gate's state)")
     ap.add_argument("--resume", default=None, help="snapshot file to restore before replaying the frames behind it")
     ap.add_argument("--imu-rate-out", default=None, help="file for the IMU-rate poses: one row per IMU sample, the layout of --out")
+    ap.add_argument("--keyframes-out", default=None, help="directory for one .npz per published keyframe and slot")
+    ap.add_argument("--cloud-out", default=None, help="file (.npz) for the last point cloud and margin cloud of every slot")
     ap.add_argument("--lenient", action="store_true", help="warn instead of failing on settings outside the built hot path")
     a = ap.parse_args(argv)
     n = len(a.config)
@@ -52,6 +56,7 @@ def main(argv=None):
     a, triples = parse_args(argv)
     P = importlib.import_module("vins-rgbd-fast_amd")
     io = importlib.import_module("vins-rgbd-fast_amd.dataio")
+    pw = io.PublicationWriter(a.keyframes_out, a.cloud_out) if (a.keyframes_out or a.cloud_out) else None
     if len(triples) > 1:
         cfg, cals, extras = io.batch_config_from_yamls([t[0] for t in triples], P, strict=not a.lenient)
         for e in extras:
@@ -64,7 +69,7 @@ def main(argv=None):
             if e["camera"] is not None:   # KANNALA_BRANDT / MEI (dataio.config_from_yaml)
                 b.set_camera(i, e["camera"])
         all_rows = io.replay_many(b, recs, [t[2] for t in triples], freqs=[e["freq"] for e in extras],
-                                  frontend_freqs=[e["frontend_freq"] for e in extras])
+                                  frontend_freqs=[e["frontend_freq"] for e in extras], publish=pw)
         for (cfg_path, data, out), rec, rows in zip(triples, recs, all_rows):
             print("%s: %d frames, %d odometry rows -> %s" % (data, len(rec), len(rows), out))
         rows = all_rows[0]
@@ -79,10 +84,13 @@ def main(argv=None):
             b.set_camera(0, extra["camera"])
         rows = io.replay(b, rec, out, freq=extra["freq"], frontend_freq=extra["frontend_freq"],
                          save_at=a.save_at, snapshot=a.snapshot, resume=a.resume,  # freq / frontend_freq: estimator_nodelet.cpp:264-286
-                         imu_rate=a.imu_rate_out)
+                         imu_rate=a.imu_rate_out, publish=pw)
         print("%d frames, %d odometry rows -> %s" % (len(rec), len(rows), out))
         if a.imu_rate_out:
             print("IMU-rate poses -> %s" % a.imu_rate_out)
+    if pw is not None:
+        pw.close()
+        print("%d keyframes -> %s, clouds -> %s" % (pw.n_keyframes, a.keyframes_out, a.cloud_out))
     if a.gt and len(rows) > 3:
         gt = np.loadtxt(a.gt, comments="#", ndmin=2)
         gp = np.array([gt[np.argmin(np.abs(gt[:, 0] - t)), 1:4] for t in rows[:, 0]])

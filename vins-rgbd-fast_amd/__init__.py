@@ -194,6 +194,50 @@ class Status(C.Structure):
 FRAME_SKIP, FRAME_TRACK, FRAME_PUBLISH = 0, 1, 2
 
 
+PUBLISH_BLOCK = 256   # VIO_PUBLISH_BLOCK: landmarks per step of the publishers' list walk
+_PUBLISH_INT = ("lm_order", "lm_id", "lm_start", "lm_nobs", "lm_solve_flag", "lm_dyn")
+_PUBLISH_F64 = ("lm_depth", "lm_obs", "Ps", "Rs", "Headers", "ric", "tic")
+
+
+class PublishTables(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _PUBLISH_INT + _PUBLISH_F64]
+
+
+def stage_publish(tables, W, n_lm, ring_base, flags, cap, fill=None, lists=(True, True, True)):
+    """vio_stage_publish: the publishers' device routine on the tables of one synthetic sequence.  tables: dict of lm_order, lm_id, lm_start,
+    lm_nobs, lm_solve_flag, lm_dyn ([NL] integers), lm_depth [NL], lm_obs [NL, W+1, 9], Ps [W+1, 3], Rs [W+1, 3, 3], Headers [W+1], ric [3, 3],
+    tic [3]; flags = (solver_flag, marginalization_flag, processed).  Returns (counts [4], kf_pose [8], cloud [cap, 3], margin [cap, 3],
+    kf_points [cap, 8]) with every output pre-filled with `fill` (NaN by default; counts with -1), so what the kernel left alone still holds
+    it; lists[i] = False passes NULL for that list (it is counted only, and returned as None)."""
+    W, n_lm, ring_base, cap = int(W), int(n_lm), int(ring_base), int(cap)
+    if cap < 0:
+        raise ValueError("cap must be >= 0")
+    if not 2 <= W <= 20:
+        raise ValueError("W must be in 2 .. 20")
+    NL = len(np.asarray(tables["lm_order"]).reshape(-1))
+    if NL < 1:
+        raise ValueError("the tables must hold at least one slot")
+    shapes = dict(lm_depth=NL, lm_obs=NL * (W + 1) * 9, Ps=3 * (W + 1), Rs=9 * (W + 1), Headers=W + 1, ric=9, tic=3)
+    keep, t = [], PublishTables()
+    for name in _PUBLISH_INT + _PUBLISH_F64:
+        a = np.ascontiguousarray(tables[name], np.int32 if name in _PUBLISH_INT else np.float64).reshape(-1)
+        if a.size != shapes.get(name, NL):
+            raise ValueError("%s holds %d values, expected %d" % (name, a.size, shapes.get(name, NL)))
+        keep.append(a)
+        setattr(t, name, a.ctypes.data)
+    f = np.ascontiguousarray(flags, np.int32).reshape(-1)
+    if f.size != 3:
+        raise ValueError("flags = (solver_flag, marginalization_flag, processed)")
+    fill = np.nan if fill is None else float(fill)
+    counts, pose = np.full(4, -1, np.int32), np.full(8, fill)
+    out = [np.full((cap, w), fill) if on else None for w, on in zip((3, 3, 8), lists)]
+    L = lib()
+    rc = L.vio_stage_publish(NL, W, n_lm, ring_base, C.byref(t), f.ctypes.data, cap, counts.ctypes.data, pose.ctypes.data, *[_ptr(o) for o in out])
+    if rc != 0:
+        raise VioError("vio_stage_publish failed (%d): %s" % (rc, L.vio_last_error().decode()))
+    return counts, pose, out[0], out[1], out[2]
+
+
 def build(verbose=False):
     """Compile libvio_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
     r = subprocess.run(["make", "-j8", "-C", os.path.join(_HERE, "csrc")], capture_output=True, text=True)
@@ -284,6 +328,8 @@ def lib():
         L.vio_get_latest_odometry.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.vio_get_latest_odometry_all.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.vio_get_imu_rate_odometry.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.vio_publish_all.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
+        L.vio_stage_publish.argtypes = [C.c_int] * 4 + [C.POINTER(PublishTables), C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.vio_set_tracker_lag.argtypes = [C.c_void_p, C.c_int]
         L.vio_set_fisheye_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.vio_get_status_all.argtypes = [C.c_void_p, C.c_void_p]
@@ -819,6 +865,36 @@ class VioBatch:
         self._chk(self.L.vio_get_imu_rate_odometry(self.h, sp, cap, n.ctypes.data, rows.ctypes.data if cap > 0 else None, 0),
                   "vio_get_imu_rate_odometry")
         return n, rows
+
+    def publish(self, cap=None, on_device=False, lists=(True, True, True), fill=0.0):
+        """pubPointCloud and pubKeyframe of every sequence in one launch and one copy (vio_publish_all): dict(counts [S, 4] = n_cloud, n_margin,
+        n_kf, kf_valid; kf_pose [S, 8] = stamp, P(3), Q(wxyz) of window frame W-2; cloud [S, cap, 3]; margin [S, cap, 3]; kf_points [S, cap, 8] =
+        world point, x, y, u, v, feature id).  Rows beyond min(count, cap), and kf_pose where kf_valid is 0, hold `fill`; the counts may
+        exceed cap.  cap = None: the landmark capacity, so nothing is cut.  lists[i] = False: that list is only counted (None is returned for
+        it).  on_device = True: the rows and poses stay in HBM, in DeviceBuffers returned under the same keys."""
+        cap = self.capacity()["landmarks"] if cap is None else int(cap)
+        if cap < 0:
+            raise ValueError("cap must be >= 0")
+        if len(lists) != 3:
+            raise ValueError("lists = (cloud, margin, kf_points)")
+        S = self.S
+        counts = np.zeros((S, 4), np.int32)
+        names, widths = ("cloud", "margin", "kf_points"), (3, 3, 8)
+        if on_device:
+            pose = DeviceBuffer(S * 8 * 8)
+            pose.upload(0, np.full((S, 8), float(fill)))
+            bufs = []
+            for w, on in zip(widths, lists):
+                bufs.append(DeviceBuffer(max(S * cap * w, 1) * 8) if on else None)
+                if on and cap > 0:
+                    bufs[-1].upload(0, np.full((S, cap, w), float(fill)))
+            self._chk(self.L.vio_publish_all(self.h, cap, counts.ctypes.data, pose.ptr, *[None if b is None else b.ptr for b in bufs], 1),
+                      "vio_publish_all")
+            return dict(zip(("counts", "kf_pose") + names, [counts, pose] + bufs))
+        pose = np.full((S, 8), float(fill))
+        out = [np.full((S, cap, w), float(fill)) if on else None for w, on in zip(widths, lists)]
+        self._chk(self.L.vio_publish_all(self.h, cap, counts.ctypes.data, pose.ctypes.data, *[_ptr(o) for o in out], 0), "vio_publish_all")
+        return dict(zip(("counts", "kf_pose") + names, [counts, pose] + out))
 
     def set_relo_frame(self, seq, stamp, index, match_points, relo_t, relo_r):
         """Estimator::setReloFrame (estimator.cpp:1728-1747): match_points[n][3] = (x, y, feature id) ascending in id"""

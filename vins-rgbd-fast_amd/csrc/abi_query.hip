@@ -160,21 +160,22 @@ int vio_get_latest_odometry(vio_batch *h, int seq, double *out11) {
 
 // staging of the two batched getters below: at least `dev` doubles in HBM and `host` doubles of page-locked memory (nothing of the handle
 // is in flight when they are regrown: the callers have synchronised)
-static int odo_stage(vio_batch *h, size_t dev, size_t host) {
-    if (dev > h->odo_cap) {
-        dev_release(h, h->d_odo);
-        h->odo_cap = 0;
-        VIO_TRY(dev_alloc(h, &h->d_odo, dev, false));
-        h->odo_cap = dev;
+static int grow_stage(vio_batch *h, double *&d, size_t &d_cap, double *&hp, size_t &h_cap, size_t dev, size_t host) {
+    if (dev > d_cap) {
+        dev_release(h, d);
+        d_cap = 0;
+        VIO_TRY(dev_alloc(h, &d, dev, false));
+        d_cap = dev;
     }
-    if (host > h->h_odo_cap) {
-        pinned_release(h, h->h_odo);
-        h->h_odo_cap = 0;
-        VIO_TRY(pinned_alloc(h, &h->h_odo, host));
-        h->h_odo_cap = host;
+    if (host > h_cap) {
+        pinned_release(h, hp);
+        h_cap = 0;
+        VIO_TRY(pinned_alloc(h, &hp, host));
+        h_cap = host;
     }
     return VIO_OK;
 }
+static int odo_stage(vio_batch *h, size_t dev, size_t host) { return grow_stage(h, h->d_odo, h->odo_cap, h->h_odo, h->h_odo_cap, dev, host); }
 
 int vio_get_latest_odometry_all(vio_batch *h, double *out, int on_device) {
     VIO_ENTER(h, VIO_NO_SEQ, false);
@@ -214,6 +215,41 @@ int vio_get_imu_rate_odometry(vio_batch *h, const double *since, int cap, int32_
         n_rows[s] = cnt[s];
         const size_t m = (size_t)std::min(cnt[s], cap);
         if (!on_device && m > 0) memcpy(out + s * (size_t)cap * 11, hb + o_rows + s * (size_t)cap * 11, m * 11 * sizeof(double));
+    }
+    return VIO_OK;
+}
+
+int vio_publish_all(vio_batch *h, int cap, int32_t *counts, double *kf_pose, double *cloud, double *margin, double *kf_points, int on_device) {
+    VIO_ENTER(h, VIO_NO_SEQ, false);
+    if (cap < 0 || !counts) return VIO_EINVAL;
+    VIO_TRY(sync_all(h));
+    // staging, in doubles: counts [S][4] (int32), kf_pose [S][8], then (host output only) the lists that were asked for, [S][cap][3 | 3 | 8]
+    const size_t S = (size_t)h->S, o_pose = 2 * S, o_rows = o_pose + 8 * S, rows = S * (size_t)cap;
+    double *const dst[3] = {cloud, margin, kf_points};
+    const size_t width[3] = {3, 3, 8};
+    size_t off[3], total = o_rows;
+    for (int l = 0; l < 3; l++) {
+        off[l] = total;
+        if (!on_device && dst[l]) total += rows * width[l];
+    }
+    VIO_TRY(grow_stage(h, h->d_pub, h->pub_cap, h->h_pub, h->h_pub_cap, total, total));
+    double *d = h->d_pub, *hb = h->h_pub;
+    double *dev[3];
+    for (int l = 0; l < 3; l++) dev[l] = !dst[l] ? nullptr : (on_device ? dst[l] : d + off[l]);
+    pub_all_kernel<<<h->S, VIO_PUBLISH_BLOCK, 0, h->stream>>>(h->B, cap, (int *)d, on_device ? kf_pose : d + o_pose, dev[0], dev[1], dev[2]);
+    HIPCHK(hipGetLastError());
+    // one copy back: the counts and, for a host output, the poses and the rows behind them
+    HIPCHK(hipMemcpyAsync(hb, d, (on_device ? o_pose : total) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int32_t *cnt = (const int32_t *)hb;
+    memcpy(counts, cnt, S * 4 * sizeof(int32_t));
+    if (on_device) return VIO_OK;
+    for (size_t s = 0; s < S; s++) {
+        if (kf_pose && cnt[4 * s + 3]) memcpy(kf_pose + 8 * s, hb + o_pose + 8 * s, 8 * sizeof(double));
+        for (int l = 0; l < 3; l++) {
+            const size_t m = (size_t)std::min(cnt[4 * s + l], cap);
+            if (dst[l] && m > 0) memcpy(dst[l] + s * (size_t)cap * width[l], hb + off[l] + s * (size_t)cap * width[l], m * width[l] * sizeof(double));
+        }
     }
     return VIO_OK;
 }

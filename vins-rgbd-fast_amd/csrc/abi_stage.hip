@@ -487,4 +487,64 @@ int vio_stage_projection_residual(const vio_config *cfg, const double *pose_i, c
     return stage_projection_impl(cfg, pose_i, pose_j, ex, inv_dep, td, obs_i, obs_j, use_td, 1, r2, J46);
 }
 
+int vio_stage_publish(int NL, int W, int n_lm, int ring_base, const vio_publish_tables *t, const int32_t *flags3, int cap, int32_t *counts4,
+                      double *kf_pose8, double *cloud, double *margin, double *kf_points) {
+    if (NL < 1 || W < 2 || W > VIO_MAXW || cap < 0 || !t || !flags3 || !counts4 || !kf_pose8) return VIO_EINVAL;
+    if (!t->lm_order || !t->lm_id || !t->lm_start || !t->lm_nobs || !t->lm_solve_flag || !t->lm_dyn || !t->lm_depth || !t->lm_obs || !t->Ps ||
+        !t->Rs || !t->Headers || !t->ric || !t->tic)
+        return VIO_EINVAL;
+    const size_t nl = (size_t)NL, W1 = (size_t)W + 1, c = (size_t)cap;
+    // integers: the six tables, then counts; doubles: depth, observations, window, extrinsic, then the outputs (one more row each: cap may be 0)
+    DevBuf<int> di;
+    DevBuf<double> dd;
+    const size_t o_cnt = 6 * nl;
+    const size_t o_obs = nl, o_ps = o_obs + nl * W1 * VIO_OBS_D, o_rs = o_ps + 3 * W1, o_hd = o_rs + 9 * W1, o_ric = o_hd + W1, o_tic = o_ric + 9,
+                 o_pose = o_tic + 3, o_cloud = o_pose + 8, o_margin = o_cloud + 3 * (c + 1), o_kf = o_margin + 3 * (c + 1), n_d = o_kf + 8 * (c + 1);
+    HIPCHK(di.alloc(o_cnt + 4));
+    HIPCHK(dd.alloc(n_d));
+    const int32_t *tabs[6] = {t->lm_order, t->lm_id, t->lm_start, t->lm_nobs, t->lm_solve_flag, t->lm_dyn};
+    for (int k = 0; k < 6; k++) HIPCHK(di.upload(tabs[k], nl, k * nl));
+    HIPCHK(di.upload(counts4, 4, o_cnt));
+    HIPCHK(dd.upload(t->lm_depth, nl));
+    HIPCHK(dd.upload(t->lm_obs, nl * W1 * VIO_OBS_D, o_obs));
+    HIPCHK(dd.upload(t->Ps, 3 * W1, o_ps));
+    HIPCHK(dd.upload(t->Rs, 9 * W1, o_rs));
+    HIPCHK(dd.upload(t->Headers, W1, o_hd));
+    HIPCHK(dd.upload(t->ric, 9, o_ric));
+    HIPCHK(dd.upload(t->tic, 3, o_tic));
+    HIPCHK(dd.upload(kf_pose8, 8, o_pose));
+    if (cloud && c) HIPCHK(dd.upload(cloud, 3 * c, o_cloud));
+    if (margin && c) HIPCHK(dd.upload(margin, 3 * c, o_margin));
+    if (kf_points && c) HIPCHK(dd.upload(kf_points, 8 * c, o_kf));
+    // the row behind each list is a guard: a write at or beyond row `cap` fails the call
+    const double guard[8] = {-1.5e300, -1.5e300, -1.5e300, -1.5e300, -1.5e300, -1.5e300, -1.5e300, -1.5e300};
+    HIPCHK(dd.upload(guard, 3, o_cloud + 3 * c));
+    HIPCHK(dd.upload(guard, 3, o_margin + 3 * c));
+    HIPCHK(dd.upload(guard, 8, o_kf + 8 * c));
+    PubIn in;
+    in.lm_order = di; in.lm_id = di + nl; in.lm_start = di + 2 * nl; in.lm_nobs = di + 3 * nl; in.lm_solve_flag = di + 4 * nl; in.lm_dyn = di + 5 * nl;
+    in.lm_depth = dd; in.lm_obs = dd + o_obs;
+    in.n_lm = n_lm; in.NL = NL; in.W = W; in.ring_base = ring_base;
+    in.Ps = dd + o_ps; in.Rs = dd + o_rs; in.Headers = dd + o_hd; in.ric = dd + o_ric; in.tic = dd + o_tic;
+    in.solver_flag = flags3[0]; in.marginalization_flag = flags3[1]; in.processed = flags3[2];
+    PubOut out;
+    out.cap = cap; out.counts = di + o_cnt; out.kf_pose = dd + o_pose;
+    out.cloud = cloud ? dd + o_cloud : nullptr; out.margin = margin ? dd + o_margin : nullptr; out.kf_points = kf_points ? dd + o_kf : nullptr;
+    pub_stage_kernel<<<1, VIO_PUBLISH_BLOCK>>>(in, out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(di.download(counts4, 4, o_cnt));
+    HIPCHK(dd.download(kf_pose8, 8, o_pose));
+    if (cloud && c) HIPCHK(dd.download(cloud, 3 * c, o_cloud));
+    if (margin && c) HIPCHK(dd.download(margin, 3 * c, o_margin));
+    if (kf_points && c) HIPCHK(dd.download(kf_points, 8 * c, o_kf));
+    double back[14];
+    HIPCHK(dd.download(back, 3, o_cloud + 3 * c));
+    HIPCHK(dd.download(back + 3, 3, o_margin + 3 * c));
+    HIPCHK(dd.download(back + 6, 8, o_kf + 8 * c));
+    for (int k = 0; k < 14; k++)
+        if (back[k] != guard[0]) { g_err = "vio_stage_publish: a row at or beyond cap was written"; return VIO_EDEVICE; }
+    return VIO_OK;
+}
+
 }  // extern "C"

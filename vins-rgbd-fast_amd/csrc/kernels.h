@@ -43,6 +43,24 @@ struct LkImages {
 __global__ void fe_begin_kernel(Batch B, const double *stamps, int gate, int publish, const uint8_t *modes, const double *R_rel);
 __global__ void be_latest_odometry_kernel(Batch B, int seq, double *out11);
 __global__ void be_imu_rate_odometry_kernel(Batch B, const double *since, int cap, int *n_rows, double *rows, double *last);
+// pubPointCloud / pubKeyframe for the whole batch (pub_kernels.hip): one sequence's tables as plain pointers, and where its four outputs go.
+// pub_all_kernel fills a PubIn per sequence from the Batch, pub_stage_kernel takes one from the host (vio_stage_publish).
+struct PubIn {
+    const int *lm_order, *lm_id, *lm_start, *lm_nobs, *lm_solve_flag, *lm_dyn;   // [NL]; lm_order lists the live slots in list order
+    const double *lm_depth;      // [NL] estimated_depth
+    const double *lm_obs;        // [NL][W+1][VIO_OBS_D], ring-indexed per frame
+    int n_lm, NL, W, ring_base;
+    const double *Ps, *Rs, *Headers, *ric, *tic;   // [W+1][3], [W+1][9] row-major, [W+1], [9], [3]
+    int solver_flag, marginalization_flag, processed;
+};
+struct PubOut {
+    int cap;             // rows of cloud / margin / kf_points; nothing is written at or beyond it
+    int *counts;         // [4] n_cloud n_margin n_kf kf_valid
+    double *kf_pose;     // [8] stamp P(3) Q(w, x, y, z) of window frame W - 2, written only when kf_valid
+    double *cloud, *margin, *kf_points;   // [cap][3], [cap][3], [cap][8], or NULL: counted only
+};
+__global__ void pub_all_kernel(Batch B, int cap, int *counts, double *kf_pose, double *cloud, double *margin, double *kf_points);
+__global__ void pub_stage_kernel(PubIn in, PubOut out);
 __global__ void fe_predict_motion_kernel(Batch B, int seq, double t0, double t1, double *out9);
 __global__ void fe_pyrdown_kernel(Batch B, const uint8_t *src_base, size_t src_stride, int sw, int sh, int dst_level, int write_level0);
 __global__ void fe_pyrdown_stage_kernel(const uint8_t *src, int sw, int sh, uint8_t *dst);

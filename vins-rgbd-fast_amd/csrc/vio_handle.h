@@ -90,6 +90,9 @@ struct vio_batch {
     // and its page-locked host image, both grown on demand
     double *d_odo = nullptr, *h_odo = nullptr;
     size_t odo_cap = 0, h_odo_cap = 0;
+    // vio_publish_all: the same pair for the publishers (counts [S][4], kf_pose [S][8], then the row lists of a host destination)
+    double *d_pub = nullptr, *h_pub = nullptr;
+    size_t pub_cap = 0, h_pub_cap = 0;
     // per-sequence calibration (vio_set_calibration): host mirror of the device table B.cal, as in effect (ric re-orthonormalised, I / 0 on
     // estimate_extrinsic = 2 handles)
     std::vector<vio_calibration> cal;
@@ -324,7 +327,7 @@ inline void stream_release(vio_batch *h, hipStream_t &s) { if (s) { disown(h->st
 // When in doubt an array is state.  The ORDER of the entries is the snapshot format (VIO_SNAPSHOT_FORMAT): do not reorder.
 // A count of 0 means "this configuration has no such array": nothing is allocated, the pointer stays null (code tests for that: B.fuse needs
 // B.pairpart, DevCfg::exc selects the calibrating ingest) and the row reports 0 bytes.  The per-call input buffers of a handle (d_stamps,
-// d_modes, d_rrel, d_r9, d_odo, d_in_*, d_ahead) are not per-sequence state and are not in the table.
+// d_modes, d_rrel, d_r9, d_odo, d_pub, d_in_*, d_ahead) are not per-sequence state and are not in the table.
 // Entry forms (the walkers define h, B = h->B, C = h->hc, D = the dimensions below, S = sequences):
 //   SEQ(kind, member, count)             Batch member B.member, row named after the member, S * count elements
 //   ROW(kind, name, lvalue, count, n)    a per-sequence row over an array that is not a plain Batch member; n elements are allocated in all

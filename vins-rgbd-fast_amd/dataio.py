@@ -302,6 +302,43 @@ class ImuRateCsvWriter(OdometryCsvWriter):
         return new
 
 
+class PublicationWriter:
+    """What pubKeyframe and pubPointCloud publish, written to files through VioBatch.publish (one launch and one copy per poll for the whole
+    handle).  keyframes_dir: one kf_<slot>_<stamp in ns>.npz per published keyframe with `pose` (stamp, P(3), Q(w, x, y, z)) and `points`
+    ([n][8]: world point, x, y, u, v, feature id); cloud_file: written by close(), `cloud_<slot>` and `margin_<slot>` ([n][3]) of the last
+    poll of every slot that was polled."""
+
+    def __init__(self, keyframes_dir=None, cloud_file=None):
+        self.keyframes_dir, self.cloud_file = keyframes_dir, cloud_file
+        self.n_keyframes, self.last = 0, {}
+        if keyframes_dir:
+            os.makedirs(keyframes_dir, exist_ok=True)
+
+    def poll(self, batch, seqs):
+        """after a feed: seqs = the slots whose frame was processed"""
+        seqs = [int(s) for s in seqs]
+        if not seqs:
+            return
+        pub = batch.publish(lists=(bool(self.cloud_file), bool(self.cloud_file), bool(self.keyframes_dir)))
+        for s in seqs:
+            n_cloud, n_margin, n_kf, valid = (int(v) for v in pub["counts"][s])
+            if self.keyframes_dir and valid:
+                pose = pub["kf_pose"][s].copy()
+                np.savez(os.path.join(self.keyframes_dir, "kf_%d_%d.npz" % (s, int(round(pose[0] * 1e9)))), pose=pose,
+                         points=pub["kf_points"][s, :n_kf].copy())
+                self.n_keyframes += 1
+            if self.cloud_file:
+                self.last[s] = (pub["cloud"][s, :n_cloud].copy(), pub["margin"][s, :n_margin].copy())
+
+    def close(self):
+        if self.cloud_file:
+            out = {}
+            for s, (cloud, margin) in sorted(self.last.items()):
+                out["cloud_%d" % s], out["margin_%d" % s] = cloud, margin
+            with open(self.cloud_file, "wb") as fd:   # (np.savez would append .npz to a bare name)
+                np.savez(fd, **out)
+
+
 def read_odometry_csv(path):
     rows = []
     for line in open(path):
@@ -519,7 +556,7 @@ def snapshot_sidecar(path):
 
 
 def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_freq=0, save_at=None, snapshot=None, resume=None,
-           imu_rate=None, before_feed=None):
+           imu_rate=None, before_feed=None, publish=None):
     """Feed a recording through a single-sequence slot of a VioBatch the way the nodelet does: push IMU through the frame stamp
     (one sample beyond, so that IMUAvailable holds), run the frame gate (``freq`` / ``frontend_freq`` of the configuration file;
     frontend_freq == 0 disables the gate: every frame is published), feed the pair with the gate's mode, append a CSV row whenever
@@ -533,7 +570,8 @@ def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_fre
     imu_rate = FILE (or an ImuRateCsvWriter): the IMU-rate poses of the slot.  Once the IMU of a frame interval has been pushed, and once
     more after the last frame, the file gets the pose at every sample newer than the last one written, each propagated from the newest
     window state of that moment: what a subscriber of pubLatestOdometry receives.  before_feed(f, batch) is called after that, right before
-    frame f is handed to the gate."""
+    frame f is handed to the gate.
+    publish = a PublicationWriter: polled after every processed frame of the slot (the caller closes it)."""
     rows, k, f0 = [], 0, 0
     ir = ImuRateCsvWriter(imu_rate) if isinstance(imu_rate, str) else imu_rate
     wr = OdometryCsvWriter(csv_path, append=False) if csv_path else None
@@ -595,6 +633,8 @@ def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_fre
             rows.append(row.copy())
             if wr:
                 wr.write(row[0], row[1:4], row[4:8], row[8:11])
+        if publish is not None and st.processed:
+            publish.poll(batch, [seq])
         if on_frame:
             on_frame(f, st)
         if save_at is not None and f == int(save_at):
@@ -611,13 +651,14 @@ def replay(batch, rec, csv_path=None, seq=0, on_frame=None, freq=0, frontend_fre
     return np.array(rows).reshape(-1, 11)
 
 
-def replay_many(batch, recordings, csv_paths=None, freqs=None, frontend_freqs=None, on_frame=None):
+def replay_many(batch, recordings, csv_paths=None, freqs=None, frontend_freqs=None, on_frame=None, publish=None):
     """replay() for several recordings through ONE handle, recording i in slot i (give each slot its calibration first,
     VioBatch.set_calibration).  Every step feeds the next frame of every recording; each keeps its own frame gate, discontinuity restart
     (vio_reset_seq of its slot only) and empty-map bookkeeping.  A slot whose recording has ended, or whose frame restarted the estimator,
     gets VIO_FRAME_SKIP with a stamp beyond its IMU, which leaves it untouched.  Returns the rows of every recording (list of [n][11]);
     on_frame(i, f, status) is called per recording and frame.  On a handle without IMU (imu: 0) a restarted slot is not held that way:
-    the SKIP then takes the place of its next first image."""
+    the SKIP then takes the place of its next first image.  publish = a PublicationWriter: polled once per step for the slots whose frame
+    was processed."""
     n = len(recordings)
     if n > batch.S:
         raise ValueError("%d recordings for %d slots" % (n, batch.S))
@@ -663,6 +704,7 @@ def replay_many(batch, recordings, csv_paths=None, freqs=None, frontend_freqs=No
             fed.add(i)
         if fed:
             batch.feed(g, dd, stamps, modes=modes)
+        processed = []
         for i in sorted(decided):
             if i not in fed:
                 if on_frame:
@@ -676,6 +718,8 @@ def replay_many(batch, recordings, csv_paths=None, freqs=None, frontend_freqs=No
                     init_feature[i] = True
                 elif not st.processed and st.code == 0:
                     gates[i].empty_map(stamps[i])
+            if st.processed:
+                processed.append(i)
             if st.solver_flag == 1 and st.processed:
                 row = batch.odometry()[i]
                 rows[i].append(row.copy())
@@ -683,6 +727,8 @@ def replay_many(batch, recordings, csv_paths=None, freqs=None, frontend_freqs=No
                     wrs[i].write(row[0], row[1:4], row[4:8], row[8:11])
             if on_frame:
                 on_frame(i, f, st)
+        if publish is not None:
+            publish.poll(batch, processed)
     for w in wrs:
         if w:
             w.close()

@@ -177,6 +177,19 @@ class KeyFrame:
         self.keypoints, self.keypoints_norm = kxy, kn
 
     @classmethod
+    def from_publication(cls, cfg, pattern, index, kf_pose_row, kf_rows, image, sequence=1, camera=None):
+        """the online constructor from what VioBatch.publish() returns for one sequence (pose_graph_nodelet's process(): the keyframe_pose and
+        keyframe_point messages of pubKeyframe): kf_pose_row = stamp, P(3), Q(w, x, y, z); kf_rows [n][8] = world point, x, y, u, v, feature id.
+        image: the frame with that stamp."""
+        p = np.asarray(kf_pose_row, np.float64).reshape(8)
+        rows = np.asarray(kf_rows, np.float64).reshape(-1, 8)
+        qw, qx, qy, qz = p[4:8]
+        R = np.array([[1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qz * qw), 2 * (qx * qz + qy * qw)],
+                      [2 * (qx * qy + qz * qw), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qx * qw)],
+                      [2 * (qx * qz - qy * qw), 2 * (qy * qz + qx * qw), 1 - 2 * (qx * qx + qy * qy)]])
+        return cls(cfg, pattern, p[0], index, p[1:4], R, image, rows[:, 0:3], rows[:, 5:7], rows[:, 3:5], rows[:, 7], sequence=sequence, camera=camera)
+
+    @classmethod
     def from_saved(cls, time_stamp, index, vio_T_w_i, vio_R_w_i, T_w_i, R_w_i, loop_index, loop_info, keypoints, keypoints_norm, brief_descriptors):
         """the "load previous keyframe" constructor (keyframe.cpp:46-78): the VIO pose is REPLACED by the loop-closed one, sequence 0, no window
         points (such a keyframe can be the old side of a loop only)"""
