@@ -703,6 +703,51 @@ int vio_stage_pinv15(int n, const double *A, double *Pinv, int *path_out);
 int vio_stage_marg_literal(int part, int md, int F0, int n, int ldc, int nt, int mxl, int pinv_direct, int second_new, const double *A, const double *b,
                            const double *Cl, const double *Hll, const double *gl, double *Ainv_out, double *Ar_out, double *br_out, double *J_out,
                            double *rf_out, double *H_out, double *r_out, double *scal2_out, int *info8_out);
+/* The DEFAULT marginalisation (marg_exact = 0) on a caller-chosen state, through the kernels a handle really launches (tests/test_gpu_marg_default.py).
+ * vio_debug_marg_set writes one sequence's pre-marginalisation state into the handle's own arrays, vio_debug_marg_run launches what vio_feed launches
+ * behind the solve (be_marg_kernel, be_marg_hbm_kernel or be_marg_pre_kernel + be_marg_alg_kernel, with the handle's thread count and dynamic LDS) and
+ * waits, vio_debug_marg_get reads the result.  W = window_size, n = 6 W + 16, NL = the handle's landmark capacity (vio_get_capacity).
+ * vio_marg_stage_in: t = the tables of vio_stage_publish (lm_order: the first n_lm entries are the live slots in list order, all distinct and < NL; the
+ * other tables are indexed by slot and passed whole, [NL]); lm_est_flag [NL]; Vs / Bas / Bgs [W+1][3]; g [3]; prior_present [W+3], prior_H [n][n],
+ * prior_r [n], prior_x0 [7 W + 17] (read when has_prior; otherwise the prior is cleared); pre_idx [W+1] = a permutation of 0 .. W (window slot ->
+ * pre-integration record).  IMU (read when the handle has use_imu): for the interval that ends in window frame j = 1 .. W, imu_n[j] <= 64 samples
+ * imu_dt [W+1][64], imu_acc / imu_gyr [W+1][64][3] (row j), the sample before the first imu_acc0 / imu_gyr0 [W+1][3] and the linearisation biases
+ * imu_ba / imu_bg [W+1][3]; they are propagated on the device by the pipeline's routine (vio_stage_preint mode 2, with the sequence's noise
+ * densities) into record pre_idx[j], whitening matrix included.  Row 0 of every IMU array is ignored.
+ * set also writes frame_count = W, do_marg = 1, rebooted = 0, processed = 0 (so be_finish, fused into the same kernels, leaves the staged window
+ * alone: the slide is not part of this harness) and derives lm_free / n_free.  It validates everything a kernel indexes with BEFORE anything is
+ * written and returns VIO_EINVAL with vio_last_error set: a slot >= NL or listed twice, n_lm outside 0 .. NL, lm_start outside 0 .. W, lm_nobs outside
+ * 1 .. W + 1 - lm_start, more than 64 samples in an interval, Headers not increasing, a depth (or any other number handed over) that is not
+ * finite, more landmarks starting in frame 0 than NRES / W residual records hold, pre_idx not a permutation, ring_base outside 0 .. W,
+ * marginalization_flag or has_prior not 0 / 1, a handle with marg_exact.  Sequences that were not staged keep do_marg as it was (0 on a fresh handle). */
+typedef struct vio_marg_stage_in {
+    vio_publish_tables t;
+    const int32_t *lm_est_flag;
+    int32_t n_lm, ring_base, marginalization_flag, has_prior;
+    const double *Vs, *Bas, *Bgs, *g;
+    double td;
+    const int32_t *prior_present;
+    const double *prior_H, *prior_r, *prior_x0;
+    const int32_t *pre_idx;
+    const int32_t *imu_n;
+    const double *imu_dt, *imu_acc, *imu_gyr, *imu_acc0, *imu_gyr0, *imu_ba, *imu_bg;
+} vio_marg_stage_in;
+/* vio_marg_stage_out (every pointer may be NULL): prior_H [n][n], prior_r [n], prior_x0 [7 W + 17], prior_present [W+3], prior_c0 [1], has_prior [1],
+ * dbg5 = BeSeq::dbg[0 .. 4]; and what survives in HBM where the handle runs be_marg_hbm_kernel (hbm_valid[0] = 1; otherwise 0 and the four are left
+ * as passed in): margA [(15 + n)^2] = the reduced system over q = [m-block (md = 15, or 6 for MARGIN_SECOND_NEW) | kept (n)] after the landmarks are
+ * eliminated, row-major with leading dimension md + n in the first (md + n)^2 doubles, margB [15 + n] its right-hand side (first md + n), margV [n][n]
+ * = A_r, b_r [n]. */
+typedef struct vio_marg_stage_out {
+    double *prior_H, *prior_r, *prior_x0;
+    int32_t *prior_present;
+    double *prior_c0;
+    int32_t *has_prior, *dbg5;
+    double *margA, *margB, *margV, *b_r;
+    int32_t *hbm_valid;
+} vio_marg_stage_out;
+int vio_debug_marg_set(vio_batch *h, int seq, const vio_marg_stage_in *in);
+int vio_debug_marg_run(vio_batch *h);
+int vio_debug_marg_get(vio_batch *h, int seq, vio_marg_stage_out *out);
 
 #ifdef __cplusplus
 }

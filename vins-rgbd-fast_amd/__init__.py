@@ -203,6 +203,21 @@ class PublishTables(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in _PUBLISH_INT + _PUBLISH_F64]
 
 
+class MargStageIn(C.Structure):
+    """vio_marg_stage_in (include/vio_abi.h)"""
+    _fields_ = [("t", PublishTables), ("lm_est_flag", C.c_void_p)] + \
+        [(n, C.c_int32) for n in ("n_lm", "ring_base", "marginalization_flag", "has_prior")] + \
+        [(n, C.c_void_p) for n in ("Vs", "Bas", "Bgs", "g")] + [("td", C.c_double)] + \
+        [(n, C.c_void_p) for n in ("prior_present", "prior_H", "prior_r", "prior_x0", "pre_idx", "imu_n", "imu_dt", "imu_acc", "imu_gyr", "imu_acc0",
+                                   "imu_gyr0", "imu_ba", "imu_bg")]
+
+
+class MargStageOut(C.Structure):
+    """vio_marg_stage_out (include/vio_abi.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("prior_H", "prior_r", "prior_x0", "prior_present", "prior_c0", "has_prior", "dbg5", "margA", "margB", "margV",
+                                          "b_r", "hbm_valid")]
+
+
 def stage_publish(tables, W, n_lm, ring_base, flags, cap, fill=None, lists=(True, True, True)):
     """vio_stage_publish: the publishers' device routine on the tables of one synthetic sequence.  tables: dict of lm_order, lm_id, lm_start,
     lm_nobs, lm_solve_flag, lm_dyn ([NL] integers), lm_depth [NL], lm_obs [NL, W+1, 9], Ps [W+1, 3], Rs [W+1, 3, 3], Headers [W+1], ric [3, 3],
@@ -936,6 +951,77 @@ class VioBatch:
         J, r, x0, pres = np.zeros((n, n)), np.zeros(n), np.zeros(self.W * 7 + 17), np.zeros(self.W + 3, np.uint8)
         k = self._chk(self.L.vio_get_prior(self.h, seq, J.ctypes.data, r.ctypes.data, x0.ctypes.data, pres.ctypes.data), "vio_get_prior")
         return (J, r, x0, pres) if k else None
+
+    def marg_stage_set(self, seq, st):
+        """vio_debug_marg_set: stage one sequence's pre-marginalisation state (include/vio_abi.h vio_marg_stage_in).  st: dict of lm_order [n_lm]
+        (n_lm may be given on its own), lm_id, lm_start, lm_nobs, lm_solve_flag, lm_dyn, lm_est_flag [NL], lm_depth [NL], lm_obs [NL, W+1, 9], Ps, Vs,
+        Bas, Bgs [W+1, 3], Rs [W+1, 3, 3], Headers [W+1], ric [3, 3], tic, g [3], td, ring_base, marginalization_flag, pre_idx [W+1], prior = None or
+        dict(present [W+3], H [n, n], r [n], x0 [7 W + 17]), and on use_imu handles imu_n [W+1], imu_dt [W+1, 64], imu_acc / imu_gyr [W+1, 64, 3],
+        imu_acc0 / imu_gyr0 / imu_ba / imu_bg [W+1, 3].  Array SIZES are checked here; the values are the library's to refuse (VioError)."""
+        W, NL, n = self.W, self.capacity()["landmarks"], 6 * self.W + 16
+        keep, s = [], MargStageIn()
+
+        def arr(a, dtype, size, name):
+            a = np.ascontiguousarray(a, dtype).reshape(-1)
+            if a.size != size:
+                raise ValueError("%s holds %d values, expected %d" % (name, a.size, size))
+            keep.append(a)
+            return a.ctypes.data
+        order = np.zeros(NL, np.int32)
+        lo = np.asarray(st["lm_order"], np.int32).reshape(-1)
+        if lo.size > NL:
+            raise ValueError("lm_order holds more than NL entries")
+        order[:lo.size] = lo
+        s.t.lm_order = arr(order, np.int32, NL, "lm_order")
+        for name in _PUBLISH_INT[1:]:
+            setattr(s.t, name, arr(st[name], np.int32, NL, name))
+        sizes = dict(lm_depth=NL, lm_obs=NL * (W + 1) * 9, Ps=3 * (W + 1), Rs=9 * (W + 1), Headers=W + 1, ric=9, tic=3)
+        for name in _PUBLISH_F64:
+            setattr(s.t, name, arr(st[name], np.float64, sizes[name], name))
+        s.lm_est_flag = arr(st["lm_est_flag"], np.int32, NL, "lm_est_flag")
+        s.n_lm, s.ring_base, s.marginalization_flag = int(st.get("n_lm", lo.size)), int(st["ring_base"]), int(st["marginalization_flag"])
+        for name in ("Vs", "Bas", "Bgs"):
+            setattr(s, name, arr(st[name], np.float64, 3 * (W + 1), name))
+        s.g, s.td = arr(st["g"], np.float64, 3, "g"), float(st["td"])
+        pr = st.get("prior")
+        s.has_prior = int(st.get("has_prior", pr is not None))
+        if pr is not None:
+            s.prior_present = arr(pr["present"], np.int32, W + 3, "prior present")
+            s.prior_H, s.prior_r = arr(pr["H"], np.float64, n * n, "prior H"), arr(pr["r"], np.float64, n, "prior r")
+            s.prior_x0 = arr(pr["x0"], np.float64, 7 * W + 17, "prior x0")
+        s.pre_idx = arr(st["pre_idx"], np.int32, W + 1, "pre_idx")
+        if "imu_n" in st:
+            s.imu_n = arr(st["imu_n"], np.int32, W + 1, "imu_n")
+            s.imu_dt = arr(st["imu_dt"], np.float64, (W + 1) * 64, "imu_dt")
+            for name in ("imu_acc", "imu_gyr"):
+                setattr(s, name, arr(st[name], np.float64, (W + 1) * 64 * 3, name))
+            for name in ("imu_acc0", "imu_gyr0", "imu_ba", "imu_bg"):
+                setattr(s, name, arr(st[name], np.float64, (W + 1) * 3, name))
+        self.L.vio_debug_marg_set.argtypes = [C.c_void_p, C.c_int, C.POINTER(MargStageIn)]
+        self._chk(self.L.vio_debug_marg_set(self.h, int(seq), C.byref(s)), "vio_debug_marg_set")
+
+    def marg_stage_run(self):
+        """vio_debug_marg_run: the marginalisation launches of vio_feed for this handle, then a wait"""
+        self.L.vio_debug_marg_run.argtypes = [C.c_void_p]
+        self._chk(self.L.vio_debug_marg_run(self.h), "vio_debug_marg_run")
+
+    def marg_stage_get(self, seq):
+        """vio_debug_marg_get: dict of prior_H [n, n], prior_r, prior_x0, prior_present, prior_c0, has_prior, dbg [5], hbm (the handle runs
+        be_marg_hbm_kernel) and then margA [15 + n, 15 + n flat], margB, margV [n, n], b_r (NaN where the handle keeps them in LDS)."""
+        W, n = self.W, 6 * self.W + 16
+        mq = 15 + n
+        o = dict(prior_H=np.full((n, n), np.nan), prior_r=np.full(n, np.nan), prior_x0=np.full(7 * W + 17, np.nan),
+                 prior_present=np.full(W + 3, -1, np.int32), prior_c0=np.full(1, np.nan), has_prior=np.full(1, -1, np.int32),
+                 dbg5=np.full(5, -1, np.int32), margA=np.full(mq * mq, np.nan), margB=np.full(mq, np.nan), margV=np.full((n, n), np.nan),
+                 b_r=np.full(n, np.nan), hbm_valid=np.full(1, -1, np.int32))
+        s = MargStageOut()
+        for name, a in o.items():
+            setattr(s, name, a.ctypes.data)
+        self.L.vio_debug_marg_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(MargStageOut)]
+        self._chk(self.L.vio_debug_marg_get(self.h, int(seq), C.byref(s)), "vio_debug_marg_get")
+        o["prior_c0"], o["has_prior"], o["hbm"] = float(o["prior_c0"][0]), int(o["has_prior"][0]), bool(o.pop("hbm_valid")[0])
+        o["dbg"] = o.pop("dbg5")
+        return o
 
     KERNELS = ("fe_begin", "fe_pyrdown", "fe_predict", "fe_lk", "fe_select", "fe_fast", "fe_add", "be_ingest", "be_solve", "be_marg")
 

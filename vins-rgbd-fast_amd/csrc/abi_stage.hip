@@ -478,6 +478,185 @@ int vio_stage_marg_literal(int part, int md, int F0, int n, int ldc, int nt, int
     return VIO_OK;
 }
 
+// ---- the default marginalisation on a staged state, through the handle's own kernels (include/vio_abi.h vio_debug_marg_set / _run / _get)
+static bool all_finite(const double *p, size_t n) {
+    for (size_t i = 0; i < n; i++) if (!std::isfinite(p[i])) return false;
+    return true;
+}
+#define MARG_STAGE_REFUSE(msg) do { g_err = std::string("vio_debug_marg_set: ") + (msg); return VIO_EINVAL; } while (0)
+int vio_debug_marg_set(vio_batch *h, int seq, const vio_marg_stage_in *in) {
+    VIO_ENTER(h, seq, true);
+    if (!in) return VIO_EINVAL;
+    const DevCfg &C = h->hc;
+    Batch &B = h->B;
+    const int W = C.W, W1 = W + 1, NL = C.NL, n = C.NPRIOR;
+    const vio_publish_tables &t = in->t;
+    // ---- validation: nothing is written before all of it has passed
+    if (C.MX > 0 || C.c.marg_exact) MARG_STAGE_REFUSE("the handle runs the literal marginalisation");
+    if (!t.lm_order || !t.lm_id || !t.lm_start || !t.lm_nobs || !t.lm_solve_flag || !t.lm_dyn || !t.lm_depth || !t.lm_obs || !t.Ps || !t.Rs || !t.Headers ||
+        !t.ric || !t.tic || !in->lm_est_flag || !in->Vs || !in->Bas || !in->Bgs || !in->g || !in->pre_idx)
+        MARG_STAGE_REFUSE("a table is missing");
+    if (in->n_lm < 0 || in->n_lm > NL) MARG_STAGE_REFUSE("n_lm outside 0 .. NL");
+    if (in->ring_base < 0 || in->ring_base > W) MARG_STAGE_REFUSE("ring_base outside 0 .. W");
+    if ((in->marginalization_flag | in->has_prior) & ~1) MARG_STAGE_REFUSE("marginalization_flag and has_prior are 0 or 1");
+    std::vector<char> live(NL, 0);
+    int F0 = 0;
+    for (int k = 0; k < in->n_lm; k++) {
+        const int slot = t.lm_order[k];
+        if (slot < 0 || slot >= NL) MARG_STAGE_REFUSE("lm_order names a slot >= NL");
+        if (live[slot]) MARG_STAGE_REFUSE("lm_order names a slot twice");
+        live[slot] = 1;
+        const int st = t.lm_start[slot], no = t.lm_nobs[slot];
+        if (st < 0 || st > W) MARG_STAGE_REFUSE("lm_start outside 0 .. W");
+        if (no < 1 || no > W1 - st) MARG_STAGE_REFUSE("lm_nobs outside 1 .. W + 1 - lm_start");
+        if (!std::isfinite(t.lm_depth[slot])) MARG_STAGE_REFUSE("a depth is not finite");
+        if (!all_finite(t.lm_obs + (size_t)slot * W1 * VIO_OBS_D, (size_t)W1 * VIO_OBS_D)) MARG_STAGE_REFUSE("an observation is not finite");
+        if (!t.lm_dyn[slot] && no >= 2 && st < W - 2 && st == 0) F0++;
+    }
+    if (F0 > C.NRES / W) MARG_STAGE_REFUSE("more landmarks start in frame 0 than NRES / W residual records hold");
+    for (int i = 1; i <= W; i++) if (!(t.Headers[i] > t.Headers[i - 1])) MARG_STAGE_REFUSE("Headers must increase");
+    if (!all_finite(t.Headers, W1) || !all_finite(t.Ps, 3 * (size_t)W1) || !all_finite(t.Rs, 9 * (size_t)W1) || !all_finite(in->Vs, 3 * (size_t)W1) ||
+        !all_finite(in->Bas, 3 * (size_t)W1) || !all_finite(in->Bgs, 3 * (size_t)W1) || !all_finite(t.ric, 9) || !all_finite(t.tic, 3) ||
+        !all_finite(in->g, 3) || !std::isfinite(in->td))
+        MARG_STAGE_REFUSE("a window state is not finite");
+    {
+        std::vector<char> seen(W1, 0);
+        for (int i = 0; i <= W; i++) {
+            const int p = in->pre_idx[i];
+            if (p < 0 || p > W || seen[p]) MARG_STAGE_REFUSE("pre_idx must be a permutation of 0 .. W");
+            seen[p] = 1;
+        }
+    }
+    if (in->has_prior) {
+        if (!in->prior_present || !in->prior_H || !in->prior_r || !in->prior_x0) MARG_STAGE_REFUSE("has_prior without a prior");
+        for (int i = 0; i < W + 3; i++) if (in->prior_present[i] & ~1) MARG_STAGE_REFUSE("prior_present holds 0 or 1");
+        if (!all_finite(in->prior_H, (size_t)n * n) || !all_finite(in->prior_r, n) || !all_finite(in->prior_x0, (size_t)W * 7 + 17))
+            MARG_STAGE_REFUSE("the prior is not finite");
+    }
+    const bool imu = C.c.use_imu != 0;
+    if (imu) {
+        if (!in->imu_n || !in->imu_dt || !in->imu_acc || !in->imu_gyr || !in->imu_acc0 || !in->imu_gyr0 || !in->imu_ba || !in->imu_bg)
+            MARG_STAGE_REFUSE("an IMU table is missing");
+        for (int j = 1; j <= W; j++) {
+            const int ns = in->imu_n[j];
+            if (ns < 0 || ns > VIO_IMU_SLOT_CAP) MARG_STAGE_REFUSE("more than 64 samples in an interval");
+            const size_t o = (size_t)j * VIO_IMU_SLOT_CAP;
+            if (!all_finite(in->imu_dt + o, ns) || !all_finite(in->imu_acc + 3 * o, 3 * (size_t)ns) || !all_finite(in->imu_gyr + 3 * o, 3 * (size_t)ns) ||
+                !all_finite(in->imu_acc0 + 3 * j, 3) || !all_finite(in->imu_gyr0 + 3 * j, 3) || !all_finite(in->imu_ba + 3 * j, 3) ||
+                !all_finite(in->imu_bg + 3 * j, 3))
+                MARG_STAGE_REFUSE("an IMU sample is not finite");
+        }
+    }
+    // ---- the window state
+    std::vector<BeSeq> bev(1);
+    BeSeq &be = bev[0];
+    HIPCHK(hipMemcpy(&be, B.be + seq, sizeof(BeSeq), hipMemcpyDeviceToHost));
+    for (int i = 0; i <= W; i++) {
+        for (int k = 0; k < 3; k++) { be.Ps[i][k] = t.Ps[3 * i + k]; be.Vs[i][k] = in->Vs[3 * i + k]; be.Bas[i][k] = in->Bas[3 * i + k]; be.Bgs[i][k] = in->Bgs[3 * i + k]; }
+        for (int k = 0; k < 9; k++) be.Rs[i][k] = t.Rs[9 * i + k];
+        be.Headers[i] = t.Headers[i];
+        be.pre_idx[i] = in->pre_idx[i];
+    }
+    for (int k = 0; k < 9; k++) be.ric[k] = t.ric[k];
+    for (int k = 0; k < 3; k++) { be.tic[k] = t.tic[k]; be.g[k] = in->g[k]; }
+    be.td = in->td;
+    be.frame_count = W; be.do_marg = 1; be.rebooted = 0; be.processed = 0;
+    be.marginalization_flag = in->marginalization_flag;
+    be.has_prior = in->has_prior;
+    for (int i = 0; i < VIO_MAXW + 3; i++) be.prior_present[i] = (in->has_prior && i < W + 3) ? in->prior_present[i] : 0;
+    be.ring_base = in->ring_base;
+    be.n_lm = in->n_lm;
+    be.n_free = NL - in->n_lm;
+    for (int k = 0; k < 16; k++) be.dbg[k] = -1;
+    // ---- the landmark tables (the free list as init_state orders it: the lowest free slot is handed out first)
+    const size_t o = (size_t)seq * NL;
+    std::vector<int> fr;
+    for (int slot = NL - 1; slot >= 0; slot--) if (!live[slot]) fr.push_back(slot);
+    fr.resize(NL, 0);
+    std::vector<int> ord(NL, 0);
+    for (int k = 0; k < in->n_lm; k++) ord[k] = t.lm_order[k];
+    HIPCHK(hipMemcpy(B.lm_order + o, ord.data(), NL * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(B.lm_free + o, fr.data(), NL * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(B.lm_id + o, t.lm_id, NL * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(B.lm_start + o, t.lm_start, NL * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(B.lm_nobs + o, t.lm_nobs, NL * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(B.lm_dyn + o, t.lm_dyn, NL * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(B.lm_solve_flag + o, t.lm_solve_flag, NL * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(B.lm_est_flag + o, in->lm_est_flag, NL * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(B.lm_depth + o, t.lm_depth, NL * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(B.lm_obs + o * W1 * VIO_OBS_D, t.lm_obs, (size_t)NL * W1 * VIO_OBS_D * sizeof(double), hipMemcpyHostToDevice));
+    // ---- the prior
+    if (in->has_prior) {
+        HIPCHK(hipMemcpy(B.prior_H + (size_t)seq * n * n, in->prior_H, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(B.prior_r + (size_t)seq * n, in->prior_r, n * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(B.prior_x0 + (size_t)seq * (W * 7 + 17), in->prior_x0, ((size_t)W * 7 + 17) * sizeof(double), hipMemcpyHostToDevice));
+    } else {
+        HIPCHK(hipMemset(B.prior_H + (size_t)seq * n * n, 0, (size_t)n * n * sizeof(double)));
+        HIPCHK(hipMemset(B.prior_r + (size_t)seq * n, 0, n * sizeof(double)));
+        HIPCHK(hipMemset(B.prior_x0 + (size_t)seq * (W * 7 + 17), 0, ((size_t)W * 7 + 17) * sizeof(double)));
+    }
+    be.prior_c0 = 0;
+    HIPCHK(hipMemcpy(B.be + seq, &be, sizeof(BeSeq), hipMemcpyHostToDevice));
+    // ---- the pre-integrations, by the pipeline's routine on the raw samples
+    if (imu) {
+        vio_config cs = C.c;   // the handle's configuration with the sequence's noise densities
+        cal_into_config(h->cal[seq], cs);
+        DevBuf<double> dbuf;
+        const size_t cap = VIO_IMU_SLOT_CAP;
+        HIPCHK(dbuf.alloc(7 * cap + 686));
+        std::vector<PreInt> hpv(1);
+        for (int j = 1; j <= W; j++) {
+            const int ns = in->imu_n[j];
+            PreInt *dp = B.pre + (size_t)seq * (W + 2) + in->pre_idx[j];
+            stage_preint_init(hpv.data(), in->imu_acc0 + 3 * j, in->imu_gyr0 + 3 * j, in->imu_ba + 3 * j, in->imu_bg + 3 * j);
+            HIPCHK(hipMemcpy(dp, hpv.data(), sizeof(PreInt), hipMemcpyHostToDevice));
+            if (ns > 0) {
+                HIPCHK(dbuf.upload(in->imu_dt + (size_t)j * cap, ns));
+                HIPCHK(dbuf.upload(in->imu_acc + 3 * (size_t)j * cap, 3 * (size_t)ns, cap));
+                HIPCHK(dbuf.upload(in->imu_gyr + 3 * (size_t)j * cap, 3 * (size_t)ns, 4 * cap));
+            }
+            be_stage_preint_kernel<<<1, 256>>>(cs, dp, ns, dbuf, dbuf + cap, dbuf + 4 * cap, 2, dbuf + 7 * cap);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipDeviceSynchronize());
+    }
+    return VIO_OK;
+}
+#undef MARG_STAGE_REFUSE
+
+int vio_debug_marg_run(vio_batch *h) {
+    VIO_ENTER(h, VIO_NO_SEQ, true);
+    VIO_TRY(vio_internal::launch_marg_all(h));
+    return sync_all(h);
+}
+
+int vio_debug_marg_get(vio_batch *h, int seq, vio_marg_stage_out *out) {
+    VIO_ENTER(h, seq, true);
+    if (!out) return VIO_EINVAL;
+    const DevCfg &C = h->hc;
+    const Batch &B = h->B;
+    const size_t W = C.W, n = C.NPRIOR, mq = 15 + n, s = (size_t)seq;
+    std::vector<BeSeq> bev(1);
+    const BeSeq &be = bev[0];
+    HIPCHK(hipMemcpy(bev.data(), B.be + seq, sizeof(BeSeq), hipMemcpyDeviceToHost));
+    if (out->prior_H) HIPCHK(hipMemcpy(out->prior_H, B.prior_H + s * n * n, n * n * sizeof(double), hipMemcpyDeviceToHost));
+    if (out->prior_r) HIPCHK(hipMemcpy(out->prior_r, B.prior_r + s * n, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (out->prior_x0) HIPCHK(hipMemcpy(out->prior_x0, B.prior_x0 + s * (W * 7 + 17), (W * 7 + 17) * sizeof(double), hipMemcpyDeviceToHost));
+    if (out->prior_present) for (size_t i = 0; i < W + 3; i++) out->prior_present[i] = be.prior_present[i];
+    if (out->prior_c0) *out->prior_c0 = be.prior_c0;
+    if (out->has_prior) *out->has_prior = be.has_prior;
+    if (out->dbg5) for (int k = 0; k < 5; k++) out->dbg5[k] = be.dbg[k];
+    const bool hbm = !h->marg_lds && C.MX == 0;
+    if (out->hbm_valid) *out->hbm_valid = hbm ? 1 : 0;
+    if (hbm) {
+        if (out->margA) HIPCHK(hipMemcpy(out->margA, B.margA + s * mq * mq, mq * mq * sizeof(double), hipMemcpyDeviceToHost));
+        if (out->margB) HIPCHK(hipMemcpy(out->margB, B.margB + s * mq, mq * sizeof(double), hipMemcpyDeviceToHost));
+        if (out->margV) HIPCHK(hipMemcpy(out->margV, B.margV + s * n * n, n * n * sizeof(double), hipMemcpyDeviceToHost));
+        if (out->b_r) HIPCHK(hipMemcpy(out->b_r, B.vec + s * VEC_SLOTS * C.LW, n * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return VIO_OK;
+}
+
 int vio_stage_projection(const vio_config *cfg, const double *pose_i, const double *pose_j, const double *ex, double inv_dep, double td,
                          const double *obs_i, const double *obs_j, int use_td, double *r2, double *J46) {
     return stage_projection_impl(cfg, pose_i, pose_j, ex, inv_dep, td, obs_i, obs_j, use_td, 0, r2, J46);

@@ -455,6 +455,26 @@ static bool split_feed(const vio_batch *h) {
     return h->marg_split && h->tracker_lag == 1 && h->solve_mode == 1 && h->hc.MX == 0 && h->marg_lds && !h->hc.c.dynamic_init && !h->dyn_active;
 }
 
+// the marginalisation (with the window slide and be_finish) behind a solve: the kernel(s) this handle launches for it, on the group's back-end stream
+static int launch_marg(vio_batch *h, vio_batch::Group &g, const Batch &Bg, int S, bool split) {
+    const DevCfg &C = h->hc;
+    hipStream_t st = g.stream;
+    if (split) {
+        // the window slide first, then the algebra: the next frame's be_ingest (on fe_stream) waits for the first only
+        be_marg_pre_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg, h->d_msnap, h->d_mlist);
+        HIPCHK(hipEventRecord(g.ev_slide, st));
+        be_marg_alg_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg, h->d_msnap, h->d_mlist);
+    } else {
+        if (C.MX > 0) be_marg_exact_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);   // vio_config.marg_exact (parity instrument)
+        else if (h->marg_lds) be_marg_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);  // marginalisation + window slide (be_finish is fused into it)
+        else be_marg_hbm_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);
+        // (a later split frame of this handle orders its be_ingest behind this one's slide all the same; a handle that never splits records nothing)
+        if (h->marg_split) HIPCHK(hipEventRecord(g.ev_slide, st));
+    }
+    g.have_slide_ev = h->marg_split;
+    return VIO_OK;
+}
+
 // one_seq >= 0: only that sequence (vio_process_obs), otherwise every sequence of the group
 // split (vio_feed only, split_feed above): be_ingest and ps_setup of this frame run on the group's front-end stream, behind the previous frame's window
 // slide (ev_slide) and beside its be_marg_alg; the back-end stream joins at the first solver slot (ev_setup) and cuts this frame's marginalisation
@@ -549,19 +569,7 @@ int launch_backend(vio_batch *h, vio_batch::Group &g, const uint16_t *d_depth, c
         HIPCHK(hipEventRecord(h->ev_state, st));
         h->state_pending = true;
     }
-    if (split) {
-        // the window slide first, then the algebra: the next frame's be_ingest (on fe_stream) waits for the first only
-        be_marg_pre_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg, h->d_msnap, h->d_mlist);
-        HIPCHK(hipEventRecord(g.ev_slide, st));
-        be_marg_alg_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg, h->d_msnap, h->d_mlist);
-    } else {
-        if (C.MX > 0) be_marg_exact_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);   // vio_config.marg_exact (parity instrument)
-        else if (h->marg_lds) be_marg_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);  // marginalisation + window slide (be_finish is fused into it)
-        else be_marg_hbm_kernel<<<S, h->marg_threads, h->lds_marg, st>>>(Bg);
-        // (a later split frame of this handle orders its be_ingest behind this one's slide all the same; a handle that never splits records nothing)
-        if (h->marg_split) HIPCHK(hipEventRecord(g.ev_slide, st));
-    }
-    g.have_slide_ev = h->marg_split;
+    VIO_TRY(launch_marg(h, g, Bg, S, split));
     if (prof) PEV(h, 11);
     HIPCHK(hipGetLastError());
     return VIO_OK;
@@ -570,6 +578,16 @@ int launch_backend(vio_batch *h, vio_batch::Group &g, const uint16_t *d_depth, c
 }  // namespace
 
 namespace vio_internal {
+// the marginalisation launches of a vio_feed call on every group of the handle, without the stages in front of them (vio_debug_marg_run)
+int launch_marg_all(vio_batch *h) {
+    for (auto &g : h->groups) {
+        Batch Bg = h->B;
+        Bg.s0 = g.s0;
+        VIO_TRY(launch_marg(h, g, Bg, g.n, split_feed(h)));
+    }
+    HIPCHK(hipGetLastError());
+    return VIO_OK;
+}
 // dynamic initialisation: before a frame is fed, pick up the solver flags of the previous one (see launch_backend)
 int refresh_dynamic_state(vio_batch *h) {
     if (!h->hc.c.dynamic_init) return VIO_OK;

@@ -470,6 +470,7 @@ enum { VIO_RESET_ESTIMATOR = 1, VIO_RESET_TRACKER = 2 };
 int init_state(vio_batch *h, int s_lo, int s_hi, int what = VIO_RESET_ESTIMATOR | VIO_RESET_TRACKER);
 int flush_imu_backend(vio_batch *h);        // vio_abi.hip
 int refresh_dynamic_state(vio_batch *h);    // vio_abi.hip
+int launch_marg_all(vio_batch *h);          // vio_abi.hip: what vio_feed launches behind the solve, on every group
 // "" when the calibration / camera is usable, else the message naming the offending field (abi_query.hip)
 std::string calibration_check(const vio_calibration &k);
 std::string camera_check(const vio_camera &m, int width, int height);
