@@ -92,6 +92,73 @@ int vio_pg_db_query(vio_pg_voc *v, const uint64_t *desc, int n, int max_results,
 int vio_pg_detect_loop(vio_pg_voc *v, const uint64_t *desc, int n, int frame_index, int32_t *loop_index, int32_t *ids4, double *scores4,
                        int32_t *n_ret);
 
+/* ---- the batch: one keyframe database per sequence, resident on the device (pg_batch.hip) ----
+ * PoseGraph::detectLoop plus the descriptor search of KeyFrame::findConnection for every sequence of a batch in one chain of launches on a
+ * stream of the batch's own: tree walk, bag-of-words vector, database score, top-4 and gates, append, search against the resident candidate.
+ * A step allocates nothing, waits once (at its end) and copies one block of results back; the only host state is one entry counter per
+ * sequence.  Every number equals what vio_pg_describe / vio_pg_detect_loop / vio_pg_match give for the same keyframes, bit for bit (the
+ * kernels share their bodies, the floating-point sums keep the reference's order).  The geometric verification (vio_pg_find_connection) and
+ * the optimisers stay per-keyframe host code, run by the caller for the sequences that report a candidate.
+ *
+ * Storage: per sequence one arena of arena_keypoints slots (descriptor 32 B, normalised and pixel keypoint 8 B each, bag-of-words word 4 B
+ * and value 8 B: 60 B per slot) that the entries fill back to back, and max_keyframes + 1 offsets.  An entry takes as many slots as it keeps
+ * keypoints (its bag-of-words vector is never longer).  frame_index of a sequence = its entry counter: every mode-1 or mode-2 step adds exactly
+ * one entry. */
+typedef struct vio_pg_batch vio_pg_batch;
+
+/* S sequences; per sequence at most max_keyframes entries, max_keypoints (<= 8192) FAST keypoints and max_window window points per keyframe.
+ * voc is borrowed (must outlive the batch; only its tree is used, its own database is untouched); pattern1024 as in vio_pg_describe.  All
+ * device memory is allocated here.  vio_pg_batch_create sizes every arena for the worst case (max_keyframes x max_keypoints slots);
+ * vio_pg_batch_create_arena takes the slots per sequence (>= max_keypoints).  NULL on failure (vio_last_error). */
+vio_pg_batch *vio_pg_batch_create(const vio_config *cfg, vio_pg_voc *voc, int S, int max_keyframes, int max_keypoints, int max_window,
+                                  const int32_t *pattern1024, int fast_threshold);
+vio_pg_batch *vio_pg_batch_create_arena(const vio_config *cfg, vio_pg_voc *voc, int S, int max_keyframes, int max_keypoints, int max_window,
+                                        const int32_t *pattern1024, int fast_threshold, int64_t arena_keypoints);
+void vio_pg_batch_destroy(vio_pg_batch *b);
+int  vio_pg_batch_set_camera(vio_pg_batch *b, int seq, const vio_camera *cam);      /* default: cfg's pinhole, like vio_pg_describe */
+int  vio_pg_batch_reset_seq(vio_pg_batch *b, int seq);                              /* empty that sequence's database */
+
+/* per-sequence result of one step, [S] of them, host */
+typedef struct vio_pg_step_out {
+    int32_t status;        /* VIO_OK, VIO_ECAPACITY (max_keyframes entries, or the arena has no room for this keyframe: nothing changed for this
+                              sequence, no query is made: n_bow = n_ret = n_match = 0, loop_index = -1), or mode 0: the whole struct untouched */
+    int32_t entry;         /* id of the entry added = that sequence's frame_index (VIO_ECAPACITY: the number of entries) */
+    int32_t n_kp;          /* keypoints found (may exceed max_keypoints: only max_keypoints are kept, as vio_pg_describe with cap) */
+    int32_t n_bow;         /* size of the bag-of-words vector */
+    int32_t n_ret;         /* results of query(4, frame_index - 50); 0 in mode 2 */
+    int32_t ids4[4];
+    double  scores4[4];
+    int32_t loop_index;    /* detectLoop's decision, -1 = none */
+    int32_t n_match;       /* window descriptors with best_index != -1 against entry loop_index (0 when loop_index == -1) */
+} vio_pg_step_out;
+
+/* core: descriptors given.  mode[S]: 0 = no keyframe for this sequence this step, 1 = detectLoop (query, then add),
+ * 2 = addKeyFrameIntoVoc (add only).  kp_desc [S][max_keypoints][4], kp_norm [S][max_keypoints][2], n_kp [S];
+ * win_desc [S][max_window][4], n_win [S].  best_index / best_dist [S][max_window] and old_norm [S][max_window][2]
+ * (the candidate's normalised keypoint at best_index, 0 where best_index is -1; gathered on the device) are written for rows < n_win of
+ * sequences with loop_index != -1, and no other row is touched.  on_device != 0: every array except mode, n_kp, n_win and out is an HBM
+ * address.  The pixel keypoints of entries added through this call are 0.  VIO_EINVAL (nothing launched, nothing changed): NULL handle or
+ * array, a mode above 2, n_kp outside 0 .. max_keypoints or n_win outside 0 .. max_window for a sequence whose mode is not 0. */
+int vio_pg_batch_step_desc(vio_pg_batch *b, const uint8_t *mode, const int32_t *n_kp, const uint64_t *kp_desc, const float *kp_norm,
+                           const int32_t *n_win, const uint64_t *win_desc, int on_device, vio_pg_step_out *out,
+                           int32_t *best_index, int32_t *best_dist, float *old_norm);
+
+/* from images: gray [S][H][W] (the layout of vio_feed), win_uv [S][max_window][2] (u, v of kf_points from vio_publish_all).
+ * = batched vio_pg_describe(_camera) into the batch's own buffers (the keypoint counts stay on the device), then the step above. */
+int vio_pg_batch_step(vio_pg_batch *b, const uint8_t *mode, const uint8_t *gray, const int32_t *n_win, const float *win_uv, int on_device,
+                      vio_pg_step_out *out, int32_t *best_index, int32_t *best_dist, float *old_norm);
+
+/* read one stored entry back (tests, savePoseGraph): counts2 = n_kp kept, n_bow; kp_xy [n_kp][2], kp_desc [n_kp][4], kp_norm [n_kp][2],
+ * bow_word / bow_value [n_bow]; any pointer may be NULL.  VIO_EINVAL for an entry that does not exist. */
+int vio_pg_batch_get_entry(vio_pg_batch *b, int seq, int entry, int32_t *counts2, float *kp_xy, uint64_t *kp_desc, float *kp_norm,
+                           int32_t *bow_word, double *bow_value);
+int vio_pg_batch_info(vio_pg_batch *b, int32_t *entries /*[S]*/);
+/* device time of the kernels of the last step in milliseconds (HIP events recorded on the batch's stream when timing is on; off by default,
+ * the events cost a few microseconds each): ms8 = describe (blur, FAST, BRIEF, lift), tree walk, bag-of-words vector, database score,
+ * top-4 / gates / append, match, result copy, whole chain.  tools/pg_batch_bench.py reads them. */
+int vio_pg_batch_set_timing(vio_pg_batch *b, int on);
+int vio_pg_batch_last_timing(vio_pg_batch *b, float *ms8);
+
 /* test entry: the blurred image alone */
 int vio_pg_stage_blur(const uint8_t *gray, int width, int height, uint8_t *out);
 

@@ -17,32 +17,10 @@
 #include <vector>
 
 #include "../../include/vio_posegraph.h"
+#include "pg_device.h"
+#include "pg_voc.h"
 
 extern thread_local std::string g_err;   // vio_abi.hip
-
-struct vio_pg_voc {
-    int k = 0, L = 0, scoring = 0, weighting = 0, n_nodes = 0, n_words = 0, nentries = 0;
-    // host copies (validation, info); the walk itself runs on the device
-    std::vector<int> child_begin, children, node_word;
-    std::vector<double> node_weight;
-    // device tree
-    int *d_child_begin = nullptr, *d_children = nullptr, *d_node_word = nullptr;
-    double *d_node_weight = nullptr;
-    uint64_t *d_node_desc = nullptr;
-    // per-call device scratch (grown on demand)
-    uint64_t *d_desc = nullptr;
-    int *d_word = nullptr;
-    double *d_w = nullptr;
-    int cap = 0;
-    std::vector<int> h_word;
-    std::vector<double> h_w;
-    // inverted file: word id -> (entry id, weight), rows in ascending entry order (TemplatedDatabase::add)
-    std::vector<std::vector<std::pair<int, double>>> ifile;
-    // query scratch
-    std::vector<double> acc;
-    std::vector<char> seen;
-    std::vector<int> touched;
-};
 
 namespace {
 
@@ -53,20 +31,7 @@ __global__ __launch_bounds__(256) void pg_voc_transform_kernel(const uint64_t *d
                                                                int *out_word, double *out_w) {
     const int wv = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
     if (wv >= n) return;
-    const uint64_t f0 = desc[(size_t)wv * 4], f1 = desc[(size_t)wv * 4 + 1], f2 = desc[(size_t)wv * 4 + 2], f3 = desc[(size_t)wv * 4 + 3];
-    int node = 0;
-    for (;;) {
-        const int b = child_begin[node], e = child_begin[node + 1];
-        if (b == e) break;   // leaf = word
-        unsigned best = 0xFFFFFFFFu;
-        for (int c = b + lane; c < e; c += 64) {
-            const uint64_t *d = ndesc + (size_t)children[c] * 4;
-            const unsigned dist = (unsigned)(__popcll(f0 ^ d[0]) + __popcll(f1 ^ d[1]) + __popcll(f2 ^ d[2]) + __popcll(f3 ^ d[3]));
-            best = min(best, (dist << 22) | (unsigned)(c - b));   // distance <= 256 (9 bits), child position < 2^22
-        }
-        for (int o = 32; o > 0; o >>= 1) best = min(best, (unsigned)__shfl_xor((int)best, o, 64));
-        node = children[b + (int)(best & 0x3FFFFFu)];
-    }
+    const int node = pgdev::voc_walk(desc + (size_t)wv * 4, child_begin, children, ndesc);
     if (lane == 0) { out_word[wv] = node_word[node]; out_w[wv] = node_weight[node]; }
 }
 

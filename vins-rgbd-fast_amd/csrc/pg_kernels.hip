@@ -6,187 +6,56 @@
 //   pg_brief_kernel       one wavefront per point: lane l evaluates the pair tests l, l + 64, l + 128, l + 192 -> four ballots = the descriptor
 //   pg_match_kernel       one wavefront per window descriptor: lanes stride over the old descriptors (v_bcnt popcounts), wave arg-min on
 //                         (distance, index) = the sequential scan's "first smallest"
-// Integer arithmetic throughout (the blur's 8-bit fixed point included), so the results are the CPU restatement's bit for bit.
+// Integer arithmetic throughout (the blur's 8-bit fixed point included), so the results are the CPU restatement's bit for bit.  The kernel
+// bodies live in pg_device.h, which the batched kernels of pg_batch.hip share.
 #include <hip/hip_runtime.h>
 #include <string>
 #include <vector>
 #include "../../include/vio_posegraph.h"
 #include "camera_model.h"
+#include "pg_device.h"
 
 extern thread_local std::string g_err;   // vio_abi.hip
 
 namespace {
 
-__device__ __forceinline__ int refl101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+__global__ __launch_bounds__(256) void pg_blur_kernel(const uint8_t *src, int W, int H, uint8_t *dst) { pgdev::blur_tile(src, W, H, dst); }
 
-#define PG_TW 64
-#define PG_TH 16
-// separable 9-tap Gaussian, 8 fractional bits per pass (52 46 32 17 7 | sum 256), one rounding: (v + 2^15) >> 16
-__global__ __launch_bounds__(256) void pg_blur_kernel(const uint8_t *src, int W, int H, uint8_t *dst) {
-    __shared__ uint8_t tile[PG_TH + 8][PG_TW + 8];
-    __shared__ int hrow[PG_TH + 8][PG_TW];
-    const int ox = blockIdx.x * PG_TW, oy = blockIdx.y * PG_TH;
-    for (int q = threadIdx.x; q < (PG_TH + 8) * (PG_TW + 8); q += 256) {
-        const int ty = q / (PG_TW + 8), tx = q - ty * (PG_TW + 8);
-        const int gy = min(max(refl101(oy + ty - 4, H), 0), H - 1), gx = min(max(refl101(ox + tx - 4, W), 0), W - 1);
-        tile[ty][tx] = src[(size_t)gy * W + gx];
-    }
-    __syncthreads();
-    for (int q = threadIdx.x; q < (PG_TH + 8) * PG_TW; q += 256) {
-        const int ty = q / PG_TW, x = q - ty * PG_TW;
-        const uint8_t *r = &tile[ty][x];
-        hrow[ty][x] = 7 * (r[0] + r[8]) + 17 * (r[1] + r[7]) + 32 * (r[2] + r[6]) + 46 * (r[3] + r[5]) + 52 * r[4];
-    }
-    __syncthreads();
-    for (int q = threadIdx.x; q < PG_TH * PG_TW; q += 256) {
-        const int y = q / PG_TW, x = q - y * PG_TW;
-        if (ox + x < W && oy + y < H) {
-            const int v = 7 * (hrow[y][x] + hrow[y + 8][x]) + 17 * (hrow[y + 1][x] + hrow[y + 7][x]) + 32 * (hrow[y + 2][x] + hrow[y + 6][x]) +
-                          46 * (hrow[y + 3][x] + hrow[y + 5][x]) + 52 * hrow[y + 4][x];
-            dst[(size_t)(oy + y) * W + ox + x] = (uint8_t)((v + (1 << 15)) >> 16);
-        }
-    }
-}
-
-__device__ __forceinline__ int pg_fast_score(const uint8_t *p, int stride, int thr) {
-    const int v = p[0];
-    int d[25];
-    d[0] = v - p[3 * stride]; d[4] = v - p[3]; d[8] = v - p[-3 * stride]; d[12] = v - p[-3];
-    const int nb = (d[0] < -thr) + (d[4] < -thr) + (d[8] < -thr) + (d[12] < -thr);
-    const int nd = (d[0] > thr) + (d[4] > thr) + (d[8] > thr) + (d[12] > thr);
-    if (nb < 2 && nd < 2) return 0;   // any 9-arc contains at least two of the four compass pixels
-    d[1] = v - p[3 * stride + 1];   d[2] = v - p[2 * stride + 2];   d[3] = v - p[stride + 3];
-    d[5] = v - p[-stride + 3];      d[6] = v - p[-2 * stride + 2];  d[7] = v - p[-3 * stride + 1];
-    d[9] = v - p[-3 * stride - 1];  d[10] = v - p[-2 * stride - 2]; d[11] = v - p[-stride - 3];
-    d[13] = v - p[stride - 3];      d[14] = v - p[2 * stride - 2];  d[15] = v - p[3 * stride - 1];
-#pragma unroll
-    for (int k = 16; k < 25; k++) d[k] = d[k - 16];
-    int best = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        int mn = d[k], mx = d[k];
-#pragma unroll
-        for (int j = 1; j < 9; j++) { mn = min(mn, d[k + j]); mx = max(mx, d[k + j]); }
-        best = max(best, max(mn, -mx));
-    }
-    return best > thr ? best - 1 : 0;
-}
-// score of every pixel at least 3 away from the border (0 elsewhere), tile (64 + 6) x (16 + 6) in LDS
 __global__ __launch_bounds__(256) void pg_fast_score_kernel(const uint8_t *img, int W, int H, int thr, uint8_t *score) {
-    __shared__ uint8_t tile[PG_TH + 6][PG_TW + 8];
-    const int ox = blockIdx.x * PG_TW, oy = blockIdx.y * PG_TH;
-    for (int q = threadIdx.x; q < (PG_TH + 6) * (PG_TW + 6); q += 256) {
-        const int ty = q / (PG_TW + 6), tx = q - ty * (PG_TW + 6);
-        const int gy = min(max(oy + ty - 3, 0), H - 1), gx = min(max(ox + tx - 3, 0), W - 1);
-        tile[ty][tx] = img[(size_t)gy * W + gx];
-    }
-    __syncthreads();
-    for (int q = threadIdx.x; q < PG_TH * PG_TW; q += 256) {
-        const int y = q / PG_TW, x = q - y * PG_TW;
-        const int gx = ox + x, gy = oy + y;
-        if (gx < W && gy < H) {
-            int sc = 0;
-            if (gx >= 3 && gx < W - 3 && gy >= 3 && gy < H - 3) sc = pg_fast_score(&tile[y + 3][x + 3], PG_TW + 8, thr);
-            score[(size_t)gy * W + gx] = (uint8_t)sc;
-        }
-    }
+    pgdev::fast_score_tile(img, W, H, thr, score);
 }
-// one workgroup of 1024 threads: the interior pixels in row-major order, 64 at a time per wavefront, contiguous ranges per wavefront; the
-// ballot words go to `words`, the per-wavefront counts are scanned after one barrier and the survivors are written at their final positions
+
 __global__ __launch_bounds__(1024) void pg_fast_nms_kernel(const uint8_t *score, int W, int H, unsigned long long *words, float *kp_xy, int cap, int *count) {
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, nw = blockDim.x >> 6;
-    const int iw = W - 6, ih = H - 6, npx = iw * ih;
-    const int nchunk = (npx + 63) >> 6, cpw = (nchunk + nw - 1) / nw;
-    __shared__ int wtot[16];
-    int mine = 0;
-    for (int ch = wv * cpw; ch < min(nchunk, (wv + 1) * cpw); ch++) {
-        const int q = ch * 64 + lane;
-        bool mx = false;
-        if (q < npx) {
-            const int y = q / iw + 3, x = q - (q / iw) * iw + 3;
-            const uint8_t *c = score + (size_t)y * W + x;
-            const int sc = c[0];
-            mx = sc && sc > c[-1] && sc > c[1] && sc > c[-W - 1] && sc > c[-W] && sc > c[-W + 1] && sc > c[W - 1] && sc > c[W] && sc > c[W + 1];
-        }
-        const unsigned long long bal = __ballot(mx);
-        if (lane == 0) words[ch] = bal;
-        mine += __popcll(bal);
-    }
-    if (lane == 0) wtot[wv] = mine;
-    __syncthreads();
-    int o = 0, total = 0;
-    for (int k = 0; k < nw; k++) { if (k < wv) o += wtot[k]; total += wtot[k]; }
-    for (int ch = wv * cpw; ch < min(nchunk, (wv + 1) * cpw); ch++) {
-        const unsigned long long bal = words[ch];
-        if ((bal >> lane) & 1ULL) {
-            const int q = ch * 64 + lane, pos = o + __popcll(bal & ((1ULL << lane) - 1ULL));
-            if (pos < cap) { kp_xy[2 * pos] = (float)(q - (q / iw) * iw + 3); kp_xy[2 * pos + 1] = (float)(q / iw + 3); }
-        }
-        o += __popcll(bal);
-    }
-    if (t == 0) *count = total;
+    const int total = pgdev::fast_nms_image(score, W, H, words, kp_xy, cap);
+    if (threadIdx.x == 0) *count = total;
 }
 
-// DVision::BRIEF::compute: bit i = I(p + (x1, y1)_i) < I(p + (x2, y2)_i) if both samples are inside the image; (int)(pt + offset) truncates
 __global__ __launch_bounds__(64) void pg_brief_kernel(const uint8_t *blur, int W, int H, const float *xy, int n, const int *pat, unsigned long long *desc) {
-    const int p = blockIdx.x, lane = threadIdx.x;
+    const int p = blockIdx.x;
     if (p >= n) return;
-    const float px = xy[2 * p], py = xy[2 * p + 1];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int i = 64 * j + lane;
-        const int x1 = (int)(px + (float)pat[i]), y1 = (int)(py + (float)pat[256 + i]);
-        const int x2 = (int)(px + (float)pat[512 + i]), y2 = (int)(py + (float)pat[768 + i]);
-        bool bit = false;
-        if (x1 >= 0 && x1 < W && y1 >= 0 && y1 < H && x2 >= 0 && x2 < W && y2 >= 0 && y2 < H) bit = blur[(size_t)y1 * W + x1] < blur[(size_t)y2 * W + x2];
-        const unsigned long long bal = __ballot(bit);
-        if (lane == 0) desc[4 * (size_t)p + j] = bal;
-    }
+    pgdev::brief_point(blur, W, H, xy, p, pat, desc);
 }
 
-// PinholeCamera::liftProjective (camera_model/src/camera_models/PinholeCamera.cc:449-510): 8 fixed-point iterations of the radial-tangential model
 __global__ void pg_lift_kernel(vio_config c, const float *xy, int n, float *nrm) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double u = xy[2 * i], v = xy[2 * i + 1];
-    const double mx_d = (1.0 / c.fx) * u + (-c.cx / c.fx), my_d = (1.0 / c.fy) * v + (-c.cy / c.fy);
-    auto dist = [&](double x, double y, double &dx, double &dy) {
-        const double mx2 = x * x, my2 = y * y, mxy = x * y, rho2 = mx2 + my2, rad = c.k1 * rho2 + c.k2 * rho2 * rho2;
-        dx = x * rad + 2.0 * c.p1 * mxy + c.p2 * (rho2 + 2.0 * mx2);
-        dy = y * rad + 2.0 * c.p2 * mxy + c.p1 * (rho2 + 2.0 * my2);
-    };
-    double dx, dy;
-    dist(mx_d, my_d, dx, dy);
-    double mx_u = mx_d - dx, my_u = my_d - dy;
-    for (int k = 1; k < 8; k++) { dist(mx_u, my_u, dx, dy); mx_u = mx_d - dx; my_u = my_d - dy; }
-    nrm[2 * i] = (float)mx_u; nrm[2 * i + 1] = (float)my_u;
+    pgdev::lift_pinhole(c, xy, i, nrm);
 }
 
-// the same through a camera model (KeyFrame::computeBRIEFPoint, keyframe.cpp:114-124): (x / z, y / z) of m_camera->liftProjective
 __global__ void pg_lift_camera_kernel(vio_camera cam, const float *xy, int n, float *nrm) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    double x, y;
-    vcam::lift_plane(cam, xy[2 * i], xy[2 * i + 1], x, y);
-    nrm[2 * i] = (float)x; nrm[2 * i + 1] = (float)y;
+    pgdev::lift_camera(cam, xy, i, nrm);
 }
 
 // one wavefront per window descriptor
 __global__ __launch_bounds__(64) void pg_match_kernel(const unsigned long long *wd, int n, const unsigned long long *od, int m, int *best_index, int *best_dist) {
-    const int i = blockIdx.x, lane = threadIdx.x;
+    const int i = blockIdx.x;
     if (i >= n) return;
-    const unsigned long long a0 = wd[4 * (size_t)i], a1 = wd[4 * (size_t)i + 1], a2 = wd[4 * (size_t)i + 2], a3 = wd[4 * (size_t)i + 3];
-    int key = (128 << 20) | 0xFFFFF;   // (distance << 20) | index: the minimum key = smallest distance, then smallest index
-    for (int j = lane; j < m; j += 64) {
-        const unsigned long long *b = od + 4 * (size_t)j;
-        const int dis = __popcll(a0 ^ b[0]) + __popcll(a1 ^ b[1]) + __popcll(a2 ^ b[2]) + __popcll(a3 ^ b[3]);
-        if (dis < 128) key = min(key, (dis << 20) | j);
-    }
-    for (int off = 32; off > 0; off >>= 1) key = min(key, __shfl_xor(key, off, 64));
-    if (lane == 0) {
-        const int bd = key >> 20, bi = key & 0xFFFFF;
-        best_dist[i] = bd;
-        best_index[i] = (bd < 80 && bi != 0xFFFFF) ? bi : -1;
+    const int key = pgdev::match_scan(wd + 4 * (size_t)i, od, m);
+    if (threadIdx.x == 0) {
+        best_dist[i] = key >> 20;
+        best_index[i] = pgdev::match_index(key);
     }
 }
 

@@ -8,7 +8,11 @@
     voc = Vocabulary.load("brief_k10L6.bin")        # PoseGraph::loadVocabulary (the blob is missing from the reference tree: the caller's file)
     loop_index = voc.detectLoop(kf.brief_descriptors, kf.index)     # PoseGraph::detectLoop, pose_graph.cpp:308-393 (-1: none)
 
-Descriptor extraction, matching and the vocabulary walk are HIP kernels; there is no CPU fallback."""
+    db = BatchDatabase(cfg, voc, pattern, S, max_keyframes, max_keypoints, max_window)     # one database per sequence, resident on the device
+    graphs = PoseGraphBatch(db, qic, tic)           # S PoseGraph states over it
+    verified = graphs.add_keyframes(pub["counts"], pub["kf_pose"], pub["kf_points"], gray)  # VioBatch.publish() in, one step for the batch
+
+Descriptor extraction, matching, the vocabulary walk and the batched database are HIP kernels; there is no CPU fallback."""
 import ctypes as C
 import importlib
 import os
@@ -44,6 +48,23 @@ def _lib():
         L.vio_pg_db_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.vio_pg_db_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.vio_pg_detect_loop.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+        for name in ("vio_pg_batch_create", "vio_pg_batch_create_arena", "vio_pg_batch_step", "vio_pg_batch_step_desc"):
+            if not hasattr(L, name):      # a missing kernel is an error, never a fall-back to the per-keyframe path
+                raise P.VioError("libvio_hip.so has no %s: rebuild the extension" % name)
+        L.vio_pg_batch_create.argtypes = [C.POINTER(P.Config), C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int]
+        L.vio_pg_batch_create.restype = C.c_void_p
+        L.vio_pg_batch_create_arena.argtypes = [C.POINTER(P.Config), C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_int64]
+        L.vio_pg_batch_create_arena.restype = C.c_void_p
+        L.vio_pg_batch_destroy.argtypes = [C.c_void_p]
+        L.vio_pg_batch_destroy.restype = None
+        L.vio_pg_batch_set_camera.argtypes = [C.c_void_p, C.c_int, C.POINTER(P.Camera)]
+        L.vio_pg_batch_reset_seq.argtypes = [C.c_void_p, C.c_int]
+        L.vio_pg_batch_step_desc.argtypes = [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 4
+        L.vio_pg_batch_step.argtypes = [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4
+        L.vio_pg_batch_get_entry.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+        L.vio_pg_batch_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.vio_pg_batch_set_timing.argtypes = [C.c_void_p, C.c_int]
+        L.vio_pg_batch_last_timing.argtypes = [C.c_void_p, C.c_void_p]
         L._pg_bound = True
     return P, L
 
@@ -206,6 +227,38 @@ class KeyFrame:
         kf.brief_descriptors = np.ascontiguousarray(brief_descriptors, np.uint64).reshape(-1, 4)
         return kf
 
+    @classmethod
+    def from_publication_row(cls, index, kf_pose_row, kf_rows, sequence=1):
+        """the keyframe of PoseGraphBatch: poses and window points from what VioBatch.publish() returns for one sequence (see
+        from_publication), nothing described here -- its keypoints and descriptors are computed by, and stay in, the BatchDatabase"""
+        p = np.asarray(kf_pose_row, np.float64).reshape(8)
+        rows = np.asarray(kf_rows, np.float64).reshape(-1, 8)
+        kf = cls.__new__(cls)
+        kf.time_stamp, kf.index, kf.sequence = float(p[0]), int(index), int(sequence)
+        kf.vio_T_w_i, kf.vio_R_w_i = p[1:4].copy(), _q2R_wxyz(p[4:8])
+        kf.T_w_i, kf.R_w_i = kf.vio_T_w_i.copy(), kf.vio_R_w_i.copy()
+        kf.origin_vio_T, kf.origin_vio_R = kf.vio_T_w_i.copy(), kf.vio_R_w_i.copy()
+        kf.point_3d = np.array(rows[:, 0:3], np.float32).reshape(-1, 3)
+        kf.point_2d_uv = np.array(rows[:, 5:7], np.float32).reshape(-1, 2)
+        kf.point_2d_norm = np.array(rows[:, 3:5], np.float32).reshape(-1, 2)
+        kf.point_id = np.array(rows[:, 7], np.float64).reshape(-1)
+        kf.has_loop, kf.loop_index, kf.loop_info = False, -1, np.zeros(8)
+        kf.match_points = np.zeros((0, 3))
+        kf.window_brief_descriptors, kf.brief_descriptors = np.zeros((0, 4), np.uint64), np.zeros((0, 4), np.uint64)
+        kf.keypoints, kf.keypoints_norm = np.zeros((0, 2), np.float32), np.zeros((0, 2), np.float32)
+        return kf
+
+    def connectMatched(self, old_index, best_index, old_norm, qic, tic):
+        """findConnection after a descriptor search done elsewhere (BatchDatabase): best_index[n] as vio_pg_match gives it, old_norm[n][2] =
+        the old keyframe's normalised keypoint of each window point (row i for window point i)"""
+        bi = np.asarray(best_index, np.int32).reshape(-1)
+        idx = np.where(bi >= 0, np.arange(len(bi), dtype=np.int32), -1).astype(np.int32)
+        ok, info, mp, self.PnP_T_old, self.PnP_R_old = find_connection(self.point_3d, self.point_id, idx, old_norm, self.origin_vio_T,
+                                                                       self.origin_vio_R, qic, tic)
+        if ok:
+            self.has_loop, self.loop_index, self.loop_info, self.match_points = True, int(old_index), info, mp
+        return ok
+
     def findConnection(self, old_kf, qic, tic):
         idx, _ = match(self.window_brief_descriptors, old_kf.brief_descriptors)
         ok, info, mp, self.PnP_T_old, self.PnP_R_old = find_connection(self.point_3d, self.point_id, idx, old_kf.keypoints_norm, self.origin_vio_T,
@@ -278,6 +331,16 @@ class PoseGraph:
 
     def addKeyFrame(self, cur_kf, flag_detect_loop=True):
         """returns the index of the verified loop partner or -1"""
+        self.beginKeyFrame(cur_kf)
+        loop_index = -1
+        if flag_detect_loop:
+            loop_index = self.voc.detectLoop(cur_kf.brief_descriptors, cur_kf.index)
+        else:
+            self.voc.add(cur_kf.brief_descriptors)             # addKeyFrameIntoVoc
+        return self.finishKeyFrame(cur_kf, loop_index, lambda old_kf: cur_kf.findConnection(old_kf, self.qic, self.tic))
+
+    def beginKeyFrame(self, cur_kf):
+        """addKeyFrame before the loop detection (:55-72): the shift into the map frame and the keyframe's index"""
         if self.sequence_cnt != cur_kf.sequence:            # a new sequence starts in its own frame (:55-65)
             self.sequence_cnt += 1
             self.sequence_loop.append(False)
@@ -287,15 +350,14 @@ class PoseGraph:
         cur_kf.vio_R_w_i = self.w_r_vio @ cur_kf.vio_R_w_i
         cur_kf.index = self.global_index
         self.global_index += 1
-        loop_index = -1
-        if flag_detect_loop:
-            loop_index = self.voc.detectLoop(cur_kf.brief_descriptors, cur_kf.index)
-        else:
-            self.voc.add(cur_kf.brief_descriptors)             # addKeyFrameIntoVoc
+
+    def finishKeyFrame(self, cur_kf, loop_index, connect):
+        """addKeyFrame after the loop detection (:74-200): connect(old_kf) = the verification of the candidate (findConnection), then the
+        bookkeeping; returns the index of the verified loop partner or -1"""
         verified = -1
         if loop_index != -1:
             old_kf = self.getKeyFrame(loop_index)
-            if old_kf is not None and cur_kf.findConnection(old_kf, self.qic, self.tic):
+            if old_kf is not None and connect(old_kf):
                 verified = loop_index
                 if self.earliest_loop_index > loop_index or self.earliest_loop_index == -1:
                     self.earliest_loop_index = loop_index
@@ -481,3 +543,255 @@ class Vocabulary:
         _chk(self.P, self.L, self.L.vio_pg_detect_loop(self.h, d.ctypes.data, n, int(frame_index), C.addressof(loop), ids.ctypes.data, sc.ctypes.data,
                                                        C.addressof(m)), "vio_pg_detect_loop")
         return (loop.value, ids[:m.value], sc[:m.value]) if with_results else loop.value
+
+
+class StepOut(C.Structure):
+    """vio_pg_step_out (include/vio_posegraph.h)"""
+    _fields_ = [("status", C.c_int32), ("entry", C.c_int32), ("n_kp", C.c_int32), ("n_bow", C.c_int32), ("n_ret", C.c_int32), ("ids4", C.c_int32 * 4),
+                ("scores4", C.c_double * 4), ("loop_index", C.c_int32), ("n_match", C.c_int32)]
+
+
+def _device_ptr(x):
+    """the HBM address of a torch device tensor or a DeviceBuffer, None for host data"""
+    if hasattr(x, "data_ptr") and getattr(x, "is_cuda", False):
+        if not x.is_contiguous():
+            raise ValueError("device tensors must be contiguous")
+        return int(x.data_ptr())
+    if hasattr(x, "ptr") and hasattr(x, "download"):
+        return int(x.ptr)
+    return None
+
+
+class BatchDatabase:
+    """One keyframe database per sequence, resident on the device (vio_pg_batch_*): a step runs PoseGraph::detectLoop and the descriptor search
+    of KeyFrame::findConnection for all S sequences in one chain of launches and one copy back.  frame_index of a sequence = its number of
+    entries.
+
+        db = BatchDatabase(cfg, voc, pattern, S, max_keyframes, max_keypoints, max_window)
+        res = db.step(mode, gray, window_uv_list)         # mode[s]: 0 no keyframe, 1 detectLoop, 2 add only; gray [S, H, W]
+        res[s] -> None (mode 0) or dict(status, entry, n_kp, n_bow, n_ret, ids4, scores4, loop_index, n_match, best_index, best_dist, old_norm)
+
+    The three match arrays are None unless loop_index != -1.  The whole-batch arrays the library wrote into are db.best_index, db.best_dist
+    [S, max_window] and db.old_norm [S, max_window, 2] (host steps) or the DeviceBuffers db.dev[...] of the same names (device steps); rows of
+    sequences without a candidate are never written.  arena_keypoints: descriptor slots per sequence (default: the worst case,
+    max_keyframes * max_keypoints; 60 B each)."""
+
+    def __init__(self, cfg, vocabulary, pattern, S, max_keyframes, max_keypoints, max_window, fast_threshold=20, arena_keypoints=None):
+        self.P, self.L = _lib()
+        self.cfg, self.voc = cfg, vocabulary               # the vocabulary is borrowed: keep it alive
+        self.S, self.K, self.MK, self.MW = int(S), int(max_keyframes), int(max_keypoints), int(max_window)
+        pat = np.ascontiguousarray(pattern, np.int32)
+        if pat.shape != (1024,):
+            raise ValueError("pattern: int32[1024] = x1 | y1 | x2 | y2")
+        vh = getattr(vocabulary, "h", None)
+        if arena_keypoints is None:
+            self.h = self.L.vio_pg_batch_create(C.byref(cfg), vh, self.S, self.K, self.MK, self.MW, pat.ctypes.data, int(fast_threshold))
+        else:
+            self.h = self.L.vio_pg_batch_create_arena(C.byref(cfg), vh, self.S, self.K, self.MK, self.MW, pat.ctypes.data, int(fast_threshold),
+                                                      int(arena_keypoints))
+        if not self.h:
+            raise self.P.VioError("vio_pg_batch_create: %s" % self.L.vio_last_error().decode())
+        n = max(self.S * self.MW, 1)
+        self.best_index, self.best_dist = np.zeros((self.S, self.MW), np.int32), np.zeros((self.S, self.MW), np.int32)
+        self.old_norm = np.zeros((self.S, self.MW, 2), np.float32)
+        self._host_ptrs = None
+        self.dev = {}
+        self._n = n
+
+    def close(self):
+        if self.h:
+            self.L.vio_pg_batch_destroy(self.h)
+            self.h = None
+        for b in self.dev.values():
+            b.free()
+        self.dev = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        return _chk(self.P, self.L, rc, what)
+
+    def set_camera(self, seq, camera):
+        self._chk(self.L.vio_pg_batch_set_camera(self.h, int(seq), C.byref(camera)), "vio_pg_batch_set_camera")
+
+    def reset_seq(self, seq):
+        self._chk(self.L.vio_pg_batch_reset_seq(self.h, int(seq)), "vio_pg_batch_reset_seq")
+
+    def entries(self):
+        o = np.zeros(self.S, np.int32)
+        self._chk(self.L.vio_pg_batch_info(self.h, o.ctypes.data), "vio_pg_batch_info")
+        return o
+
+    def entry(self, seq, i):
+        """one stored entry: dict(kp_xy, kp_desc, kp_norm, bow_word, bow_value)"""
+        c = np.zeros(2, np.int32)
+        self._chk(self.L.vio_pg_batch_get_entry(self.h, int(seq), int(i), c.ctypes.data, None, None, None, None, None), "vio_pg_batch_get_entry")
+        n, nb = int(c[0]), int(c[1])
+        xy, d, nr = np.zeros((max(n, 1), 2), np.float32), np.zeros((max(n, 1), 4), np.uint64), np.zeros((max(n, 1), 2), np.float32)
+        w, v = np.zeros(max(nb, 1), np.int32), np.zeros(max(nb, 1))
+        self._chk(self.L.vio_pg_batch_get_entry(self.h, int(seq), int(i), c.ctypes.data, xy.ctypes.data, d.ctypes.data, nr.ctypes.data, w.ctypes.data,
+                                                v.ctypes.data), "vio_pg_batch_get_entry")
+        return dict(kp_xy=xy[:n], kp_desc=d[:n], kp_norm=nr[:n], bow_word=w[:nb], bow_value=v[:nb])
+
+    def set_timing(self, on):
+        self._chk(self.L.vio_pg_batch_set_timing(self.h, int(bool(on))), "vio_pg_batch_set_timing")
+
+    def last_timing(self):
+        """device milliseconds of the last step: describe, walk, bow, score, select, match, copy, total"""
+        o = np.zeros(8, np.float32)
+        self._chk(self.L.vio_pg_batch_last_timing(self.h, o.ctypes.data), "vio_pg_batch_last_timing")
+        return dict(zip(("describe", "walk", "bow", "score", "select", "match", "copy", "total"), (float(x) for x in o)))
+
+    # ---------------------------------------------------------------------------------------------- steps
+    def _mode(self, mode):
+        m = np.ascontiguousarray(mode, np.uint8).reshape(-1)
+        if len(m) != self.S:
+            raise ValueError("mode: one value per sequence")
+        return m
+
+    def _pad(self, rows_list, cap, width, dtype, what):
+        """list of per-sequence [n][width] arrays (None = empty) -> ([S][cap][width], counts [S]); the counts are passed on unclipped so
+        that the library refuses an overlong list"""
+        if len(rows_list) != self.S:
+            raise ValueError("%s: one array per sequence" % what)
+        out, cnt = np.zeros((self.S, max(cap, 1), width), dtype), np.zeros(self.S, np.int32)
+        for s, r in enumerate(rows_list):
+            if r is None:
+                continue
+            r = np.ascontiguousarray(r, dtype).reshape(-1, width)
+            cnt[s] = len(r)
+            out[s, :min(len(r), cap)] = r[:cap]
+        return out, cnt
+
+    def _devbuf(self, name, nbytes):
+        if name not in self.dev:
+            self.dev[name] = self.P.DeviceBuffer(max(int(nbytes), 8))
+        return self.dev[name]
+
+    def _match_ptrs(self, on_device):
+        if on_device:
+            return [self._devbuf("best_index", self._n * 4).ptr, self._devbuf("best_dist", self._n * 4).ptr, self._devbuf("old_norm", self._n * 8).ptr]
+        return [self.best_index.ctypes.data, self.best_dist.ctypes.data, self.old_norm.ctypes.data]
+
+    def _results(self, mode, n_win, out, on_device):
+        res = []
+        bi = bd = on = None
+        for s in range(self.S):
+            if mode[s] == 0:
+                res.append(None)
+                continue
+            o = out[s]
+            r = dict(status=int(o.status), entry=int(o.entry), n_kp=int(o.n_kp), n_bow=int(o.n_bow), n_ret=int(o.n_ret),
+                     ids4=np.array(o.ids4[:o.n_ret], np.int32), scores4=np.array(o.scores4[:o.n_ret], np.float64), loop_index=int(o.loop_index),
+                     n_match=int(o.n_match), best_index=None, best_dist=None, old_norm=None)
+            if r["status"] == 0 and r["loop_index"] != -1:
+                if on_device and bi is None:
+                    bi = self.dev["best_index"].download(0, (self.S, self.MW), np.int32)
+                    bd = self.dev["best_dist"].download(0, (self.S, self.MW), np.int32)
+                    on = self.dev["old_norm"].download(0, (self.S, self.MW, 2), np.float32)
+                a, b, c = (bi, bd, on) if on_device else (self.best_index, self.best_dist, self.old_norm)
+                n = int(n_win[s])
+                r["best_index"], r["best_dist"], r["old_norm"] = a[s, :n].copy(), b[s, :n].copy(), c[s, :n].copy()
+            res.append(r)
+        return res
+
+    def step_desc(self, mode, kp_desc_list, kp_norm_list, win_desc_list, on_device=False):
+        """descriptors given: per sequence kp_desc [n][4] u64, kp_norm [n][2] f32, win_desc [m][4] u64 (None = none).  on_device: the padded
+        arrays are uploaded first and the library is handed HBM addresses (the path of a caller whose descriptors are on the device)."""
+        mode = self._mode(mode)
+        kd, nk = self._pad(kp_desc_list, self.MK, 4, np.uint64, "kp_desc_list")
+        kn, nk2 = self._pad(kp_norm_list, self.MK, 2, np.float32, "kp_norm_list")
+        wd, nw = self._pad(win_desc_list, self.MW, 4, np.uint64, "win_desc_list")
+        if not np.array_equal(nk, nk2):
+            raise ValueError("kp_desc_list and kp_norm_list differ in length")
+        out = (StepOut * self.S)()
+        if on_device:
+            bufs = []
+            for name, a in (("in_kp_desc", kd), ("in_kp_norm", kn), ("in_win_desc", wd)):
+                b = self._devbuf(name, a.nbytes)
+                b.upload(0, a)
+                bufs.append(b.ptr)
+        else:
+            bufs = [kd.ctypes.data, kn.ctypes.data, wd.ctypes.data]
+        self._chk(self.L.vio_pg_batch_step_desc(self.h, mode.ctypes.data, nk.ctypes.data, bufs[0], bufs[1], nw.ctypes.data, bufs[2], int(on_device),
+                                                C.addressof(out), *self._match_ptrs(on_device)), "vio_pg_batch_step_desc")
+        return self._results(mode, nw, out, on_device)
+
+    def step(self, mode, gray, window_uv_list, n_win=None):
+        """from images: gray [S, H, W] u8 (numpy, or a torch device tensor / DeviceBuffer: then the step runs with on_device = 1);
+        window_uv_list: per sequence [n][2] pixel coordinates (None = none), or, with n_win [S] given, one [S, max_window, 2] float32 array on
+        the same side as gray"""
+        mode = self._mode(mode)
+        gptr = _device_ptr(gray)
+        on_device = gptr is not None
+        if n_win is None:
+            uv, nw = self._pad(window_uv_list, self.MW, 2, np.float32, "window_uv_list")
+            if on_device:
+                b = self._devbuf("in_win_uv", uv.nbytes)
+                b.upload(0, uv)
+                uvptr = b.ptr
+            else:
+                uvptr = uv.ctypes.data
+        else:
+            nw = np.ascontiguousarray(n_win, np.int32).reshape(self.S)
+            uvptr = _device_ptr(window_uv_list)
+            if (uvptr is not None) != on_device:
+                raise ValueError("gray and the window points must both be host arrays or both be on the device")
+            if uvptr is None:
+                uv = np.ascontiguousarray(window_uv_list, np.float32).reshape(self.S, max(self.MW, 1), 2)
+                uvptr = uv.ctypes.data
+        if not on_device:
+            gray = np.ascontiguousarray(gray, np.uint8)
+            if gray.shape != (self.S, self.cfg.height, self.cfg.width):
+                raise ValueError("gray: [S, height, width] uint8")
+            gptr = gray.ctypes.data
+        out = (StepOut * self.S)()
+        self._chk(self.L.vio_pg_batch_step(self.h, mode.ctypes.data, gptr, nw.ctypes.data, uvptr, int(on_device), C.addressof(out),
+                                           *self._match_ptrs(on_device)), "vio_pg_batch_step")
+        return self._results(mode, nw, out, on_device)
+
+
+class PoseGraphBatch:
+    """S PoseGraph states over one BatchDatabase: add_keyframes takes what VioBatch.publish() returns and the frames' images, runs one
+    database step for the whole batch, the geometric verification (find_connection, host) for the sequences that report a candidate, and
+    PoseGraph.addKeyFrame's bookkeeping for each.  graphs[s] is the sequence's PoseGraph (keyframelist, optimize(), savePoseGraph's poses);
+    its keyframes carry no descriptors: those live in the database (database.entry(s, index))."""
+
+    def __init__(self, database, qic, tic):
+        self.db = database
+        self.graphs = [PoseGraph(None, qic, tic) for _ in range(database.S)]
+
+    def add_keyframes(self, counts, kf_pose, kf_points, gray, detect_loop=True):
+        """counts [S, 4] (n_cloud, n_margin, n_kf, kf_valid), kf_pose [S, 8], kf_points [S, cap, 8] of VioBatch.publish(); gray [S, H, W] = the
+        images with those stamps.  Sequences with kf_valid == 0 add nothing.  Returns the verified loop partner per sequence (-1: none,
+        None: no keyframe)."""
+        S = self.db.S
+        counts = np.asarray(counts).reshape(S, 4)
+        kf_pose, kf_points = np.asarray(kf_pose, np.float64).reshape(S, 8), np.asarray(kf_points, np.float64)
+        mode = np.where(counts[:, 3] != 0, 1 if detect_loop else 2, 0).astype(np.uint8)
+        kfs, uv = [None] * S, [None] * S
+        for s in range(S):
+            if mode[s]:
+                n = min(int(counts[s, 2]), kf_points.shape[1])
+                kfs[s] = KeyFrame.from_publication_row(-1, kf_pose[s], kf_points[s, :n])
+                uv[s] = kfs[s].point_2d_uv
+        res = self.db.step(mode, gray, uv)
+        verified = [None] * S
+        for s in range(S):
+            if not mode[s]:
+                continue
+            g, kf, r = self.graphs[s], kfs[s], res[s]
+            if r["status"] != 0:
+                raise self.db.P.VioError("sequence %d: the keyframe database is full (status %d)" % (s, r["status"]))
+            g.beginKeyFrame(kf)
+            assert kf.index == r["entry"], "database entries and graph keyframes out of step"
+            verified[s] = g.finishKeyFrame(kf, r["loop_index"],
+                                           lambda old, kf=kf, r=r, g=g: kf.connectMatched(old.index, r["best_index"], r["old_norm"], g.qic, g.tic))
+        return verified
+
+    def optimize(self):
+        return [g.optimize() for g in self.graphs]
