@@ -748,6 +748,55 @@ typedef struct vio_marg_stage_out {
 int vio_debug_marg_set(vio_batch *h, int seq, const vio_marg_stage_in *in);
 int vio_debug_marg_run(vio_batch *h);
 int vio_debug_marg_get(vio_batch *h, int seq, vio_marg_stage_out *out);
+/* The SOLVER on a caller-chosen state, launch by launch, through the kernels a handle really launches (tests/test_gpu_solve_stage.py).
+ * vio_debug_solve_set takes the input of vio_debug_marg_set through the same validation and writes the same state, with do_solve = 1,
+ * solver_flag = 1, do_marg = 0, openExEstimation = 0, no relocalisation request, init_frame = 0 and last_P / last_R (what failureDetection
+ * compares the solved window with) = the staged newest frame, as a processed frame leaves them.  It refuses in addition, with VIO_EINVAL and
+ * nothing written, what the solver indexes with and the marginalisation does not: lm_est_flag of a live slot outside 0 .. 2; more projection
+ * residuals (sum of lm_nobs - 1 over the landmarks in the problem: !lm_dyn, lm_nobs >= 2, lm_start < W - 2) than the residual list holds
+ * (NRES - 2 NL records) or, on a phased handle, than its evaluation launch covers (landmarks in the problem cannot exceed NL once the list is
+ * valid).  marginalization_flag
+ * is stored and otherwise ignored.
+ * vio_debug_solve_run(h, slots, stop_phase, radius0), slots >= 0: ps_setup, `slots` whole slots (evaluate [+ accept], assemble, Schur, serial, line
+ * search), then the kernels of one more slot up to and including stop_phase, then it waits; no ps_final, so the staged window stays as it is and
+ * the state can be run again.  radius0 > 0 overwrites SolveSt::radius by a copy between ps_setup and the first slot -- the only state the harness
+ * touches itself; the copy goes to the sequences vio_debug_solve_set has staged on this handle and to no other (an idle sequence's snapshot stays as it is).  slots + (stop_phase != NONE) may not exceed max_iterations + the handle's extra slots.  slots < 0: the whole solve with
+ * ps_final (or the persistent kernel), the launches of vio_feed on the back-end stream (stop_phase and radius0 must be 0); the only form a
+ * handle without the phased solver (VIO_SOLVE_MODE=0, or a configuration it does not cover) accepts.
+ * vio_debug_solve_get (every pointer may be NULL; P = 15 (W + 1) + 7, parameter order pose k at 6 k, speed-bias k at 6 (W + 1) + 9 k, extrinsic at
+ * 15 (W + 1), td at 15 (W + 1) + 6; F, Fa = landmarks in the problem / variable ones; phased handles only, VIO_EINVAL otherwise):
+ *   always (after ps_setup)      scal_i [11] = stage iter iters_done F Fa nres ex_active td_active vext constrained fused; scal_d [7] = cost ccost
+ *                                radius mu alpha dogleg_norm model_change; X [16 (W + 1) + 8] = pose [W+1][7], speed-bias [W+1][9], extrinsic [7], td;
+ *                                feat [NL] (first F: inverse depths in list order); var_slots [NL] (first Fa: landmark slots in solver order)
+ *                                (ccost = the partial costs of the last evaluation, SolveSt::part, summed in index order: the kernels keep the
+ *                                candidate's cost in a register and never write SolveSt::ccost)
+ *   after VIO_SOLVE_STOP_ASM_A   cost (slot 0) or ccost, the accept / reject decision and the new radius (later slots); Hpl [NL][P] (first Fa rows;
+ *                                columns of poses and, with vext, of extrinsic and td -- every other column is returned as 0, the kernels leave
+ *                                them unwritten), Hll, gl [NL] of the CURRENT point (X, feat), unscaled
+ *   after VIO_SOLVE_STOP_SCHUR   H [P][P] (full, symmetric, unscaled), g [P], sp [P] (Jacobi column scaling, 0 = constant parameter); Sc [LW][LW]
+ *                                (LW = P rounded up to 16): the lower 16 x 16 tiles untiled, 0 above them.  While the column scaling is being fixed
+ *                                (the first linearisation of a solve, and Cholesky retries) the tiles hold U = sum_k w_k h_k h_k^T, the landmark part
+ *                                of the Schur complement, in the tiles the landmark rows touch only (the others are stale); afterwards all of them
+ *                                hold S = Sp (H - U) Sp + mu D^2 with unit diagonal for constant and padding parameters
+ *   after VIO_SOLVE_STOP_SERIAL  sl [NL], dgp [P] / dgl [NL] (trust-region diagonal D), gnp / gnl (Gauss-Newton step, D-scaled: - D y), stp / stl
+ *                                (dogleg step in the Jacobi-scaled variables: x step = sp stp, sl stl), alpha, dogleg_norm, model_change, Xc and
+ *                                cfeat (the candidate); on windows beyond W = 10 Sc then holds the Cholesky factor
+ *   after VIO_SOLVE_STOP_LS      Xc, cfeat: the candidate the projected line search of a bounds-constrained solve settled on
+ * Landmark vectors are indexed by solver order (var_slots), the first Fa entries. */
+enum { VIO_SOLVE_STOP_NONE = 0, VIO_SOLVE_STOP_ASM_A = 1, VIO_SOLVE_STOP_SCHUR = 2, VIO_SOLVE_STOP_SERIAL = 3, VIO_SOLVE_STOP_LS = 4 };
+typedef struct vio_solve_stage_out {
+    int32_t *scal_i;
+    double *scal_d;
+    double *X, *Xc, *feat, *cfeat;
+    int32_t *var_slots;
+    double *H, *g, *sp;
+    double *Hpl, *Hll, *gl, *sl;
+    double *Sc;
+    double *dgp, *dgl, *gnp, *gnl, *stp, *stl;
+} vio_solve_stage_out;
+int vio_debug_solve_set(vio_batch *h, int seq, const vio_marg_stage_in *in);
+int vio_debug_solve_run(vio_batch *h, int slots, int stop_phase, double radius0);
+int vio_debug_solve_get(vio_batch *h, int seq, vio_solve_stage_out *out);
 
 #ifdef __cplusplus
 }

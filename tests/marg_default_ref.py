@@ -126,7 +126,7 @@ def _as_ld(M):
 
 # ------------------------------------------------------------------------------------------------------------ the generator
 DEFAULTS = dict(W=4, F0=5, seed=0, estimate_td=0, use_imu=1, prior="full", moved=0, second_new=0, flat=0, outlier=0, blind=0, long_dt=0, ring_base=0,
-                rot_pre=0, shuffle=1, tr=0.0)
+                rot_pre=0, shuffle=1, tr=0.0, extra_spec=())
 
 
 def make_case(cfg, **kw):
@@ -137,6 +137,7 @@ def make_case(cfg, **kw):
     1e-2 in every present block and the quaternion of x0's pose 2 is negated (q0^-1 q has a negative scalar part); flat = the first `flat` of
     those landmarks are seen from frames 0 and 1 only, and frame 1 has the pose of frame 0 exactly (d = 0 up to round-off); outlier = 1: one
     observation is 0.2 off in x; blind = 1: no marginalised landmark sees frame W; long_dt = 1: interval 1 has sum_dt >= 10.
+    extra_spec = further landmarks (start, nobs, dyn) behind the standard ones (tests/solve_ref.py: the solver's cases).
     Returns dict(kw, st = the tables for VioBatch.marg_stage_set in SLOTS slots (pad_tables widens them), X = the parameters)."""
     k = dict(DEFAULTS, **kw)
     W, F0 = k["W"], k["F0"]
@@ -171,6 +172,8 @@ def make_case(cfg, **kw):
     if F0 > k["flat"]:
         spec[F0 - 1] = (0, top, 0)                         # the longest track is always there
     spec += [(0, 3, 1), (1, min(3, W1 - 1), 0), (W - 2, 2, 0), (0, 1, 0), (1, W, 0)]       # dynamic, start > 0, start >= W - 2, nobs = 1, a long later one
+    spec += [tuple(int(v) for v in e) for e in k["extra_spec"]]
+    assert len(spec) <= NLs
     slots = rng.permutation(NLs)[:len(spec)] if k["shuffle"] else np.arange(len(spec))
     order = np.array(slots, np.int32)
     if k["shuffle"]:
@@ -273,6 +276,73 @@ def pad_tables(st, NL):
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------ the factors, with their error terms
+def prior_dx(X, x0, present, W, cv):
+    """The prior's tangent dx = x (-) x0 over its n = 6 W + 16 slots (pose 0 .. W-1, speed-bias 0, extrinsic, td; 0 where a block is absent), the
+    scale of each entry's error (ddx = KF eps scale) and the smallest scalar part of q0^-1 q met"""
+    n = 6 * W + 16
+    dx, sdx, w_min = np.zeros(n), np.zeros(n), None
+    for s in range(W):
+        if present[s]:
+            d6, s6, w = fr.pose_delta(X["pose"][s], x0[7 * s:7 * s + 7])
+            dx[6 * s:6 * s + 6], sdx[6 * s:6 * s + 6] = d6, s6
+            w_min = float(w) if w_min is None else min(w_min, float(w))
+    if present[W]:
+        dx[6 * W:6 * W + 9] = _f64(cv(X["sb"][0]) - cv(x0[7 * W:7 * W + 9]))
+        sdx[6 * W:6 * W + 9] = np.maximum(np.abs(X["sb"][0]), np.abs(x0[7 * W:7 * W + 9]))
+    if present[W + 1]:
+        d6, s6, _ = fr.pose_delta(X["ex"], x0[7 * W + 9:7 * W + 16])
+        dx[6 * W + 9:6 * W + 15], sdx[6 * W + 9:6 * W + 15] = d6, s6
+    if present[W + 2]:
+        dx[6 * W + 15] = X["td"] - x0[7 * W + 16]
+        sdx[6 * W + 15] = max(abs(X["td"]), abs(x0[7 * W + 16]))
+    return dx, sdx, w_min
+
+
+_pre_cache = {}
+
+
+def imu_pre(cfg, st, j):
+    """factor_ref.preint of the samples of the interval that ends in frame j (cached on the samples)"""
+    ns = int(st["imu_n"][j])
+    noise = (float(cfg.acc_n), float(cfg.gyr_n), float(cfg.acc_w), float(cfg.gyr_w))
+    a = (st["imu_dt"][j, :ns], st["imu_acc"][j, :ns], st["imu_gyr"][j, :ns], st["imu_acc0"][j], st["imu_gyr0"][j], st["imu_ba"][j], st["imu_bg"][j])
+    key = tuple(np.ascontiguousarray(x, np.float64).tobytes() for x in a) + (noise,)
+    if key not in _pre_cache:
+        _pre_cache[key] = fr.preint(*a, noise)
+    return _pre_cache[key], ns
+
+
+def imu_gram(cfg, pre, ns, pi, sbi, pj, sbj):
+    """The IMU factor between two frames at the given parameters: G = [J r]^T C^-1 [J r] (31 x 31, columns pose_i, speed-bias_i, pose_j,
+    speed-bias_j, residual), its entrywise error bound EG (module docstring) and kappa of the Jacobi-scaled covariance"""
+    a4 = (pre, float(cfg.g_norm), pi, sbi, pj, sbj)
+    rr, rs = fr.imu_residual(*a4)
+    Jf, Js = fr.imu_jacobian_formula(*a4)
+    rs = np.maximum(rs, np.r_[np.full(3, pre["scale_p"]), np.ones(3), np.full(3, pre["scale_v"]), np.zeros(6)])
+    G = fr.gram_ref(Jf, rr, pre["cov"])
+    cov = 0.5 * (pre["cov"] + pre["cov"].T)
+    dc_ = 1.0 / np.sqrt(np.diag(cov))
+    ev = np.linalg.eigvalsh(cov * np.outer(dc_, dc_))          # the Jacobi-scaled covariance: what a Cholesky factor's accuracy depends on
+    kappa = float(ev[-1] / ev[0])
+    cols = np.hstack([Js, rs[:, None]]) * dc_[:, None]
+    e_col = C * (ns + 1) * KF * EPS * np.sqrt((cols * cols).sum(axis=0)) / np.sqrt(ev[0])
+    sg = np.sqrt(np.abs(np.diag(G)))
+    EG = e_col[:, None] * sg[None, :] + sg[:, None] * e_col[None, :] + C * (ns + 31) * EPS * kappa * np.outer(sg, sg)
+    return G, EG, kappa
+
+
+def proj_rows(K, pi, pj, ex, inv_dep, td, oi, oj, use_td):
+    """One projection pair under CauchyLoss(1): the weighted Jacobian w J (2 x 20: pose_i, pose_j, extrinsic, td, inverse depth), the weighted
+    residual w r, their factor-level error bounds dJ, dr (module docstring), the weight w = sqrt(rho') and the raw residual"""
+    a9 = (K, pi, pj, ex, inv_dep, td, oi, oj, use_td)
+    r2, r2s = fr.proj_residual(*a9)
+    J, Js = fr.proj_jacobian_formula(*a9)
+    w = fr.cauchy_weight(r2)
+    dw = float(np.abs(r2) @ (KF * EPS * r2s)) / (1.0 + float(r2 @ r2)) + 4 * EPS
+    return w * J, w * KF * EPS * Js + np.abs(w * J) * dw, w * r2, w * KF * EPS * r2s + np.abs(w * r2) * dw, w, r2, r2s
+
+
 # ------------------------------------------------------------------------------------------------------------ the definition
 class Ref:
     pass
@@ -334,22 +404,7 @@ def reference(case, cfg, route=None):
             return rT
         idx = np.array([pm(a) for a in range(n)])
         H, pr, x0 = np.asarray(prior["H"], np.float64), np.asarray(prior["r"], np.float64), np.asarray(prior["x0"], np.float64)
-        dx, sdx = np.zeros(n), np.zeros(n)
-        r.w_min = None
-        for s in range(W):
-            if present_in[s]:
-                d6, s6, w = fr.pose_delta(X["pose"][s], x0[7 * s:7 * s + 7])
-                dx[6 * s:6 * s + 6], sdx[6 * s:6 * s + 6] = d6, s6
-                r.w_min = float(w) if r.w_min is None else min(r.w_min, float(w))
-        if present_in[W]:
-            dx[6 * W:6 * W + 9] = _f64(cv(X["sb"][0]) - cv(x0[7 * W:7 * W + 9]))
-            sdx[6 * W:6 * W + 9] = np.maximum(np.abs(X["sb"][0]), np.abs(x0[7 * W:7 * W + 9]))
-        if present_in[W + 1]:
-            d6, s6, _ = fr.pose_delta(X["ex"], x0[7 * W + 9:7 * W + 16])
-            dx[6 * W + 9:6 * W + 15], sdx[6 * W + 9:6 * W + 15] = d6, s6
-        if present_in[W + 2]:
-            dx[6 * W + 15] = X["td"] - x0[7 * W + 16]
-            sdx[6 * W + 15] = max(abs(X["td"]), abs(x0[7 * W + 16]))
+        dx, sdx, r.w_min = prior_dx(X, x0, present_in, W, cv)
         r.dx, r.prior_idx = dx, idx
         Hc = cv(H)
         grad = cv(pr) + Hc @ cv(dx)
@@ -372,26 +427,11 @@ def reference(case, cfg, route=None):
         # ---- IMU factor (0, 1)
         if cfg.use_imu:
             j = 1
-            ns = int(st["imu_n"][j])
-            noise = (float(cfg.acc_n), float(cfg.gyr_n), float(cfg.acc_w), float(cfg.gyr_w))
-            pre = fr.preint(st["imu_dt"][j, :ns], st["imu_acc"][j, :ns], st["imu_gyr"][j, :ns], st["imu_acc0"][j], st["imu_gyr0"][j], st["imu_ba"][j],
-                            st["imu_bg"][j], noise)
+            pre, ns = imu_pre(cfg, st, j)
             r.sum_dt = pre["sum_dt"]
             if pre["sum_dt"] < 10.0:
                 r.imu_used = True
-                a4 = (pre, float(cfg.g_norm), X["pose"][0], X["sb"][0], X["pose"][1], X["sb"][1])
-                rr, rs = fr.imu_residual(*a4)
-                Jf, Js = fr.imu_jacobian_formula(*a4)
-                rs = np.maximum(rs, np.r_[np.full(3, pre["scale_p"]), np.ones(3), np.full(3, pre["scale_v"]), np.zeros(6)])
-                G = fr.gram_ref(Jf, rr, pre["cov"])
-                cov = 0.5 * (pre["cov"] + pre["cov"].T)
-                dc_ = 1.0 / np.sqrt(np.diag(cov))
-                ev = np.linalg.eigvalsh(cov * np.outer(dc_, dc_))          # the Jacobi-scaled covariance: what a Cholesky factor's accuracy depends on
-                r.cov_kappa = float(ev[-1] / ev[0])
-                cols = np.hstack([Js, rs[:, None]]) * dc_[:, None]
-                e_col = C * (ns + 1) * KF * EPS * np.sqrt((cols * cols).sum(axis=0)) / np.sqrt(ev[0])
-                sg = np.sqrt(np.abs(np.diag(G)))
-                EG = e_col[:, None] * sg[None, :] + sg[:, None] * e_col[None, :] + C * (ns + 31) * EPS * r.cov_kappa * np.outer(sg, sg)
+                G, EG, r.cov_kappa = imu_gram(cfg, pre, ns, X["pose"][0], X["sb"][0], X["pose"][1], X["sb"][1])
                 ii = np.r_[np.arange(15), md + np.arange(6), rS + np.arange(9)]
                 Gc = cv(G)
                 A[np.ix_(ii, ii)] = A[np.ix_(ii, ii)] + Gc[:30, :30]
@@ -412,21 +452,17 @@ def reference(case, cfg, route=None):
             dJq, dJl, drw = np.zeros((2 * m, mq)), np.zeros(2 * m), np.zeros(2 * m)
             for kf in range(1, no):
                 oj = st["lm_obs"][slot, (kf + rb) % W1]
-                a9 = (K, X["pose"][0], X["pose"][kf], X["ex"], inv_dep, X["td"], oi, oj, use_td)
-                r2, r2s = fr.proj_residual(*a9)
-                J, Js = fr.proj_jacobian_formula(*a9)
-                w = fr.cauchy_weight(r2)
-                dw = float(np.abs(r2) @ (KF * EPS * r2s)) / (1.0 + float(r2 @ r2)) + 4 * EPS
+                wJ, dJ, wr, dr, w, _, _ = proj_rows(K, X["pose"][0], X["pose"][kf], X["ex"], inv_dep, X["td"], oi, oj, use_td)
                 r.weights.append(w)
                 cols = np.r_[np.arange(6), md + 6 * (kf - 1) + np.arange(6), rE + np.arange(6)]
                 src = np.arange(18)
                 if use_td:
                     cols, src = np.r_[cols, rT], np.arange(19)
                 rows = slice(2 * (kf - 1), 2 * kf)
-                Jq[rows, cols] = w * J[:, src]
-                dJq[rows, cols] = w * KF * EPS * Js[:, src] + np.abs(w * J[:, src]) * dw
-                Jl[rows], dJl[rows] = w * J[:, 19], w * KF * EPS * Js[:, 19] + np.abs(w * J[:, 19]) * dw
-                rw[rows], drw[rows] = w * r2, w * KF * EPS * r2s + np.abs(w * r2) * dw
+                Jq[rows, cols] = wJ[:, src]
+                dJq[rows, cols] = dJ[:, src]
+                Jl[rows], dJl[rows] = wJ[:, 19], dJ[:, 19]
+                rw[rows], drw[rows] = wr, dr
                 present[kf - 1] = 1
             present[W + 1] = 1
             if use_td:

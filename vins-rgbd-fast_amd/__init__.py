@@ -218,6 +218,18 @@ class MargStageOut(C.Structure):
                                           "b_r", "hbm_valid")]
 
 
+class SolveStageOut(C.Structure):
+    """vio_solve_stage_out (include/vio_abi.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("scal_i", "scal_d", "X", "Xc", "feat", "cfeat", "var_slots", "H", "g", "sp", "Hpl", "Hll", "gl", "sl", "Sc",
+                                          "dgp", "dgl", "gnp", "gnl", "stp", "stl")]
+
+
+SOLVE_STOP = dict(none=0, asm_a=1, schur=2, serial=3, ls=4)   # VIO_SOLVE_STOP_*
+_SOLVE_SCAL_I = ("stage", "iter", "iters_done", "F", "Fa", "nres", "ex_active", "td_active", "vext", "constrained", "fused")
+_SOLVE_SCAL_D = ("cost", "ccost", "radius", "mu", "alpha", "dogleg_norm", "model_change")
+PS_STAGES = ("idle", "eval_x0", "asm", "schur", "step", "eval_c", "done")   # SolveSt::stage
+
+
 def stage_publish(tables, W, n_lm, ring_base, flags, cap, fill=None, lists=(True, True, True)):
     """vio_stage_publish: the publishers' device routine on the tables of one synthetic sequence.  tables: dict of lm_order, lm_id, lm_start,
     lm_nobs, lm_solve_flag, lm_dyn ([NL] integers), lm_depth [NL], lm_obs [NL, W+1, 9], Ps [W+1, 3], Rs [W+1, 3, 3], Headers [W+1], ric [3, 3],
@@ -952,7 +964,7 @@ class VioBatch:
         k = self._chk(self.L.vio_get_prior(self.h, seq, J.ctypes.data, r.ctypes.data, x0.ctypes.data, pres.ctypes.data), "vio_get_prior")
         return (J, r, x0, pres) if k else None
 
-    def marg_stage_set(self, seq, st):
+    def marg_stage_set(self, seq, st, _fn="vio_debug_marg_set"):
         """vio_debug_marg_set: stage one sequence's pre-marginalisation state (include/vio_abi.h vio_marg_stage_in).  st: dict of lm_order [n_lm]
         (n_lm may be given on its own), lm_id, lm_start, lm_nobs, lm_solve_flag, lm_dyn, lm_est_flag [NL], lm_depth [NL], lm_obs [NL, W+1, 9], Ps, Vs,
         Bas, Bgs [W+1, 3], Rs [W+1, 3, 3], Headers [W+1], ric [3, 3], tic, g [3], td, ring_base, marginalization_flag, pre_idx [W+1], prior = None or
@@ -997,8 +1009,9 @@ class VioBatch:
                 setattr(s, name, arr(st[name], np.float64, (W + 1) * 64 * 3, name))
             for name in ("imu_acc0", "imu_gyr0", "imu_ba", "imu_bg"):
                 setattr(s, name, arr(st[name], np.float64, (W + 1) * 3, name))
-        self.L.vio_debug_marg_set.argtypes = [C.c_void_p, C.c_int, C.POINTER(MargStageIn)]
-        self._chk(self.L.vio_debug_marg_set(self.h, int(seq), C.byref(s)), "vio_debug_marg_set")
+        fn = getattr(self.L, _fn)
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(MargStageIn)]
+        self._chk(fn(self.h, int(seq), C.byref(s)), _fn)
 
     def marg_stage_run(self):
         """vio_debug_marg_run: the marginalisation launches of vio_feed for this handle, then a wait"""
@@ -1021,6 +1034,47 @@ class VioBatch:
         self._chk(self.L.vio_debug_marg_get(self.h, int(seq), C.byref(s)), "vio_debug_marg_get")
         o["prior_c0"], o["has_prior"], o["hbm"] = float(o["prior_c0"][0]), int(o["has_prior"][0]), bool(o.pop("hbm_valid")[0])
         o["dbg"] = o.pop("dbg5")
+        return o
+
+    def solve_stage_set(self, seq, st):
+        """vio_debug_solve_set: the state of marg_stage_set (same dict), staged in front of a solve"""
+        self.marg_stage_set(seq, st, _fn="vio_debug_solve_set")
+
+    def solve_stage_run(self, slots=-1, stop="none", radius0=0.0):
+        """vio_debug_solve_run: ps_setup, `slots` whole slots and the next one up to `stop` (a key of SOLVE_STOP), then a wait; slots < 0: the
+        whole solve with ps_final, as vio_feed launches it"""
+        self.L.vio_debug_solve_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double]
+        self._chk(self.L.vio_debug_solve_run(self.h, int(slots), SOLVE_STOP[stop], float(radius0)), "vio_debug_solve_run")
+
+    def solve_stage_get(self, seq):
+        """vio_debug_solve_get: dict of the SolveSt scalars by name (stage as a name of PS_STAGES), X / Xc = dict(pose [W+1, 7], sb [W+1, 9], ex [7],
+        td), feat / cfeat [F], var_slots [Fa], H [P, P], g, sp [P], Hpl [Fa, P], Hll, gl, sl [Fa], Sc [LW, LW] (lower tiles), dgp / gnp / stp [P],
+        dgl / gnl / stl [Fa]; which of them mean what after which stop phase: include/vio_abi.h"""
+        W1, NL = self.W + 1, self.capacity()["landmarks"]
+        Pn = 15 * W1 + 7
+        LW = (Pn + 15) & ~15
+        o = dict(scal_i=np.full(11, -1, np.int32), scal_d=np.full(7, np.nan), X=np.full(16 * W1 + 8, np.nan), Xc=np.full(16 * W1 + 8, np.nan),
+                 feat=np.full(NL, np.nan), cfeat=np.full(NL, np.nan), var_slots=np.full(NL, -1, np.int32), H=np.full((Pn, Pn), np.nan),
+                 g=np.full(Pn, np.nan), sp=np.full(Pn, np.nan), Hpl=np.full((NL, Pn), np.nan), Hll=np.full(NL, np.nan), gl=np.full(NL, np.nan),
+                 sl=np.full(NL, np.nan), Sc=np.full((LW, LW), np.nan), dgp=np.full(Pn, np.nan), dgl=np.full(NL, np.nan), gnp=np.full(Pn, np.nan),
+                 gnl=np.full(NL, np.nan), stp=np.full(Pn, np.nan), stl=np.full(NL, np.nan))
+        s = SolveStageOut()
+        for name, a in o.items():
+            setattr(s, name, a.ctypes.data)
+        self.L.vio_debug_solve_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(SolveStageOut)]
+        self._chk(self.L.vio_debug_solve_get(self.h, int(seq), C.byref(s)), "vio_debug_solve_get")
+        o.update(zip(_SOLVE_SCAL_I, (int(v) for v in o.pop("scal_i"))))
+        o.update(zip(_SOLVE_SCAL_D, (float(v) for v in o.pop("scal_d"))))
+        o["stage"] = PS_STAGES[o["stage"]]
+        for k in ("X", "Xc"):
+            v = o[k]
+            o[k] = dict(pose=v[:7 * W1].reshape(W1, 7).copy(), sb=v[7 * W1:16 * W1].reshape(W1, 9).copy(), ex=v[16 * W1:16 * W1 + 7].copy(),
+                        td=float(v[16 * W1 + 7]))
+        F, Fa = o["F"], o["Fa"]
+        for k in ("feat", "cfeat"):
+            o[k] = o[k][:F].copy()
+        for k in ("var_slots", "Hpl", "Hll", "gl", "sl", "dgl", "gnl", "stl"):
+            o[k] = o[k][:Fa].copy()
         return o
 
     KERNELS = ("fe_begin", "fe_pyrdown", "fe_predict", "fe_lk", "fe_select", "fe_fast", "fe_add", "be_ingest", "be_solve", "be_marg")

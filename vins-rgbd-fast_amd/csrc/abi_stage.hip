@@ -483,24 +483,22 @@ static bool all_finite(const double *p, size_t n) {
     for (size_t i = 0; i < n; i++) if (!std::isfinite(p[i])) return false;
     return true;
 }
-#define MARG_STAGE_REFUSE(msg) do { g_err = std::string("vio_debug_marg_set: ") + (msg); return VIO_EINVAL; } while (0)
-int vio_debug_marg_set(vio_batch *h, int seq, const vio_marg_stage_in *in) {
-    VIO_ENTER(h, seq, true);
-    if (!in) return VIO_EINVAL;
+#define MARG_STAGE_REFUSE(msg) do { g_err = std::string(who) + ": " + (msg); return VIO_EINVAL; } while (0)
+// The validation vio_debug_marg_set and vio_debug_solve_set share: everything a kernel of either stage indexes with.  Writes nothing; live[slot] = the
+// slot is in the list.  solve: also what only the solver indexes with (include/vio_abi.h vio_debug_solve_set).
+static int stage_validate(const vio_batch *h, const vio_marg_stage_in *in, const char *who, bool solve, std::vector<char> &live) {
     const DevCfg &C = h->hc;
-    Batch &B = h->B;
     const int W = C.W, W1 = W + 1, NL = C.NL, n = C.NPRIOR;
     const vio_publish_tables &t = in->t;
-    // ---- validation: nothing is written before all of it has passed
-    if (C.MX > 0 || C.c.marg_exact) MARG_STAGE_REFUSE("the handle runs the literal marginalisation");
     if (!t.lm_order || !t.lm_id || !t.lm_start || !t.lm_nobs || !t.lm_solve_flag || !t.lm_dyn || !t.lm_depth || !t.lm_obs || !t.Ps || !t.Rs || !t.Headers ||
         !t.ric || !t.tic || !in->lm_est_flag || !in->Vs || !in->Bas || !in->Bgs || !in->g || !in->pre_idx)
         MARG_STAGE_REFUSE("a table is missing");
     if (in->n_lm < 0 || in->n_lm > NL) MARG_STAGE_REFUSE("n_lm outside 0 .. NL");
     if (in->ring_base < 0 || in->ring_base > W) MARG_STAGE_REFUSE("ring_base outside 0 .. W");
     if ((in->marginalization_flag | in->has_prior) & ~1) MARG_STAGE_REFUSE("marginalization_flag and has_prior are 0 or 1");
-    std::vector<char> live(NL, 0);
+    live.assign(NL, 0);
     int F0 = 0;
+    long long nres = 0;
     for (int k = 0; k < in->n_lm; k++) {
         const int slot = t.lm_order[k];
         if (slot < 0 || slot >= NL) MARG_STAGE_REFUSE("lm_order names a slot >= NL");
@@ -512,6 +510,16 @@ int vio_debug_marg_set(vio_batch *h, int seq, const vio_marg_stage_in *in) {
         if (!std::isfinite(t.lm_depth[slot])) MARG_STAGE_REFUSE("a depth is not finite");
         if (!all_finite(t.lm_obs + (size_t)slot * W1 * VIO_OBS_D, (size_t)W1 * VIO_OBS_D)) MARG_STAGE_REFUSE("an observation is not finite");
         if (!t.lm_dyn[slot] && no >= 2 && st < W - 2 && st == 0) F0++;
+        if (!t.lm_dyn[slot] && no >= 2 && st < W - 2) nres += no - 1;
+        if (solve && (in->lm_est_flag[slot] < 0 || in->lm_est_flag[slot] > 2)) MARG_STAGE_REFUSE("lm_est_flag outside 0 .. 2");
+    }
+    if (solve) {
+        // (landmarks in the problem <= n_lm <= NL by the checks above; the next test cannot fire at today's sizing either, NRES >= W NP + 2 NL: it is
+        // there for the day the sizing changes)
+        if (nres > (long long)C.NRES - 2 * NL) MARG_STAGE_REFUSE("more projection residuals than the NRES - 2 NL records of the residual list");
+        // (ps_setup asks for 3 + ceil(nres / (256 eval_rpt)) evaluation workgroups; the launch has ps_eval_blocks: a solve beyond them would never be accepted)
+        if (h->solve_mode == 1 && nres > (long long)(h->ps_eval_blocks - 3) * 256 * h->B.eval_rpt)
+            MARG_STAGE_REFUSE("more projection residuals than the handle's evaluation launch covers");
     }
     if (F0 > C.NRES / W) MARG_STAGE_REFUSE("more landmarks start in frame 0 than NRES / W residual records hold");
     for (int i = 1; i <= W; i++) if (!(t.Headers[i] > t.Headers[i - 1])) MARG_STAGE_REFUSE("Headers must increase");
@@ -533,8 +541,7 @@ int vio_debug_marg_set(vio_batch *h, int seq, const vio_marg_stage_in *in) {
         if (!all_finite(in->prior_H, (size_t)n * n) || !all_finite(in->prior_r, n) || !all_finite(in->prior_x0, (size_t)W * 7 + 17))
             MARG_STAGE_REFUSE("the prior is not finite");
     }
-    const bool imu = C.c.use_imu != 0;
-    if (imu) {
+    if (C.c.use_imu) {
         if (!in->imu_n || !in->imu_dt || !in->imu_acc || !in->imu_gyr || !in->imu_acc0 || !in->imu_gyr0 || !in->imu_ba || !in->imu_bg)
             MARG_STAGE_REFUSE("an IMU table is missing");
         for (int j = 1; j <= W; j++) {
@@ -547,6 +554,18 @@ int vio_debug_marg_set(vio_batch *h, int seq, const vio_marg_stage_in *in) {
                 MARG_STAGE_REFUSE("an IMU sample is not finite");
         }
     }
+    return VIO_OK;
+}
+#undef MARG_STAGE_REFUSE
+
+// A validated state (stage_validate) into the handle's arrays.  solve: the state in front of a solve (vio_debug_solve_set) instead of the one in front
+// of a marginalisation.
+static int stage_write(vio_batch *h, int seq, const vio_marg_stage_in *in, const std::vector<char> &live, bool solve) {
+    const DevCfg &C = h->hc;
+    Batch &B = h->B;
+    const int W = C.W, W1 = W + 1, NL = C.NL, n = C.NPRIOR;
+    const vio_publish_tables &t = in->t;
+    const bool imu = C.c.use_imu != 0;
     // ---- the window state
     std::vector<BeSeq> bev(1);
     BeSeq &be = bev[0];
@@ -560,7 +579,13 @@ int vio_debug_marg_set(vio_batch *h, int seq, const vio_marg_stage_in *in) {
     for (int k = 0; k < 9; k++) be.ric[k] = t.ric[k];
     for (int k = 0; k < 3; k++) { be.tic[k] = t.tic[k]; be.g[k] = in->g[k]; }
     be.td = in->td;
-    be.frame_count = W; be.do_marg = 1; be.rebooted = 0; be.processed = 0;
+    be.frame_count = W; be.do_marg = solve ? 0 : 1; be.rebooted = 0; be.processed = 0;
+    if (solve) {
+        be.do_solve = 1; be.solver_flag = 1; be.openExEstimation = 0; be.relo_info = 0; be.init_frame = 0; be.overflow = 0;
+        // what failureDetection at the end of the solve compares the new window with: as the previous frame left them
+        for (int k = 0; k < 3; k++) { be.last_P[k] = t.Ps[3 * W + k]; be.last_P0[k] = t.Ps[k]; }
+        for (int k = 0; k < 9; k++) { be.last_R[k] = t.Rs[9 * W + k]; be.last_R0[k] = t.Rs[k]; }
+    }
     be.marginalization_flag = in->marginalization_flag;
     be.has_prior = in->has_prior;
     for (int i = 0; i < VIO_MAXW + 3; i++) be.prior_present[i] = (in->has_prior && i < W + 3) ? in->prior_present[i] : 0;
@@ -622,7 +647,16 @@ int vio_debug_marg_set(vio_batch *h, int seq, const vio_marg_stage_in *in) {
     }
     return VIO_OK;
 }
-#undef MARG_STAGE_REFUSE
+
+int vio_debug_marg_set(vio_batch *h, int seq, const vio_marg_stage_in *in) {
+    VIO_ENTER(h, seq, true);
+    if (!in) return VIO_EINVAL;
+    // ---- validation: nothing is written before all of it has passed
+    if (h->hc.MX > 0 || h->hc.c.marg_exact) { g_err = "vio_debug_marg_set: the handle runs the literal marginalisation"; return VIO_EINVAL; }
+    std::vector<char> live;
+    VIO_TRY(stage_validate(h, in, "vio_debug_marg_set", false, live));
+    return stage_write(h, seq, in, live, false);
+}
 
 int vio_debug_marg_run(vio_batch *h) {
     VIO_ENTER(h, VIO_NO_SEQ, true);
@@ -653,6 +687,104 @@ int vio_debug_marg_get(vio_batch *h, int seq, vio_marg_stage_out *out) {
         if (out->margB) HIPCHK(hipMemcpy(out->margB, B.margB + s * mq, mq * sizeof(double), hipMemcpyDeviceToHost));
         if (out->margV) HIPCHK(hipMemcpy(out->margV, B.margV + s * n * n, n * n * sizeof(double), hipMemcpyDeviceToHost));
         if (out->b_r) HIPCHK(hipMemcpy(out->b_r, B.vec + s * VEC_SLOTS * C.LW, n * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return VIO_OK;
+}
+
+// ---- the solver on a staged state, launch by launch (include/vio_abi.h vio_debug_solve_set / _run / _get)
+int vio_debug_solve_set(vio_batch *h, int seq, const vio_marg_stage_in *in) {
+    VIO_ENTER(h, seq, true);
+    if (!in) return VIO_EINVAL;
+    std::vector<char> live;
+    VIO_TRY(stage_validate(h, in, "vio_debug_solve_set", true, live));
+    VIO_TRY(stage_write(h, seq, in, live, true));
+    h->solve_staged.resize(h->S, 0);
+    h->solve_staged[seq] = 1;
+    return VIO_OK;
+}
+
+int vio_debug_solve_run(vio_batch *h, int slots, int stop_phase, double radius0) {
+    VIO_ENTER(h, VIO_NO_SEQ, true);
+    if (slots < 0) {
+        if (stop_phase != VIO_SOLVE_STOP_NONE || radius0 != 0) { g_err = "vio_debug_solve_run: the whole solve takes no stop phase and no radius"; return VIO_EINVAL; }
+        VIO_TRY(vio_internal::launch_solve_all(h, nullptr));
+        return sync_all(h);
+    }
+    if (h->solve_mode != 1) { g_err = "vio_debug_solve_run: a handle without the phased solver runs the whole solve only (slots < 0)"; return VIO_EINVAL; }
+    if (stop_phase < VIO_SOLVE_STOP_NONE || stop_phase > VIO_SOLVE_STOP_LS || !(radius0 >= 0) || !std::isfinite(radius0) ||
+        slots + (stop_phase != VIO_SOLVE_STOP_NONE ? 1 : 0) > h->hc.c.max_iterations + h->extra_slots) {
+        g_err = "vio_debug_solve_run: stop_phase, radius0 or the number of slots out of range";
+        return VIO_EINVAL;
+    }
+    const vio_internal::SolveCut cut = {slots, stop_phase, radius0};   // (alive until sync_all has returned: its radius0 is copied asynchronously)
+    VIO_TRY(vio_internal::launch_solve_all(h, &cut));
+    return sync_all(h);
+}
+
+int vio_debug_solve_get(vio_batch *h, int seq, vio_solve_stage_out *out) {
+    VIO_ENTER(h, seq, true);
+    if (!out) return VIO_EINVAL;
+    if (h->solve_mode != 1) { g_err = "vio_debug_solve_get: the handle does not run the phased solver"; return VIO_EINVAL; }
+    const DevCfg &C = h->hc;
+    const Batch &B = h->B;
+    const size_t W1 = (size_t)C.W + 1, P = C.P, LW = C.LW, NL = C.NL, NLs = NL + 8, s = (size_t)seq, S = (size_t)B.S;
+    std::vector<SolveSt> stv(1);
+    const SolveSt &st = stv[0];
+    HIPCHK(hipMemcpy(stv.data(), B.sst + seq, sizeof(SolveSt), hipMemcpyDeviceToHost));
+    if (out->scal_i) {
+        const int v[11] = {st.stage, st.iter, st.iters_done, st.F, st.Fa, st.nres, st.ex_active, st.td_active, st.vext, st.constrained, st.fused};
+        for (int k = 0; k < 11; k++) out->scal_i[k] = v[k];
+    }
+    if (out->scal_d) {
+        // ccost: ps_accept keeps the candidate's cost in a register (SolveSt::ccost is never written) and stores it as `cost` only when it accepts;
+        // what it summed is still there: the partial costs of the last evaluation, one per workgroup or chunk, added here in index order
+        const int nparts = std::min((int)PS_MAX_EVAL_BLOCKS, st.fused ? 2 + st.nblk : st.n_eval_blocks);
+        double ccost = 0;
+        for (int k = 0; k < nparts; k++) ccost += st.part[k];
+        const double v[7] = {st.cost, ccost, st.radius, st.mu, st.alpha, st.dogleg_norm, st.model_change};
+        for (int k = 0; k < 7; k++) out->scal_d[k] = v[k];
+    }
+    auto params = [&](const Params &X, double *o) {
+        if (!o) return;
+        memcpy(o, X.pose, 7 * W1 * sizeof(double)); memcpy(o + 7 * W1, X.sb, 9 * W1 * sizeof(double));
+        memcpy(o + 16 * W1, X.ex, 7 * sizeof(double)); o[16 * W1 + 7] = X.td;
+    };
+    params(st.X, out->X); params(st.Xc, out->Xc);
+    if (out->feat) HIPCHK(hipMemcpy(out->feat, B.para_feat + s * NL, NL * sizeof(double), hipMemcpyDeviceToHost));
+    if (out->cfeat) HIPCHK(hipMemcpy(out->cfeat, B.cand_feat + s * NL, NL * sizeof(double), hipMemcpyDeviceToHost));
+    // (the variable-landmark slots: the last NL entries of the sequence's pair_list, solve_prologue)
+    if (out->var_slots) HIPCHK(hipMemcpy(out->var_slots, B.pair_list + s * C.NRES + C.NRES - NL, NL * sizeof(int), hipMemcpyDeviceToHost));
+    if (out->H) {
+        std::vector<double> Hd(LW * LW);
+        HIPCHK(hipMemcpy(Hd.data(), B.H + s * LW * LW, LW * LW * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t a = 0; a < P; a++) memcpy(out->H + a * P, &Hd[a * LW], P * sizeof(double));
+    }
+    const double *vec = B.vec + s * VEC_SLOTS * LW, *lvec = B.lvec + s * NLs * 8;
+    auto pvec = [&](double *o, int slot) { return o ? hipMemcpy(o, vec + slot * LW, P * sizeof(double), hipMemcpyDeviceToHost) : hipSuccess; };
+    auto lv = [&](double *o, const double *src) { return o ? hipMemcpy(o, src, NL * sizeof(double), hipMemcpyDeviceToHost) : hipSuccess; };
+    // (be_phased.h ps_serial_body: g, sp, dgp, gradp, gnp, stp = slots 0 .. 5 of c.vec; sl, dgl, gradl, gnl, stl = 0 .. 4 of c.lvec)
+    HIPCHK(pvec(out->g, 0)); HIPCHK(pvec(out->sp, 1)); HIPCHK(pvec(out->dgp, 2)); HIPCHK(pvec(out->gnp, 4)); HIPCHK(pvec(out->stp, 5));
+    HIPCHK(lv(out->sl, lvec)); HIPCHK(lv(out->dgl, lvec + NLs)); HIPCHK(lv(out->gnl, lvec + 3 * NLs)); HIPCHK(lv(out->stl, lvec + 4 * NLs));
+    // the landmark rows of the current point: the half st.rowbuf of the double-buffered arrays (be_phased.h ps_sel_rows)
+    const size_t rb = st.rowbuf ? 1 : 0;
+    HIPCHK(lv(out->Hll, B.Hll + s * NLs + rb * S * NLs)); HIPCHK(lv(out->gl, B.gl + s * NLs + rb * S * NLs));
+    if (out->Hpl) {
+        std::vector<double> Wd(NL * LW);
+        HIPCHK(hipMemcpy(Wd.data(), B.Hpl + s * NLs * LW + rb * S * NLs * LW, NL * LW * sizeof(double), hipMemcpyDeviceToHost));
+        const size_t n0 = 6 * W1, e0 = 15 * W1, ne = st.vext ? 7 : 0;   // the columns the kernels write (ps_asm_a)
+        for (size_t k = 0; k < NL; k++)
+            for (size_t a = 0; a < P; a++) out->Hpl[k * P + a] = (a < n0 || (a >= e0 && a < e0 + ne)) ? Wd[k * LW + a] : 0.0;
+    }
+    if (out->Sc) {
+        std::vector<double> Sd(LW * LW);
+        HIPCHK(hipMemcpy(Sd.data(), B.Sc + s * LW * LW, LW * LW * sizeof(double), hipMemcpyDeviceToHost));
+        const size_t nb = LW >> 4;
+        for (size_t q = 0; q < LW * LW; q++) out->Sc[q] = 0.0;
+        for (size_t ti = 0; ti < nb; ti++)
+            for (size_t tj = 0; tj <= ti; tj++)
+                for (size_t r = 0; r < 16; r++)
+                    for (size_t c = 0; c < 16; c++)   // be_linalg.h tl_idx
+                        out->Sc[(16 * ti + r) * LW + 16 * tj + c] = Sd[((ti * (ti + 1) / 2 + tj) << 8) + (r << 4) + (c ^ r)];
     }
     return VIO_OK;
 }

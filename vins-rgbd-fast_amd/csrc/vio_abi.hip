@@ -475,6 +475,75 @@ static int launch_marg(vio_batch *h, vio_batch::Group &g, const Batch &Bg, int S
     return VIO_OK;
 }
 
+// the solve of one frame on the group's back-end stream: the phased solver's launches from ps_setup_kernel to ps_final_kernel, or the persistent
+// kernel.  Bg.fuse_only is settled here (the caller's later launches carry it, as they always have); split: ps_setup runs on the front-end
+// stream and the back-end stream joins at the first slot (launch_backend)
+// cut (vio_handle.h SolveCut): the stage harness's cut through these launches; nullptr = the whole solve, as every other caller wants it
+static int launch_solve(vio_batch *h, vio_batch::Group &g, Batch &Bg, int S, bool split, const vio_internal::SolveCut *cut = nullptr) {
+    const DevCfg &C = h->hc;
+    hipStream_t st = g.stream;
+    hipStream_t st_in = split ? g.fe_stream : st;   // ps_setup
+    const int be_threads = h->be_threads;
+    if (h->solve_mode == 1) {
+        // phased solver: every data-parallel phase of the trust-region loop covers all sequences with many workgroups; max_iterations
+        // + 1 slots carry the iterations, two more absorb Cholesky retries (a converged sequence falls through the remaining launches)
+        // The two-kernel path (ps_eval + ps_asm_a) is launched beside the fused kernel only where a solve of this handle can need it: the
+        // extrinsic / td blocks may open (42-double records), the handle has ever been handed a relocalisation request (vio_set_relo_frame; the request waits on the device for its sequence's next solve), or the
+        // residual list can plausibly outgrow the fused kernel's PS_FUSE_MAXBLK chunks (a solve that does so anyway on a fused-only handle is skipped and
+        // flagged, overflow bit 256).  Decided on the host from the configuration: deterministic, no device feedback.
+        // (VIO_FUSE, default 0: measured on the canonical workload the fused kernel moves 28 % less data -- 0.80 against 1.11 GB per 64-sequence solve --
+        // and wins where the device is throughput-bound (S = 256: +2.5 %, S = 512: +2 %), but at 64 sequences per stream group, where the chain of
+        // dependent launches bounds the step, the two-kernel path is 2 % faster: its smaller workgroups share the CUs better with the other group's
+        // kernels.  One path per handle whatever the batch size, so that a sequence's result never depends on the batch it runs in.)
+        const bool fuse_only = Bg.fuse > 0 && !C.c.estimate_extrinsic && !C.c.estimate_td && h->relo_frames <= 0 &&
+                               (size_t)(C.W + 1) * C.c.max_cnt * 12 / 10 <= (size_t)PS_FUSE_MAXBLK * (PS_FUSE_CAP - C.W);
+        Bg.fuse_only = fuse_only ? 1 : 0;
+        ps_setup_kernel<<<S, 512, 0, st_in>>>(Bg);
+        if (split) { HIPCHK(hipEventRecord(g.ev_setup, st_in)); HIPCHK(hipStreamWaitEvent(st, g.ev_setup, 0)); }
+        const int all_slots = C.c.max_iterations + h->extra_slots;
+        if (cut && cut->radius0 > 0)
+            for (int q = 0; q < S; q++)
+                if ((size_t)(Bg.s0 + q) < h->solve_staged.size() && h->solve_staged[Bg.s0 + q]) HIPCHK(hipMemcpyAsync(&h->B.sst[Bg.s0 + q].radius, &cut->radius0 /* (the caller keeps it alive until it has waited) */, sizeof(double), hipMemcpyHostToDevice, st));
+        // (cut: `slots` whole ones and the first `stop` phases of the next; every launch keeps the place and the arguments it has in the whole solve)
+        const int slots = cut ? cut->slots + (cut->stop > 0 ? 1 : 0) : all_slots;
+        // XCD-aware block map (ps_blk): every block of a sequence on the XCD its one-block kernels run on
+        const bool xm = h->xcd_map && S >= 8;
+        const int XN = 8;   // XCDs the map assumes (measured with the back-end streams masked to six XCDs: 8 -> +2 %, 6 -> +0.3 %, 3 / 12 -> -1 %: the block -> XCD rotation ignores the mask)
+        const int nb_e = h->ps_eval_blocks, nb_a = h->ps_asm_a_blocks, nb_bs = h->ps_asm_b_blocks + h->ps_schur_tiles + 1 /* ps_gn_rhs_body */, S8 = XN * ((S + XN - 1) / XN);
+        Batch Be = Bg, Ba = Bg, Bb = Bg;
+        Be.ns = Ba.ns = Bb.ns = S;
+        Be.xcd_n = Ba.xcd_n = Bb.xcd_n = XN;
+        Be.xcd_nb = xm ? nb_e : 0; Ba.xcd_nb = xm ? nb_a : 0; Bb.xcd_nb = xm ? nb_bs : 0;
+        const dim3 g_e = xm ? dim3(S8 * nb_e) : dim3(nb_e, S), g_a = xm ? dim3(S8 * nb_a) : dim3(nb_a, S), g_b = xm ? dim3(S8 * nb_bs) : dim3(nb_bs, S);
+        Batch Bf = Bg;
+        Bf.ns = S; Bf.xcd_n = XN; Bf.xcd_nb = xm ? h->ps_evalf_blocks : 0;
+        const dim3 g_f = xm ? dim3(S8 * h->ps_evalf_blocks) : dim3(h->ps_evalf_blocks, S);
+        for (int k = 0; k < slots; k++) {
+            const int stop = cut && k == cut->slots ? cut->stop : VIO_SOLVE_STOP_NONE;   // the slot that is cut short
+            // fused evaluate + assemble for the solves that qualify (st.fused); ps_eval / ps_asm_a serve the others and idle for these
+            if (Bg.fuse) ps_evalf_kernel<<<g_f, 256, h->lds_ps_evalf, st>>>(Bf);
+            if (!fuse_only) {
+                // (idle launches are not free here: their workgroups ask for 40 KB of LDS each and queue behind the other stream group's
+                // fused workgroups, which fill the CUs' LDS -- 15 us per idle launch, measured)
+                ps_eval_kernel<<<g_e, 256, h->lds_ps_eval, st>>>(Be);
+                ps_asm_a_kernel<<<g_a, 512, 0, st>>>(Ba);
+            }
+            if (stop == VIO_SOLVE_STOP_ASM_A) break;
+            ps_asm_b_schur_kernel<<<g_b, 256, (size_t)(C.NL + 16 + (6 * (C.W + 1) + 7 <= 128 ? 8 * 128 : 8 * 192) /* eight compact partial rows of ps_gn_rhs_body (>= the 4 x 256 of a Schur tile) */) * sizeof(double), st>>>(Bb, h->ps_asm_b_blocks);   // per-row factors + the partial tiles of wavefronts 1 .. 3 + the tile of H
+            if (stop == VIO_SOLVE_STOP_SCHUR) break;
+            if (h->serial_big) ps_serial_big_kernel<<<S, 512, h->lds_serial, st>>>(Bg);
+            else ps_serial_kernel_512<<<S, 512, h->lds_serial, st>>>(Bg);
+            // Ceres' projected line search of bounds-constrained solves (one workgroup per sequence, idle otherwise); the candidate of the
+            // last slot is never evaluated, so no search follows it
+            if (stop == VIO_SOLVE_STOP_SERIAL) break;
+            if (h->line_search && k + 1 < all_slots) ps_ls_kernel<<<S, 256, h->lds_ps_ls, st>>>(Bg);
+        }
+        if (!cut) ps_final_kernel<<<S, 256, 0, st>>>(Bg);
+    } else if (be_threads <= 512) be_solve_kernel_512<<<S, be_threads, h->lds_solve, st>>>(Bg);
+    else be_solve_kernel<<<S, be_threads, h->lds_solve, st>>>(Bg);
+    return VIO_OK;
+}
+
 // one_seq >= 0: only that sequence (vio_process_obs), otherwise every sequence of the group
 // split (vio_feed only, split_feed above): be_ingest and ps_setup of this frame run on the group's front-end stream, behind the previous frame's window
 // slide (ev_slide) and beside its be_marg_alg; the back-end stream joins at the first solver slot (ev_setup) and cuts this frame's marginalisation
@@ -509,55 +578,7 @@ int launch_backend(vio_batch *h, vio_batch::Group &g, const uint16_t *d_depth, c
         for (int s = 0; s < h->S; s++) any = any || !h->dyn[s].nonlinear;
         h->dyn_active = any;
     }
-    const int be_threads = h->be_threads;
-    if (h->solve_mode == 1) {
-        // phased solver: every data-parallel phase of the trust-region loop covers all sequences with many workgroups; max_iterations
-        // + 1 slots carry the iterations, two more absorb Cholesky retries (a converged sequence falls through the remaining launches)
-        // The two-kernel path (ps_eval + ps_asm_a) is launched beside the fused kernel only where a solve of this handle can need it: the
-        // extrinsic / td blocks may open (42-double records), the handle has ever been handed a relocalisation request (vio_set_relo_frame; the request waits on the device for its sequence's next solve), or the
-        // residual list can plausibly outgrow the fused kernel's PS_FUSE_MAXBLK chunks (a solve that does so anyway on a fused-only handle is skipped and
-        // flagged, overflow bit 256).  Decided on the host from the configuration: deterministic, no device feedback.
-        // (VIO_FUSE, default 0: measured on the canonical workload the fused kernel moves 28 % less data -- 0.80 against 1.11 GB per 64-sequence solve --
-        // and wins where the device is throughput-bound (S = 256: +2.5 %, S = 512: +2 %), but at 64 sequences per stream group, where the chain of
-        // dependent launches bounds the step, the two-kernel path is 2 % faster: its smaller workgroups share the CUs better with the other group's
-        // kernels.  One path per handle whatever the batch size, so that a sequence's result never depends on the batch it runs in.)
-        const bool fuse_only = Bg.fuse > 0 && !C.c.estimate_extrinsic && !C.c.estimate_td && h->relo_frames <= 0 &&
-                               (size_t)(C.W + 1) * C.c.max_cnt * 12 / 10 <= (size_t)PS_FUSE_MAXBLK * (PS_FUSE_CAP - C.W);
-        Bg.fuse_only = fuse_only ? 1 : 0;
-        ps_setup_kernel<<<S, 512, 0, st_in>>>(Bg);
-        if (split) { HIPCHK(hipEventRecord(g.ev_setup, st_in)); HIPCHK(hipStreamWaitEvent(st, g.ev_setup, 0)); }
-        const int slots = C.c.max_iterations + h->extra_slots;
-        // XCD-aware block map (ps_blk): every block of a sequence on the XCD its one-block kernels run on
-        const bool xm = h->xcd_map && S >= 8;
-        const int XN = 8;   // XCDs the map assumes (measured with the back-end streams masked to six XCDs: 8 -> +2 %, 6 -> +0.3 %, 3 / 12 -> -1 %: the block -> XCD rotation ignores the mask)
-        const int nb_e = h->ps_eval_blocks, nb_a = h->ps_asm_a_blocks, nb_bs = h->ps_asm_b_blocks + h->ps_schur_tiles + 1 /* ps_gn_rhs_body */, S8 = XN * ((S + XN - 1) / XN);
-        Batch Be = Bg, Ba = Bg, Bb = Bg;
-        Be.ns = Ba.ns = Bb.ns = S;
-        Be.xcd_n = Ba.xcd_n = Bb.xcd_n = XN;
-        Be.xcd_nb = xm ? nb_e : 0; Ba.xcd_nb = xm ? nb_a : 0; Bb.xcd_nb = xm ? nb_bs : 0;
-        const dim3 g_e = xm ? dim3(S8 * nb_e) : dim3(nb_e, S), g_a = xm ? dim3(S8 * nb_a) : dim3(nb_a, S), g_b = xm ? dim3(S8 * nb_bs) : dim3(nb_bs, S);
-        Batch Bf = Bg;
-        Bf.ns = S; Bf.xcd_n = XN; Bf.xcd_nb = xm ? h->ps_evalf_blocks : 0;
-        const dim3 g_f = xm ? dim3(S8 * h->ps_evalf_blocks) : dim3(h->ps_evalf_blocks, S);
-        for (int k = 0; k < slots; k++) {
-            // fused evaluate + assemble for the solves that qualify (st.fused); ps_eval / ps_asm_a serve the others and idle for these
-            if (Bg.fuse) ps_evalf_kernel<<<g_f, 256, h->lds_ps_evalf, st>>>(Bf);
-            if (!fuse_only) {
-                // (idle launches are not free here: their workgroups ask for 40 KB of LDS each and queue behind the other stream group's
-                // fused workgroups, which fill the CUs' LDS -- 15 us per idle launch, measured)
-                ps_eval_kernel<<<g_e, 256, h->lds_ps_eval, st>>>(Be);
-                ps_asm_a_kernel<<<g_a, 512, 0, st>>>(Ba);
-            }
-            ps_asm_b_schur_kernel<<<g_b, 256, (size_t)(C.NL + 16 + (6 * (C.W + 1) + 7 <= 128 ? 8 * 128 : 8 * 192) /* eight compact partial rows of ps_gn_rhs_body (>= the 4 x 256 of a Schur tile) */) * sizeof(double), st>>>(Bb, h->ps_asm_b_blocks);   // per-row factors + the partial tiles of wavefronts 1 .. 3 + the tile of H
-            if (h->serial_big) ps_serial_big_kernel<<<S, 512, h->lds_serial, st>>>(Bg);
-            else ps_serial_kernel_512<<<S, 512, h->lds_serial, st>>>(Bg);
-            // Ceres' projected line search of bounds-constrained solves (one workgroup per sequence, idle otherwise); the candidate of the
-            // last slot is never evaluated, so no search follows it
-            if (h->line_search && k + 1 < slots) ps_ls_kernel<<<S, 256, h->lds_ps_ls, st>>>(Bg);
-        }
-        ps_final_kernel<<<S, 256, 0, st>>>(Bg);
-    } else if (be_threads <= 512) be_solve_kernel_512<<<S, be_threads, h->lds_solve, st>>>(Bg);
-    else be_solve_kernel<<<S, be_threads, h->lds_solve, st>>>(Bg);
+    VIO_TRY(launch_solve(h, g, Bg, S, split));
     if (prof) PEV(h, 10);
     (void)hipEventRecord(g.ev_solve, st);  // the next frame's front-end may start here (it only needs latest_Bg / td / imu_head, and a
     g.have_solve_ev = true;                // reboot - which rewrites them - is decided at the end of be_solve)
@@ -584,6 +605,17 @@ int launch_marg_all(vio_batch *h) {
         Batch Bg = h->B;
         Bg.s0 = g.s0;
         VIO_TRY(launch_marg(h, g, Bg, g.n, split_feed(h)));
+    }
+    HIPCHK(hipGetLastError());
+    return VIO_OK;
+}
+// the solver launches of a vio_feed call on every group of the handle (vio_debug_solve_run): whole -- cut == nullptr: ps_final included, or the
+// persistent kernel -- or cut short; *cut must outlive the launches (its radius0 is the source of an asynchronous copy)
+int launch_solve_all(vio_batch *h, const SolveCut *cut) {
+    for (auto &g : h->groups) {
+        Batch Bg = h->B;
+        Bg.s0 = g.s0;
+        VIO_TRY(launch_solve(h, g, Bg, g.n, false, cut));
     }
     HIPCHK(hipGetLastError());
     return VIO_OK;

@@ -160,6 +160,7 @@ struct vio_batch {
     int *d_mlist = nullptr;
     // VIO_SOLVE_MODE: 0 = persistent kernel (one workgroup per sequence for the whole solve), 1 = phased solver (be_phased.h, default)
     int solve_mode = 1;
+    std::vector<char> solve_staged;   // [S] vio_debug_solve_set has staged the sequence: the only ones whose SolveSt::radius vio_debug_solve_run may write
     bool serial_big = false;          // the window's Schur complement does not fit LDS: ps_serial_big_kernel (HBM-resident tiles, streaming Cholesky)
     size_t lds_ps_eval = 0;
     int ps_eval_blocks = 0, ps_asm_a_blocks = 0, ps_schur_tiles = 0;
@@ -471,6 +472,11 @@ int init_state(vio_batch *h, int s_lo, int s_hi, int what = VIO_RESET_ESTIMATOR 
 int flush_imu_backend(vio_batch *h);        // vio_abi.hip
 int refresh_dynamic_state(vio_batch *h);    // vio_abi.hip
 int launch_marg_all(vio_batch *h);          // vio_abi.hip: what vio_feed launches behind the solve, on every group
+// A cut through the solver's launches, for the stage harness only: ps_setup, `slots` whole slots, then the kernels of one more slot up to and
+// including phase `stop` (VIO_SOLVE_STOP_*), and no ps_final.  radius0 > 0: SolveSt::radius of every staged sequence is overwritten by a copy between
+// ps_setup and the first slot.
+struct SolveCut { int slots, stop; double radius0; };
+int launch_solve_all(vio_batch *h, const SolveCut *cut);   // vio_abi.hip: the solver launches of vio_feed on every group (nullptr: the whole solve)
 // "" when the calibration / camera is usable, else the message naming the offending field (abi_query.hip)
 std::string calibration_check(const vio_calibration &k);
 std::string camera_check(const vio_camera &m, int width, int height);
