@@ -593,7 +593,7 @@ int vio_stage_host_sfm_window(int window_size, int nf, const int32_t *start, con
 int vio_stage_imu_block(const vio_config *cfg, int n, const double *dt, const double *acc, const double *gyr, const double *acc0,
                         const double *gyr0, const double *ba, const double *bg, const double *pose_i, const double *sb_i,
                         const double *pose_j, const double *sb_j, double *G961);
-/* Harnesses of the factor code alone (be_factors.h and the propagation routines of be_kernels.hip), for tests against the definitions.
+/* Harnesses of the factor code alone (be_factors.h and the propagation routines of be_preint.h), for tests against the definitions.
  * vio_stage_preint: IntegrationBase(acc0, gyr0, ba, bg) followed by n x propagate (integration_base.h:56-162) through mode 0 = preint_propagate step
  * by step, 1 = preint_propagate_many(append = false), 2 = preint_propagate_many(append = true), the merge of MARGIN_SECOND_NEW, which also files
  * the samples (push_back).  dt[n], acc[n][3], gyr[n][3]; the noise densities are cfg's.  out686 = delta_p(3) delta_q(wxyz) delta_v(3) sum_dt

@@ -1,4 +1,4 @@
-"""The factor kernels (csrc/be_factors.h, the propagation routines of csrc/be_kernels.hip, imu_block_mfma) against their definitions in extended
+"""The factor kernels (csrc/be_factors.h, the propagation routines of csrc/be_preint.h, imu_block_mfma) against their definitions in extended
 precision (tests/factor_ref.py) on the named edge cases of tests/factor_cases.py, through stage entries that run each routine alone.
 
 Bounds, none of them taken from the device's output:

@@ -4,8 +4,10 @@
 //                   inliers), decomposeE and the four cv::triangulatePoints votes.
 //   ex_average      CalibrationExRotation (:12-68): Huber-weighted rotation averaging over the stored (Rc, Rimu, Rc_g) pairs.
 //   ex_calibrate    the per-frame phase of be_ingest<true> (estimator.cpp:208-226).
-// Included by be_kernels.hip after be_linalg.h (block_sum, block_scan_flags, jacobi_small, Ctx / obs_ptr).
+// Included by be_ingest.hip and be_stage.hip; uses block_sum, block_scan_flags, jacobi_small (be_linalg.h) and Ctx / obs_ptr (be_ctx.h).
 #pragma once
+#include "be_ctx.h"
+#include "be_linalg.h"
 #include "fe_ransac.h"
 
 namespace {

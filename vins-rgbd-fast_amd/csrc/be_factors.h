@@ -1,5 +1,5 @@
 // Per-thread factor math of the sliding-window back-end (FP64). __host__ __device__ so the same functions can be
-// exercised by host self tests; the HIP kernels in be_kernels.hip are the only product callers.
+// exercised by host self tests; the HIP kernels in be_kernels.hip and be_ingest.hip are the only product callers.
 // Reference: vins_estimator/src/factor/integration_base.h:56-195, imu_factor.h:20-205,
 //            projection_factor.cpp:22-130, projection_td_factor.cpp:34-150, pose_local_parameterization.cpp:3-28,
 //            marginalization_factor.cpp:39-72 (loss correction), :374-393 (pose delta).
@@ -83,7 +83,7 @@ DM_HD PreintStep preint_midpoint(const PreInt &p, double dt, v3 acc_1, v3 gyr_1,
     return o;
 }
 
-// The two halves of preint_midpoint for the pipelined propagation (be_kernels.hip preint_propagate_many; same expressions, hence the same
+// The two halves of preint_midpoint for the pipelined propagation (be_preint.h preint_propagate_many; same expressions, hence the same
 // bits): the state recursion (serial, a few dozen operations per sample) and the F / V matrices of a step, which depend only on the
 // state BEFORE it.  preint_step_FV writes the non-zero blocks; zero = false: the caller hands it cleared matrices.
 struct PreintPre { quat dq; v3 acc0, gyr0; };   // what a step's F / V need besides (dt, acc_1, gyr_1) and the linearisation biases

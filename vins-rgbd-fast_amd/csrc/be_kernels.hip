@@ -8,1060 +8,14 @@
 //              frame-pair blocked J^T J, landmark Schur complement, dense Cholesky, step control as SURVEY.md App. B.5
 //   be_marg    marginalisation (estimator.cpp:1370-1575, marginalization_factor.cpp:181-315) in the canonical layout
 //   be_finish  movingConsistencyCheck, failureDetection, slideWindow, removeFailures, odometry row
-#include <hip/hip_runtime.h>
-#include "kernels.h"
-#include "be_factors.h"
-
-using namespace dm;
-
-// phase timers (debug): thread 0 of sequence 0 accumulates 100 MHz wall-clock ticks into B.timings[k]
-#if VIO_TIMERS
-#define PH_INIT long long ph_t0 = (s == 0 && threadIdx.x == 0) ? VIO_CLOCK() : 0
-#define PH(k) do { if (s == 0 && threadIdx.x == 0) { long long n_ = VIO_CLOCK(); B.timings[k] += (float)(n_ - ph_t0); ph_t0 = n_; } } while (0)
-#else
-#define PH_INIT long long ph_t0 = 0   // (never read: the functions that tick take it as a parameter in both builds)
-#define PH(k) do {} while (0)
-#endif
-
-namespace {
-
-struct Ctx {
-    float *timings;
-    const DevCfg *C;
-    int s, W, P, LW, NL, NLs, NPR;
-    BeSeq *be;
-    FeSeq *fe;
-    const vio_calibration *K;   // the sequence's calibration (Batch::cal)
-    PreInt *pre;
-    int *lm_id, *lm_start, *lm_nobs, *lm_est, *lm_solve, *lm_dyn, *lm_order, *lm_free, *lm_tmp, *lm_pidx, *lm_aidx, *lm_relo;
-    double *lm_depth, *lm_obs, *feat, *cfeat, *relo_xy, *relo_mp;
-    double *H, *Sc, *Hpl, *vec, *Hll, *gl, *lvec, *res;
-    int *res_lm, *res_k, *pair_start, *pair_list;
-    double *pairblk, *imu_raw;
-    double *prior_J, *prior_r, *prior_x0, *prior_H, *prior_rf;
-    double *margA, *margB, *margV, *margW, *margE;
-    int nres_cap;
-};
-
-__device__ Ctx make_ctx(const Batch &B, int s) {
-    Ctx c;
-    // (round 6: the dimensions come from the kernel arguments -- as fields of *B.cfg they were one dependent global round trip at the top of every
-    // workgroup of every kernel before the first useful address could be formed)
-    struct { int W, P, LW, NL, NP, NRES, NPRIOR, MX; } C = {B.gW, B.gP, B.gLW, B.gNL, B.gNP, B.gNRES, B.gNPRIOR, B.gMX};
-    c.timings = B.timings;
-    c.C = B.cfg; c.s = s; c.W = C.W; c.P = C.P; c.LW = C.LW; c.NL = C.NL; c.NLs = C.NL + 8; c.NPR = C.NPRIOR;
-    c.be = B.be + s; c.fe = B.fe + s; c.K = B.cal + s;
-    c.pre = B.pre + (size_t)s * (C.W + 2);
-    size_t o = (size_t)s * C.NL;
-    c.lm_id = B.lm_id + o; c.lm_start = B.lm_start + o; c.lm_nobs = B.lm_nobs + o; c.lm_est = B.lm_est_flag + o;
-    c.lm_solve = B.lm_solve_flag + o; c.lm_dyn = B.lm_dyn + o; c.lm_order = B.lm_order + o; c.lm_free = B.lm_free + o;
-    c.lm_tmp = B.lm_tmp + o; c.lm_pidx = B.lm_pidx + o; c.lm_aidx = B.lm_aidx + o; c.lm_relo = B.lm_relo + o;
-    c.relo_xy = B.relo_xy + o * 2; c.relo_mp = B.relo_mp + (size_t)s * C.NP * 3;
-    c.lm_depth = B.lm_depth + o; c.feat = B.para_feat + o; c.cfeat = B.cand_feat + o;
-    c.lm_obs = B.lm_obs + o * (C.W + 1) * VIO_OBS_D;
-    c.H = B.H + (size_t)s * C.LW * C.LW; c.Sc = B.Sc + (size_t)s * C.LW * C.LW; c.Hpl = B.Hpl + (size_t)s * (C.NL + 8) * C.LW;
-    c.vec = B.vec + (size_t)s * VEC_SLOTS * C.LW;
-    c.Hll = B.Hll + (size_t)s * (C.NL + 8); c.gl = B.gl + (size_t)s * (C.NL + 8); c.lvec = B.lvec + (size_t)s * (C.NL + 8) * 8;
-    c.nres_cap = C.NRES;
-    c.res = B.res + (size_t)s * c.nres_cap * 42;
-    c.res_lm = B.res_lm + (size_t)s * c.nres_cap; c.res_k = B.res_k + (size_t)s * c.nres_cap;
-    int np = (C.W + 1) * (C.W + 1);
-    c.pair_start = B.pair_start + (size_t)s * (np + 1); c.pair_list = B.pair_list + (size_t)s * c.nres_cap;
-    c.pairblk = B.pairblk + (size_t)s * np * 210;
-    c.imu_raw = B.imu_raw + (size_t)s * C.W * 15 * 31;
-    int n = C.NPRIOR;
-    c.prior_J = B.prior_J + (size_t)s * n * n; c.prior_r = B.prior_r + (size_t)s * n;
-    c.prior_x0 = B.prior_x0 + (size_t)s * (C.W * 7 + 17); c.prior_H = B.prior_H + (size_t)s * n * n;
-    c.prior_rf = B.prior_rf + (size_t)s * n;
-    int mq = 15 + n;
-    c.margA = B.margA + (size_t)s * mq * mq; c.margB = B.margB + (size_t)s * mq;
-    c.margV = B.margV + (size_t)s * n * n; c.margW = B.margW + (size_t)s * (n + 16) * (n + 16);
-    c.margE = C.MX > 0 ? B.margE + (size_t)s * ((size_t)3 * C.MX * C.MX + (size_t)n * C.MX) : nullptr;
-    return c;
-}
-
-__device__ __forceinline__ double *obs_ptr(const Ctx &c, int slot, int frame) {
-    int W1 = c.W + 1;
-    int ph = (frame + c.be->ring_base) % W1;
-    return c.lm_obs + ((size_t)slot * W1 + ph) * VIO_OBS_D;
-}
-__device__ __forceinline__ bool in_problem(const Ctx &c, int slot) {
-    return !c.lm_dyn[slot] && c.lm_nobs[slot] >= 2 && c.lm_start[slot] < c.W - 2;
-}
-
-}  // namespace
-#include "be_linalg.h"
-#include "be_excalib.h"
-namespace {
-
-
-// ------------------------------------------------------------------ IntegrationBase::propagate, block-cooperative
-// LDS workspace: sJ sP sFJ sFP (225 each) sF (225) sV (270)
-struct PreWork { double J[225], Pm[225], FJ[225], FP[225], F[225], V[270]; };
-// PI_CH (kernels.h): samples per chunk of the pipelined propagation (F / V of a chunk live in LDS: 8 x 495 doubles)
-__device__ __forceinline__ void preint_load(const PreInt &p, PreWork &w) {
-    for (int i = threadIdx.x; i < 225; i += blockDim.x) { w.J[i] = p.jac[i]; w.Pm[i] = p.cov[i]; }
-    __syncthreads();
-}
-// Also refreshes the whitening matrix of the IMU factor: M = chol(cov)^-1 (lower triangular), M^T M = cov^-1.
-// The reference uses LLT(cov^-1).L^T (imu_factor.h:66-69); both satisfy M^T M = cov^-1, so J^T J, J^T r and |r|^2 - the only
-// quantities the solver and the marginalisation consume - are identical up to round-off (DESIGN.md "equivalent whitening").
-__device__ __forceinline__ void preint_store(PreInt &p, PreWork &w) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    for (int i = t; i < 225; i += blockDim.x) { p.jac[i] = w.J[i]; p.cov[i] = w.Pm[i]; }
-    if (t < 225) { int i = t / 15, j = t - i * 15; w.FJ[t] = 0.5 * (w.Pm[i * 15 + j] + w.Pm[j * 15 + i]); }
-    __syncthreads();
-    for (int j = 0; j < 15; j++) {
-        if (t == 0) { double d = w.FJ[j * 15 + j]; w.FJ[j * 15 + j] = (d > 0.0 && isfinite(d)) ? sqrt(d) : 0.0; }
-        __syncthreads();
-        double l = w.FJ[j * 15 + j];
-        if (t > j && t < 15) w.FJ[t * 15 + j] = l > 0.0 ? w.FJ[t * 15 + j] / l : 0.0;
-        __syncthreads();
-        if (t < 225) { int i = t / 15, k = t - i * 15; if (k > j && i >= k) w.FJ[t] -= w.FJ[i * 15 + j] * w.FJ[k * 15 + j]; }
-        __syncthreads();
-    }
-    if (t < 225) w.FP[t] = 0;
-    __syncthreads();
-    if (t < 15) {
-        double x[15];
-        bool ok = true;
-        for (int i = 0; i < 15; i++) ok = ok && w.FJ[i * 15 + i] > 0.0;
-        for (int i = 0; i < 15; i++) {
-            double sacc = (i == t) ? 1.0 : 0.0;
-            for (int k = 0; k < i; k++) sacc -= w.FJ[i * 15 + k] * x[k];
-            x[i] = ok ? sacc / w.FJ[i * 15 + i] : 0.0;
-            w.FP[i * 15 + t] = x[i];
-        }
-    }
-    __syncthreads();
-    if (t < 225) p.sqrt_info[t] = w.FP[t];
-    __syncthreads();
-}
-// one step of the jacobian / covariance recursion on the LDS-resident matrices, all threads: J <- F J, P <- F P F^T + V Q V^T
-// (integration_base.h:131-132).  N: the noise densities (acc_n, gyr_n, acc_w, gyr_w): the sequence's vio_calibration, or the vio_config
-// of a stage harness
-template <class N> __device__ __forceinline__ void preint_cov_step(PreWork &w, const double *Fk, const double *Vk, const N &c) {
-    const int t = threadIdx.x;
-    if (t < 225) {
-        int i = t / 15, j = t - i * 15;
-        double s1 = 0, s2 = 0;
-        for (int u = 0; u < 15; u++) { s1 += Fk[i * 15 + u] * w.J[u * 15 + j]; s2 += Fk[i * 15 + u] * w.Pm[u * 15 + j]; }
-        w.FJ[t] = s1; w.FP[t] = s2;
-    }
-    __syncthreads();
-    if (t < 225) {
-        int i = t / 15, j = t - i * 15;
-        double s1 = 0;
-        for (int u = 0; u < 15; u++) s1 += w.FP[i * 15 + u] * Fk[j * 15 + u];
-        const double nn[6] = {c.acc_n * c.acc_n, c.gyr_n * c.gyr_n, c.acc_n * c.acc_n, c.gyr_n * c.gyr_n, c.acc_w * c.acc_w, c.gyr_w * c.gyr_w};
-        double tt = 0;
-        for (int u = 0; u < 18; u++) tt += Vk[i * 18 + u] * nn[u / 3] * Vk[j * 18 + u];
-        w.J[t] = w.FJ[t];
-        w.Pm[t] = s1 + tt;
-    }
-    __syncthreads();
-}
-// one propagate(dt, acc, gyr) on the LDS-resident jacobian/covariance; p's small state is updated by thread 0
-template <class N> __device__ void preint_propagate(PreInt &p, PreWork &w, const N &c, double dt, v3 acc1, v3 gyr1) {
-    if (threadIdx.x == 0) {
-        bf::PreintStep o = bf::preint_midpoint(p, dt, acc1, gyr1, w.F, w.V);
-        st3(p.dp, o.dp); st3(p.dv, o.dv);
-        quat q = qnormalized(o.dq);
-        p.dq[0] = q.w; p.dq[1] = q.x; p.dq[2] = q.y; p.dq[3] = q.z;
-        p.sum_dt += dt;
-        st3(p.acc0, acc1); st3(p.gyr0, gyr1);
-    }
-    __syncthreads();
-    preint_cov_step(w, w.F, w.V, c);
-}
-
-// Sample sources of preint_propagate_many: get(q) yields dt, acc and gyr of sample q of the n to integrate.
-struct PreintArrays {   // the samples as arrays (a slot's own buffers, a stage harness)
-    const double *dt; const double (*acc)[3]; const double (*gyr)[3];
-    __device__ __forceinline__ void get(int q, double &dt_q, double *acc_q, double *gyr_q) const {
-        dt_q = dt[q];
-        for (int k = 0; k < 3; k++) { acc_q[k] = acc[q][k]; gyr_q[k] = gyr[q][k]; }
-    }
-};
-// Side jobs of preint_propagate_many: run by thread 64 (another wavefront than thread 0's) on the m staged samples of a chunk.
-struct PreintNoSide { __device__ __forceinline__ void operator()(int, const double *, const double (*)[3], const double (*)[3]) {} };
-// Estimator::processIMU's world-state recursion of a frame (estimator.cpp:142-152); acc_0 / gyr_0 are the estimator's, not the slot's
-struct WorldStep {
-    v3 a0, g0, P, V; m3 R; v3 Ba, Bg, g;
-    __device__ __forceinline__ void operator()(int m, const double *dt_s, const double (*acc_s)[3], const double (*gyr_s)[3]) {
-        for (int k = 0; k < m; k++) {
-            const v3 acc = ld3(acc_s[k]), gyr = ld3(gyr_s[k]);
-            const double dt = dt_s[k];
-            v3 un_acc_0 = sub(mul(R, sub(a0, Ba)), g);
-            v3 un_gyr = sub(scl(0.5, add(g0, gyr)), Bg);
-            R = mul(R, q2R(deltaQ(scl(dt, un_gyr))));
-            v3 un_acc_1 = sub(mul(R, sub(acc, Ba)), g);
-            v3 un_acc = scl(0.5, add(un_acc_0, un_acc_1));
-            P = add(add(P, scl(dt, V)), scl(dt * dt, scl(0.5, un_acc)));
-            V = add(V, scl(dt, un_acc));
-            a0 = acc; g0 = gyr;
-        }
-    }
-};
-
-// n propagate steps on the LDS-resident jacobian / covariance (preint_load'ed into w), IntegrationBase::push_back pipelined in chunks of
-// PI_CH samples:
-//   A  thread 0 runs the short delta-state recursion of the chunk and keeps the state before every step, thread 64 - another
-//      wavefront - the caller's side job, and with IDLE_CLEARS the threads from 128 on clear the chunk's F / V (the caller then
-//      launches more than 128 threads);
-//   B  one lane per sample builds that step's F (15 x 15) and V (15 x 18) from the state before it, clearing them first without
-//      IDLE_CLEARS (495 stores of one lane);
-//   C  the jacobian / covariance recursion consumes them step by step.
-// The arithmetic of n calls of preint_propagate (be_factors.h preint_state_step / preint_step_FV are the two halves of preint_midpoint)
-// with the serial part of a step shrunk from the whole midpoint step to the recursion.  append: the samples are also filed into p's
-// own buffers (IntegrationBase::push_back); the caller decides what running over VIO_IMU_SLOT_CAP means.  The per-frame integration of
-// be_ingest and the merge of MARGIN_SECOND_NEW (estimator.cpp:1651-1687) both run this.
-// lds_fv: PREINT_MANY_LDS_DOUBLES (kernels.h) doubles for F and V of a chunk, lent by the caller.
-template <bool IDLE_CLEARS, class N, class Src, class Side>
-__device__ void preint_propagate_many(PreInt &p, PreWork &w, const N &cfg, int n, const Src &src, Side &side, bool append, double *lds_fv) {
-    const int t = threadIdx.x, nt = blockDim.x;
-    double (*pm_F)[225] = (double (*)[225])lds_fv;
-    double (*pm_V)[270] = (double (*)[270])(lds_fv + PI_CH * 225);
-    __shared__ double pm_dt[PI_CH], pm_acc[PI_CH][3], pm_gyr[PI_CH][3];
-    __shared__ bf::PreintPre pm_pre[PI_CH];
-    const int nb0 = p.n_buf;
-    const v3 lba = ld3(p.lin_ba), lbg = ld3(p.lin_bg);
-    quat s_dq = mkq(p.dq[0], p.dq[1], p.dq[2], p.dq[3]);
-    v3 s_dp = ld3(p.dp), s_dv = ld3(p.dv), s_a0 = ld3(p.acc0), s_g0 = ld3(p.gyr0);
-    double s_sum = p.sum_dt;
-    __syncthreads();
-    for (int q0 = 0; q0 < n; q0 += PI_CH) {
-        const int m = min(PI_CH, n - q0);
-        if (t < m) {   // stage the chunk's samples
-            const int q = q0 + t, nb = nb0 + q;
-            double dt, acc[3], gyr[3];
-            src.get(q, dt, acc, gyr);
-            pm_dt[t] = dt;
-            for (int k = 0; k < 3; k++) { pm_acc[t][k] = acc[k]; pm_gyr[t][k] = gyr[k]; }
-            if (append && nb < VIO_IMU_SLOT_CAP) { p.dt_buf[nb] = dt; for (int k = 0; k < 3; k++) { p.acc_buf[nb][k] = acc[k]; p.gyr_buf[nb][k] = gyr[k]; } }
-        }
-        __syncthreads();
-        if (t == 0) {
-            for (int k = 0; k < m; k++) {
-                const v3 acc = ld3(pm_acc[k]), gyr = ld3(pm_gyr[k]);
-                pm_pre[k].dq = s_dq; pm_pre[k].acc0 = s_a0; pm_pre[k].gyr0 = s_g0;
-                bf::preint_state_step(s_dq, s_dp, s_dv, s_a0, s_g0, lba, lbg, pm_dt[k], acc, gyr);
-                s_sum += pm_dt[k];
-                s_a0 = acc; s_g0 = gyr;
-            }
-        } else if (t == 64) {
-            side(m, pm_dt, pm_acc, pm_gyr);
-        } else if (IDLE_CLEARS && t >= 128) {   // (idle otherwise during the recursions)
-            for (int q = t - 128; q < m * 225; q += nt - 128) (&pm_F[0][0])[q] = 0;
-            for (int q = t - 128; q < m * 270; q += nt - 128) (&pm_V[0][0])[q] = 0;
-        }
-        __syncthreads();
-        if (t < m) bf::preint_step_FV(pm_pre[t], lba, lbg, pm_dt[t], ld3(pm_acc[t]), ld3(pm_gyr[t]), pm_F[t], pm_V[t], !IDLE_CLEARS);
-        __syncthreads();
-        for (int k = 0; k < m; k++) preint_cov_step(w, pm_F[k], pm_V[k], cfg);
-    }
-    if (t == 0) {
-        st3(p.dp, s_dp); st3(p.dv, s_dv);
-        p.dq[0] = s_dq.w; p.dq[1] = s_dq.x; p.dq[2] = s_dq.y; p.dq[3] = s_dq.z;
-        p.sum_dt = s_sum;
-        st3(p.acc0, s_a0); st3(p.gyr0, s_g0);
-        if (append) p.n_buf = min(nb0 + n, VIO_IMU_SLOT_CAP);
-    }
-    __syncthreads();
-}
-
-// 4x4 / small symmetric cyclic Jacobi (row-cyclic, as oracle/om.h sym_eig); A destroyed, eigenvalues unsorted in A diag
-// stable compaction of the landmark order list; flags[k] = keep. Freed slots go back to the free stack.
-__device__ void lm_compact(Ctx &c, int *flags, int *offs, int *scratch) {
-    int n = c.be->n_lm;
-    int kept = block_scan_flags(flags, n, offs, scratch);
-    const int t = threadIdx.x, nt = blockDim.x;
-    int nfree0 = c.be->n_free;
-    for (int k = t; k < n; k += nt) c.lm_tmp[k] = c.lm_order[k];
-    __syncthreads();
-    for (int k = t; k < n; k += nt) {
-        int slot = c.lm_tmp[k];
-        if (flags[k]) c.lm_order[offs[k]] = slot;
-        else c.lm_free[nfree0 + (k - offs[k])] = slot;
-    }
-    __syncthreads();
-    if (t == 0) { c.be->n_lm = kept; c.be->n_free = nfree0 + (n - kept); }
-    __syncthreads();
-}
-
-// the same compaction on LDS copies of the order list, the flags and the offsets (finish_body<true>): the counters stay in registers (n, nfree:
-// uniform over the workgroup), the freed slots go to the free stack in HBM in the same places; the caller writes order / counters back once
-__device__ void lm_compact_staged(Ctx &c, int *ord, int *tmp, int *flags, int *offs, int *scratch, int &n, int &nfree) {
-    const int kept = block_scan_flags(flags, n, offs, scratch);
-    const int t = threadIdx.x, nt = blockDim.x;
-    for (int k = t; k < n; k += nt) tmp[k] = ord[k];
-    __syncthreads();
-    // (two loops: as one if / else the compiler merges the two stores into a single flat store through a selected LDS-or-HBM address)
-    for (int k = t; k < n; k += nt) if (flags[k]) ord[offs[k]] = tmp[k];
-    for (int k = t; k < n; k += nt) if (!flags[k]) c.lm_free[nfree + (k - offs[k])] = tmp[k];
-    __syncthreads();
-    nfree += n - kept;
-    n = kept;
-}
-
-}  // namespace
-
-// ------------------------------------------------------------------ VO mode: FeatureManager::initFramePoseByPnP
-// cv::Rodrigues and its derivative (closed form, Gallego & Yezzi 2015), as the host side of the dynamic initialisation restates them
-__device__ m3 pnp_rodrigues(v3 r) {
-    const double th = nrm(r);
-    if (th < 2.220446049250313e-16) return eye();
-    const v3 k = scl(1.0 / th, r);
-    const double cth = cos(th), sth = sin(th), c1 = 1 - cth;
-    const m3 K = skew(k);
-    const double kk[3] = {k.x, k.y, k.z};
-    m3 R;
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) R.a[i * 3 + j] = (i == j ? cth : 0.0) + c1 * kk[i] * kk[j] + sth * K.a[i * 3 + j];
-    return R;
-}
-__device__ v3 pnp_rodrigues_inv(const m3 &R) {
-    v3 r = mk(R.a[7] - R.a[5], R.a[2] - R.a[6], R.a[3] - R.a[1]);
-    const double sn = sqrt(dot(r, r) * 0.25);
-    double cs = (R.a[0] + R.a[4] + R.a[8] - 1) * 0.5;
-    cs = cs > 1 ? 1 : (cs < -1 ? -1 : cs);
-    const double th = acos(cs);
-    if (sn < 1e-5) {
-        if (cs > 0) return mk(0, 0, 0);
-        v3 v;
-        v.x = sqrt(fmax((R.a[0] + 1) * 0.5, 0.0));
-        v.y = sqrt(fmax((R.a[4] + 1) * 0.5, 0.0)) * (R.a[1] < 0 ? -1.0 : 1.0);
-        v.z = sqrt(fmax((R.a[8] + 1) * 0.5, 0.0)) * (R.a[2] < 0 ? -1.0 : 1.0);
-        if (fabs(v.x) < fabs(v.y) && fabs(v.x) < fabs(v.z) && (R.a[5] > 0) != (v.y * v.z > 0)) v.z = -v.z;
-        return scl(th / nrm(v), v);
-    }
-    return scl(th / (2 * sn), r);
-}
-// dR / dr_i (i = 0 .. 2) at r, Rm = pnp_rodrigues(r)
-__device__ void pnp_rodrigues_jac(v3 r, const m3 &Rm, m3 dR[3]) {
-    const double th2 = dot(r, r);
-    for (int i = 0; i < 3; i++) {
-        const v3 e = mk(i == 0, i == 1, i == 2);
-        if (th2 < 1e-24) { dR[i] = skew(e); continue; }
-        const v3 w = cross(r, mul(sub(eye(), Rm), e));
-        dR[i] = scl(1.0 / th2, mul(add(scl(get(r, i), skew(r)), skew(w)), Rm));
-    }
-}
-// The Levenberg-Marquardt core of cv::solvePnP(ITERATIVE): refines par[6] = (rvec, tvec) in LDS over n pairs pts[5 n] = (X, Y, Z, u, v).
-// prev: 6 doubles of LDS, sw: >= (waves x 28) doubles of LDS.  Every thread of the block takes part.  trace (may be null, written by thread
-// 0): outer iterations, lambda escalations, final lambda_lg10.
-__device__ void pnp_refine_block(const double *pts, int n, double *sh_par, double *sh_prev, double *sw, int *trace = nullptr) {
-    const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6, nw = nt >> 6;
-    // reduction of NV values per thread: wave DPP sums, then a fixed-order sum over the waves
-    auto reduce = [&](double *v, int NV) {
-        for (int q = 0; q < NV; q++) v[q] = wave_sum_dpp(v[q]);
-        __syncthreads();
-        if (lane == 0) for (int q = 0; q < NV; q++) sw[wave * 28 + q] = v[q];
-        __syncthreads();
-        for (int q = 0; q < NV; q++) { double r = 0; for (int w = 0; w < nw; w++) r += sw[w * 28 + q]; v[q] = r; }
-    };
-    // residuals (and Jacobian sums) at sh_par; every thread returns the same values
-    auto project = [&](bool jac, double *acc /*27: JtJ upper 21 + JtErr 6*/) -> double {
-        const v3 r = mk(sh_par[0], sh_par[1], sh_par[2]), tt = mk(sh_par[3], sh_par[4], sh_par[5]);
-        const m3 Rm = pnp_rodrigues(r);
-        m3 dR[3];
-        if (jac) pnp_rodrigues_jac(r, Rm, dR);
-        double v[28];
-        for (int q = 0; q < 28; q++) v[q] = 0;
-        for (int i = t; i < n; i += nt) {
-            const double *q = pts + (size_t)i * 5;
-            const v3 Y = add(mul(Rm, mk(q[0], q[1], q[2])), tt);
-            const double iz = 1.0 / Y.z, x = Y.x * iz, y = Y.y * iz;
-            const double e0 = x - q[3], e1 = y - q[4];
-            v[27] += e0 * e0 + e1 * e1;
-            if (!jac) continue;
-            double J0[6], J1[6];
-            for (int k = 0; k < 3; k++) {
-                const v3 d = mul(dR[k], mk(q[0], q[1], q[2]));
-                J0[k] = iz * d.x - x * iz * d.z;
-                J1[k] = iz * d.y - y * iz * d.z;
-            }
-            J0[3] = iz; J0[4] = 0; J0[5] = -x * iz;
-            J1[3] = 0; J1[4] = iz; J1[5] = -y * iz;
-            int e = 0;
-            for (int a = 0; a < 6; a++) for (int b = a; b < 6; b++) v[e++] += J0[a] * J0[b] + J1[a] * J1[b];
-            for (int a = 0; a < 6; a++) v[21 + a] += J0[a] * e0 + J1[a] * e1;
-        }
-        reduce(v, jac ? 28 : 28);
-        if (jac) for (int q = 0; q < 27; q++) acc[q] = v[q];
-        return sqrt(v[27]);
-    };
-    double acc[27];
-    int lambda_lg10 = -3, iters = 0, raises = 0;
-    double prev_err = 0;
-    auto take_step = [&]() {   // thread 0: param = prev - pinv(JtJ with damped diagonal) JtErr
-        if (t == 0) {
-            const double lambda = exp(lambda_lg10 * 2.302585092994046);
-            double N[36], V[36];
-            int e = 0;
-            for (int a = 0; a < 6; a++) for (int b = a; b < 6; b++) { N[a * 6 + b] = acc[e]; N[b * 6 + a] = acc[e]; e++; }
-            for (int a = 0; a < 6; a++) N[a * 7] *= 1.0 + lambda;
-            jacobi_small(N, V, 6);
-            double wmax = 0;
-            for (int k = 0; k < 6; k++) wmax = fmax(wmax, fabs(N[k * 7]));
-            double d[6] = {0, 0, 0, 0, 0, 0};
-            for (int k = 0; k < 6; k++) {
-                const double wk = N[k * 7];
-                if (!(fabs(wk) > wmax * 2 * 2.220446049250313e-16 * 6)) continue;
-                double sacc = 0;
-                for (int i = 0; i < 6; i++) sacc += V[i * 6 + k] * acc[21 + i];
-                sacc /= wk;
-                for (int i = 0; i < 6; i++) d[i] += V[i * 6 + k] * sacc;
-            }
-            for (int i = 0; i < 6; i++) sh_par[i] = sh_prev[i] - d[i];
-        }
-        __syncthreads();
-    };
-    for (;;) {
-        const double e_at = project(true, acc);
-        if (t == 0) for (int i = 0; i < 6; i++) sh_prev[i] = sh_par[i];
-        __syncthreads();
-        take_step();
-        if (iters == 0) prev_err = e_at;
-        bool done = false;
-        for (;;) {
-            const double e = project(false, acc);
-            if (e > prev_err && ++lambda_lg10 <= 16) { raises++; take_step(); continue; }
-            lambda_lg10 = max(lambda_lg10 - 1, -16);
-            double dn = 0, pn = 0;
-            for (int i = 0; i < 6; i++) { dn += (sh_par[i] - sh_prev[i]) * (sh_par[i] - sh_prev[i]); pn += sh_prev[i] * sh_prev[i]; }
-            // cvNorm(param, prevParam, CV_RELATIVE_L2) = |param - prev| / (|prev| + DBL_EPSILON)
-            if (++iters >= 20 || sqrt(dn) / (sqrt(pn) + 2.220446049250313e-16) < 1.1920928955078125e-07) done = true;
-            prev_err = e;
-            break;
-        }
-        if (done) break;
-    }
-    if (trace && t == 0) { trace[0] = iters; trace[1] = raises; trace[2] = lambda_lg10; }
-    __syncthreads();
-}
-
-// FeatureManager::initFramePoseByPnP + solvePoseByPnP (feature_manager.cpp:545-642): cv::solvePnP(SOLVEPNP_ITERATIVE,
-// useExtrinsicGuess) = CvLevMarq on (rvec, tvec) with lambda = 10^k, diagonal x (1 + lambda), at most 20 iterations, FLT_EPSILON
-// on the relative parameter change.  Block-cooperative: one thread per 3-D / 2-D pair evaluates its two residual rows and 2 x 6
-// Jacobian, the 27 sums of J^T J / J^T e are reduced in a fixed order, thread 0 solves the damped 6 x 6 system through its
-// eigen-decomposition (cv::solve DECOMP_SVD).  pts: scratch in HBM, 5 doubles per pair.  sw: >= 16 * 28 + 64 doubles of LDS.
-__device__ void init_frame_pose_by_pnp(Ctx &c, int fc, double *pts, double *sw) {
-    const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6, nw = nt >> 6;
-    BeSeq &be = *c.be;
-    if (fc <= 0) return;
-    __shared__ int sh_n;
-    __shared__ double sh_par[6], sh_prev[6], sh_flag[4];
-    if (t == 0) sh_n = 0;
-    __syncthreads();
-    const m3 ric = ldm(be.ric);
-    const v3 tic = ld3(be.tic);
-    const int nlm = be.n_lm;
-    // pairs in list order (deterministic): flags + scan
-    int *flag = c.lm_pidx, *offs = c.lm_aidx;   // free outside the solve
-    __shared__ int scan_scratch[2 * 256 + 8];
-    for (int k = t; k < nlm; k += nt) {
-        const int slot = c.lm_order[k];
-        const int index = fc - c.lm_start[slot];
-        flag[k] = (c.lm_depth[slot] > 0 && index >= 0 && c.lm_nobs[slot] >= index + 1) ? 1 : 0;
-    }
-    __syncthreads();
-    const int n = block_scan_flags(flag, nlm, offs, scan_scratch);
-    for (int k = t; k < nlm; k += nt) {
-        if (!flag[k]) continue;
-        const int slot = c.lm_order[k], st = c.lm_start[slot];
-        const double *o0 = obs_ptr(c, slot, st), *oi = obs_ptr(c, slot, fc);
-        const double d = c.lm_depth[slot];
-        const v3 pc = add(mul(ric, mk(o0[0] * d, o0[1] * d, o0[2] * d)), tic);
-        const v3 pw = add(mul(ldm(be.Rs[st]), pc), ld3(be.Ps[st]));
-        double *q = pts + (size_t)offs[k] * 5;
-        q[0] = (double)(float)pw.x; q[1] = (double)(float)pw.y; q[2] = (double)(float)pw.z;   // cv::Point3f / cv::Point2f
-        q[3] = (double)(float)oi[0]; q[4] = (double)(float)oi[1];
-    }
-    __syncthreads();
-    if (n < 4) return;
-    if (t == 0) {
-        const m3 RCam = mul(ldm(be.Rs[fc - 1]), ric);
-        const v3 PCam = add(mul(ldm(be.Rs[fc - 1]), tic), ld3(be.Ps[fc - 1]));
-        const m3 R0 = tr(RCam);
-        const v3 P0 = neg(mul(R0, PCam));
-        const v3 r = pnp_rodrigues_inv(R0);
-        sh_par[0] = r.x; sh_par[1] = r.y; sh_par[2] = r.z; sh_par[3] = P0.x; sh_par[4] = P0.y; sh_par[5] = P0.z;
-    }
-    __syncthreads();
-    pnp_refine_block(pts, n, sh_par, sh_prev, sw);
-    __syncthreads();
-    if (t == 0) {
-        bool fin = true;
-        for (int i = 0; i < 6; i++) fin = fin && isfinite(sh_par[i]);
-        if (fin) {
-            const m3 Rn = pnp_rodrigues(mk(sh_par[0], sh_par[1], sh_par[2]));
-            const v3 tn = mk(sh_par[3], sh_par[4], sh_par[5]);
-            const m3 RCam = tr(Rn);
-            const v3 PCam = mul(RCam, neg(tn));
-            stm(be.Rs[fc], mul(RCam, tr(ric)));
-            st3(be.Ps[fc], add(neg(mul(RCam, mul(tr(ric), tic))), PCam));
-        }
-    }
-    __syncthreads();
-}
-
-// FeatureManager::triangulateWithDepth (feature_manager.cpp:386-543), one thread per landmark of the list
-__device__ void triangulate_with_depth(Ctx &c, int nlm) {
-    const int t = threadIdx.x, nt = blockDim.x;
-    BeSeq &be = *c.be;
-    const vio_config &cfg = c.C->c;
-        m3 ric = ldm(be.ric);
-        v3 tic = ld3(be.tic);
-        for (int k = t; k < nlm; k += nt) {
-            int slot = c.lm_order[k];
-            if (c.lm_depth[slot] > 0) continue;
-            if (!in_problem(c, slot)) continue;
-            int imu_i = c.lm_start[slot], K = c.lm_nobs[slot];
-            v3 trr = add(ld3(be.Ps[imu_i]), mul(ldm(be.Rs[imu_i]), tic));
-            m3 Rr = mul(ldm(be.Rs[imu_i]), ric);
-            double vsum = 0, rsum = 0;
-            int vn = 0, rn = 0, no_depth = 0;
-            for (int a = 0; a < K; a++) {
-                const double *oa = obs_ptr(c, slot, imu_i + a);
-                if (oa[8] == 0) { no_depth++; continue; }
-                v3 t0 = add(ld3(be.Ps[imu_i + a]), mul(ldm(be.Rs[imu_i + a]), tic));
-                m3 R0 = mul(ldm(be.Rs[imu_i + a]), ric);
-                v3 point0 = scl(oa[8], mk(oa[0], oa[1], oa[2]));
-                point0 = mk(oa[0] * oa[8], oa[1] * oa[8], oa[2] * oa[8]);
-                v3 t2r = mul(tr(Rr), sub(t0, trr));
-                m3 R2r = mul(tr(Rr), R0);
-                for (int b = 0; b < K; b++) {
-                    if (a == b) continue;
-                    const double *ob = obs_ptr(c, slot, imu_i + b);
-                    v3 t1 = add(ld3(be.Ps[imu_i + b]), mul(ldm(be.Rs[imu_i + b]), tic));
-                    m3 R1 = mul(ldm(be.Rs[imu_i + b]), ric);
-                    v3 t20 = mul(tr(R0), sub(t1, t0));
-                    m3 R20 = mul(tr(R0), R1);
-                    v3 pp = sub(mul(tr(R20), point0), mul(tr(R20), t20));
-                    double rx = ob[0] - pp.x / pp.z, ry = ob[1] - pp.y / pp.z;
-                    if (sqrt(rx * rx + ry * ry) < 10.0 / 460) {
-                        v3 pr = add(mul(R2r, point0), t2r);
-                        if (oa[8] > cfg.depth_max) { rsum += pr.z; rn++; } else { vsum += pr.z; vn++; }
-                    }
-                }
-            }
-            double dep;
-            int ef;
-            if (vn == 0) {
-                if (rn == 0) {
-                    if (no_depth == K) {
-                        double AtA[16], Vv[16];
-                        for (int q = 0; q < 16; q++) AtA[q] = 0;
-                        v3 t0 = add(ld3(be.Ps[imu_i]), mul(ldm(be.Rs[imu_i]), tic));
-                        m3 R0 = mul(ldm(be.Rs[imu_i]), ric);
-                        for (int a = 0; a < K; a++) {
-                            const double *oa = obs_ptr(c, slot, imu_i + a);
-                            v3 t1 = add(ld3(be.Ps[imu_i + a]), mul(ldm(be.Rs[imu_i + a]), tic));
-                            m3 R1 = mul(ldm(be.Rs[imu_i + a]), ric);
-                            v3 tt = mul(tr(R0), sub(t1, t0));
-                            m3 Rt = tr(mul(tr(R0), R1));
-                            v3 mt = neg(mul(Rt, tt));
-                            double Pm[12];
-                            for (int r = 0; r < 3; r++) { for (int q = 0; q < 3; q++) Pm[r * 4 + q] = Rt.a[r * 3 + q]; Pm[r * 4 + 3] = get(mt, r); }
-                            v3 f = mk(oa[0], oa[1], oa[2]);
-                            f = scl(1.0 / nrm(f), f);
-                            f = mk(oa[0] / nrm(mk(oa[0], oa[1], oa[2])), oa[1] / nrm(mk(oa[0], oa[1], oa[2])), oa[2] / nrm(mk(oa[0], oa[1], oa[2])));
-                            double row[8];
-                            for (int q = 0; q < 4; q++) { row[q] = f.x * Pm[8 + q] - f.z * Pm[q]; row[4 + q] = f.y * Pm[8 + q] - f.z * Pm[4 + q]; }
-                            for (int rr = 0; rr < 2; rr++)
-                                for (int x = 0; x < 4; x++) for (int y = 0; y < 4; y++) AtA[x * 4 + y] += row[rr * 4 + x] * row[rr * 4 + y];
-                        }
-                        jacobi_small(AtA, Vv, 4);
-                        int mi = 0;
-                        for (int q = 1; q < 4; q++) if (AtA[q * 5] < AtA[mi * 5]) mi = q;
-                        double svd_method = Vv[2 * 4 + mi] / Vv[3 * 4 + mi];
-                        dep = svd_method < cfg.depth_min ? cfg.depth_max : svd_method;
-                        ef = 2;
-                    } else
-                        continue;
-                } else { dep = rsum / rn; ef = 0; }
-            } else { dep = vsum / vn; ef = 1; }
-            if (dep < 0.1) { dep = cfg.init_depth; ef = 0; }
-            c.lm_depth[slot] = dep;
-            c.lm_est[slot] = ef;
-        }
-}
-
-// pre_integrations[j]->repropagate(Vector3d::Zero(), Bgs[j]) for every window slot (estimator.cpp:275-279, :829-836), block-cooperative
-__device__ void repropagate_window(Ctx &c, PreWork &pw) {
-    const int t = threadIdx.x, nt = blockDim.x, W = c.W;
-    BeSeq &be = *c.be;
-    const vio_config &cfg = c.C->c;
-    for (int j = 0; j <= W; j++) {
-            PreInt &p = c.pre[be.pre_idx[j]];
-            if (!p.valid) continue;
-            if (t == 0) {
-                int nb = p.n_buf;
-                v3 la = ld3(p.lin_acc), lg = ld3(p.lin_gyr);
-                p.sum_dt = 0;
-                st3(p.acc0, la); st3(p.gyr0, lg);
-                p.dp[0] = p.dp[1] = p.dp[2] = 0; p.dv[0] = p.dv[1] = p.dv[2] = 0;
-                p.dq[0] = 1; p.dq[1] = p.dq[2] = p.dq[3] = 0;
-                p.lin_ba[0] = p.lin_ba[1] = p.lin_ba[2] = 0;
-                st3(p.lin_bg, ld3(be.Bgs[j]));
-                p.n_buf = nb;
-            }
-            for (int i = t; i < 225; i += nt) { pw.J[i] = ((i / 15) == (i % 15)) ? 1.0 : 0.0; pw.Pm[i] = 0; }
-            __syncthreads();
-            for (int q = 0; q < p.n_buf; q++) preint_propagate(p, pw, *c.K, p.dt_buf[q], ld3(p.acc_buf[q]), ld3(p.gyr_buf[q]));
-            preint_store(p, pw);
-        }
-}
-
-// ====================================================================================================== the frame's IMU, ahead of be_ingest
-// getIMUInterval (estimator.cpp:1910-1942) on a sequence's ring, by one wavefront: head = the first sample later than prevT from head0 on, k = the
-// first one at or after curTime: 64 samples per trip, one lane each (the two scalar loops were a chain of dependent loads, ~14 of them per frame at
-// 200 Hz).  Every lane returns the same head and k.
-__device__ __forceinline__ void imu_interval_search(const double *it, int NIMU, int cnt_all, double prevT, double curTime, int head0, int &head, int &k) {
-    const int t = threadIdx.x & 63;
-    head = head0;
-    for (;;) {
-        const int idx = head + t;
-        const bool pass = idx < cnt_all && it[idx % NIMU] <= prevT;
-        const unsigned long long stop = ~__ballot(pass);
-        if (stop) { head += __ffsll((long long)stop) - 1; break; }
-        head += 64;
-    }
-    k = head;
-    for (;;) {
-        const int idx = k + t;
-        const bool pass = idx < cnt_all && it[idx % NIMU] < curTime;
-        const unsigned long long stop = ~__ballot(pass);
-        if (stop) { k += __ffsll((long long)stop) - 1; break; }
-        k += 64;
-    }
-}
-// PreAhead::in, entry i, as the sequence holds it now
-__device__ __forceinline__ const double *ahead_in_ptr(const BeSeq &be, int W, int i) {
-    return i < 3 ? be.acc_0 + i : i < 6 ? be.gyr_0 + (i - 3) : i < 9 ? be.Ps[W] + (i - 6) : i < 12 ? be.Vs[W] + (i - 9) : i < 21 ? be.Rs[W] + (i - 12)
-         : i < 24 ? be.Bas[W] + (i - 21) : i < 27 ? be.Bgs[W] + (i - 24) : be.g + (i - 27);
-}
-__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
-
-// What be_ingest does between its feature part and the triangulation for a steady-state frame (NON_LINEAR, full window), on copies: the interval search,
-// the fresh pre-integration of slot W and its n propagate steps with processIMU's world-state recursion as the side job -- through the very device
-// functions be_ingest calls, so that the bits are the same.  Its inputs are final once the previous frame's solve has ended (the window slide of
-// be_marg never writes slot W of Ps / Vs / Rs / Bas / Bgs, nor acc_0 / gyr_0 / g / td / prevTime / imu_head), so it runs beside that frame's be_marg.
-// It reads the sequence and writes nothing but its record.
-__global__ __launch_bounds__(256) void be_preint_ahead_kernel(Batch B, const double *stamps, PreAhead *ahead) {
-    const int s = blockIdx.x + B.s0, t = threadIdx.x;
-    Ctx c = make_ctx(B, s);
-    const DevCfg &C = *B.cfg;
-    const vio_calibration &K = *c.K;
-    const BeSeq &be = *c.be;
-    const int W = c.W;
-    PreAhead &rec = ahead[s];
-    __shared__ int sh_i[8];
-    __shared__ double sh_in[30];
-    __shared__ PreWork pw;
-    __shared__ double pi_fv[PREINT_MANY_LDS_DOUBLES];
-    const double *it = B.imu_t + (size_t)s * C.NIMU;
-    const double *ia = B.imu_acc + (size_t)s * C.NIMU * 3, *ig = B.imu_gyr + (size_t)s * C.NIMU * 3;
-    const double stamp = stamps[s], prevT = be.prevTime, curTime = stamp + be.td;
-    const int head0 = be.imu_head, cnt_all = be.imu_count;
-    if (t < 30) sh_in[t] = *ahead_in_ptr(be, W, t);
-    if (t == 0) {
-        bool ok = C.c.use_imu && W > 0 && be.solver_flag == 1 && be.frame_count == W && !be.rebooted && be.first_imu && be.initFirstPoseFlag;
-        ok = ok && head0 >= 0 && cnt_all > head0 && cnt_all - head0 <= C.NIMU;   // (a longer backlog: be_ingest moves the head and flags the overrun)
-        ok = ok && curTime <= it[(cnt_all - 1) % C.NIMU];                          // the IMU reaches the frame (estimator.cpp:178-183)
-        sh_i[0] = ok;
-        if (!ok) rec.valid = 0;
-    }
-    __syncthreads();
-    if (!sh_i[0]) return;
-    if (t < 64) {
-        int head, k;
-        imu_interval_search(it, C.NIMU, cnt_all, prevT, curTime, head0, head, k);
-        sh_i[6] = head; sh_i[7] = k;
-    }
-    PreInt &P = rec.pre;
-    if (t == 0) {
-        rec.valid = 0;   // until the record is complete
-        rec.stamp = stamp; rec.cur_time = curTime; rec.prev_time = prevT;
-        rec.imu_head = head0; rec.imu_count = cnt_all;
-        rec.noise[0] = K.acc_n; rec.noise[1] = K.gyr_n; rec.noise[2] = K.acc_w; rec.noise[3] = K.gyr_w;
-        bf::preint_init(P, ld3(sh_in), ld3(sh_in + 3), ld3(sh_in + 21), ld3(sh_in + 24));
-    }
-    if (t >= 64 && t < 94) rec.in[t - 64] = sh_in[t - 64];
-    __syncthreads();
-    const int head = sh_i[6], n = sh_i[7] - head + 1;
-    preint_load(P, pw);
-    const PreintRing ring = {it, ia, ig, head, C.NIMU, prevT, curTime, n};
-    WorldStep ws = {ld3(sh_in), ld3(sh_in + 3), ld3(sh_in + 6), ld3(sh_in + 9), ldm(sh_in + 12), ld3(sh_in + 21), ld3(sh_in + 24), ld3(sh_in + 27)};
-    preint_propagate_many<true>(P, pw, K, n, ring, ws, true, pi_fv);
-    if (t == 64) { st3(rec.out, ws.P); st3(rec.out + 3, ws.V); stm(rec.out + 6, ws.R); st3(rec.out + 15, ws.a0); st3(rec.out + 18, ws.g0); }
-    preint_store(P, pw);
-    if (t == 0) { rec.head = head; rec.k = sh_i[7]; rec.n = n; rec.valid = 1; }
-}
-
-// be_ingest's side: is `rec` the result of exactly the integration this frame would run (every input bit for bit, slot W's pre-integration P the
-// untouched fresh one)?  Then file it -- what the integration would have written, no byte more (the tails of the slot's sample buffers keep their stale
-// content, as they do today) -- and return true.  Every thread of the block, uniform result.
-__device__ __forceinline__ bool preint_ahead_take(Ctx &c, PreAhead &rec, double stamp, double curTime, int *sh_flag) {
-    const int t = threadIdx.x, nt = blockDim.x, W = c.W;
-    BeSeq &be = *c.be;
-    const vio_calibration &K = *c.K;
-    PreInt &P = c.pre[be.pre_idx[W]];
-    if (t < 64) {
-        bool ok = true;
-        if (t < 30) ok = same_bits(rec.in[t], *ahead_in_ptr(be, W, t));
-        else if (t < 42) { const int i = t - 30; ok = same_bits(P.lin_acc[i], rec.in[i < 6 ? i : i + 15]); }   // lin_acc lin_gyr lin_ba lin_bg, contiguous
-        else if (t == 42) ok = same_bits(rec.noise[0], K.acc_n) && same_bits(rec.noise[1], K.gyr_n) && same_bits(rec.noise[2], K.acc_w) && same_bits(rec.noise[3], K.gyr_w);
-        else if (t == 43) ok = same_bits(rec.stamp, stamp) && same_bits(rec.cur_time, curTime) && same_bits(rec.prev_time, be.prevTime);
-        else if (t == 44) ok = rec.valid == 1 && rec.imu_head == be.imu_head && rec.imu_count == be.imu_count && P.valid && P.n_buf == 0 && be.first_imu && be.initFirstPoseFlag;
-        const bool all = __ballot(ok) == ~0ull;
-        if (t == 0) *sh_flag = all;
-    }
-    __syncthreads();
-    if (!*sh_flag) return false;
-    const int n = rec.n, m = min(n, VIO_IMU_SLOT_CAP);
-    const PreInt &Q = rec.pre;
-    {
-        double *d = (double *)&P;
-        const double *q = (const double *)&Q;
-        for (int i = t; i < (int)(offsetof(PreInt, dt_buf) / sizeof(double)); i += nt) d[i] = q[i];
-        for (int i = t; i < m; i += nt) P.dt_buf[i] = Q.dt_buf[i];
-        for (int i = t; i < 3 * m; i += nt) { (&P.acc_buf[0][0])[i] = (&Q.acc_buf[0][0])[i]; (&P.gyr_buf[0][0])[i] = (&Q.gyr_buf[0][0])[i]; }
-    }
-    if (t >= 64 && t < 85) {
-        const int i = t - 64;
-        double *d = i < 3 ? be.Ps[W] + i : i < 6 ? be.Vs[W] + (i - 3) : i < 15 ? be.Rs[W] + (i - 6) : i < 18 ? be.acc_0 + (i - 15) : be.gyr_0 + (i - 18);
-        *d = rec.out[i];
-    }
-    if (t == 0) {
-        P.n_buf = Q.n_buf;
-        be.imu_head = rec.k;   // that last sample is not popped
-        be.n_imu_frame = n;
-        be.imu_frame_head = rec.head;
-        be.prevTime = curTime;
-        if (n > VIO_IMU_SLOT_CAP) be.overflow |= 2;
-        rec.used++;
-    }
-    __syncthreads();
-    return true;
-}
-
-// ====================================================================================================== be_ingest
-// src.ids == NULL: the feature map packaged by the last vio_track / front-end of vio_feed (B.obs_id / B.obs / FeSeq);
-// otherwise a caller-supplied map (vio_process_obs = Estimator::processImage(image, header), estimator.h:46): n_obs[s] < 0 skips s.
-// EXCALIB (estimate_extrinsic = 2 handles only): the extrinsic-rotation calibration phase (be_excalib.h) runs after the pre-integration; the
-// dynamic LDS then also holds the correspondences (4 NP doubles, see vio_abi.hip ingest_lds_bytes).
-template <bool EXCALIB>
-__global__ __launch_bounds__(256) void be_ingest_kernel(Batch B, const uint16_t *depth_base, size_t depth_stride, IngestSrc src) {
-    const int s = blockIdx.x + B.s0, t = threadIdx.x, nt = blockDim.x;
-    Ctx c = make_ctx(B, s);
-    const DevCfg &C = *B.cfg;
-    const vio_config &cfg = C.c;
-    const vio_calibration &K = *c.K;   // the sequence's IMU noise
-    BeSeq &be = *c.be;
-    FeSeq &fe = *c.fe;
-    const int W = c.W;
-    __shared__ int sh_i[8];
-    __shared__ double sh_d[8];
-    __shared__ int scratch[2 * 256 + 8];
-    __shared__ double sred[256];
-    __shared__ PreWork pw;
-    PH_INIT;
-    const bool ext = src.ids != nullptr;
-    const int ext_n = ext ? src.n_obs[s] : 0;
-    const double in_stamp = ext ? src.stamps[s] : fe.cur_time;
-    if (t == 0) {
-        // the state the next call's tracker sees with tracker lag 1 (that tracker runs while THIS frame is still being optimised)
-        for (int k = 0; k < 3; k++) be.track_Bg[k] = be.latest_Bg[k];
-        be.track_td = be.td;
-        be.imu_count_ingest = be.imu_count;
-        be.do_solve = 0; be.do_marg = 0; be.processed = 0; be.rebooted = 0; be.init_frame = 0; be.dyn_failed = 0;
-        be.status_code = (!ext && fe.n_forw == -2) ? VIO_NEED_IMU : VIO_OK;
-        be.cur_stamp = in_stamp;
-        be.overflow = 0;
-        if (be.imu_count - be.imu_head > C.NIMU) { be.imu_head = be.imu_count - C.NIMU; be.overflow |= 16; }  // samples overwritten in the ring before they were consumed
-    }
-    __syncthreads();
-    PreAhead *const ahead = src.ahead ? src.ahead + s : nullptr;   // a record that is not taken over counts as declined, whatever the reason
-    if (ext ? ext_n <= 0 : (fe.n_forw < 0 || !fe.publish_ok)) {
-        if (ahead && t == 0) ahead->declined++;
-        return;
-    }
-    // ---- IMU availability (estimator.cpp:178-183, :1882-1888)
-    const double *it = B.imu_t + (size_t)s * C.NIMU;
-    const double *ia = B.imu_acc + (size_t)s * C.NIMU * 3, *ig = B.imu_gyr + (size_t)s * C.NIMU * 3;
-    double stamp = in_stamp, curTime = stamp + be.td;
-    if (cfg.use_imu) {
-        bool have = be.imu_count > be.imu_head;
-        double back_t = have ? it[(be.imu_count - 1) % C.NIMU] : -1e300;
-        if (!(have && curTime <= back_t)) {
-            if (t == 0) { be.status_code = VIO_NEED_IMU; if (ahead) ahead->declined++; }
-            return;
-        }
-    }
-    const uint16_t *depth = depth_base + (size_t)s * depth_stride;
-    const int fc = be.frame_count;
-    // ---- addFeatureCheckParallax (feature_manager.cpp:56-123)
-    int nobs = ext ? min(ext_n, C.NP) : fe.n_obs, nlm = be.n_lm;
-    const int *o_id = ext ? src.ids + (size_t)s * src.cap : B.obs_id + (size_t)s * C.NP;
-    const double *o = ext ? src.obs + (size_t)s * src.cap * 7 : B.obs + (size_t)s * C.NP * 7;
-    int *flag = c.lm_tmp;         // new-landmark flags per observation (NP <= NL is checked at create)
-    int *offs = c.lm_pidx;        // temporary
-    int tracked = 0;
-    // id -> slot lookup (feature_manager.cpp:66-67 find_if over the list).  The list is NOT sorted by id: a landmark removed by
-    // outlier rejection while the tracker keeps its id is re-appended at the end.  Open-addressing hash table in LDS.
-    extern __shared__ int htab[];  // [2 * HT]: keys, values
-    const int HT = C.lm_hash_size;
-    for (int q = t; q < HT; q += nt) htab[q] = -1;
-    __syncthreads();
-    for (int k = t; k < nlm; k += nt) {
-        int slot = c.lm_order[k], id = c.lm_id[slot];
-        unsigned hsh = ((unsigned)id * 2654435761u) & (unsigned)(HT - 1);
-        while (atomicCAS(&htab[hsh], -1, id) != -1) hsh = (hsh + 1) & (unsigned)(HT - 1);
-        htab[HT + hsh] = slot;
-    }
-    __syncthreads();
-    for (int j = t; j < nobs; j += nt) {
-        const double *p = o + (size_t)j * 7;
-        unsigned short mm = depth[(size_t)min(max((int)p[4], 0), cfg.height - 1) * cfg.width + min(max((int)p[3], 0), cfg.width - 1)];
-        double dmm = mm / 1000.0;
-        int isnew = 0;
-        if (!(0 < dmm && dmm < cfg.depth_min)) {
-            int fid = o_id[j];
-            int found = -1;
-            unsigned hsh = ((unsigned)fid * 2654435761u) & (unsigned)(HT - 1);
-            while (htab[hsh] != -1) {
-                if (htab[hsh] == fid) { found = htab[HT + hsh]; break; }
-                hsh = (hsh + 1) & (unsigned)(HT - 1);
-            }
-            if (found >= 0) {
-                int k = c.lm_nobs[found];
-                if (k <= W) {
-                    double *q = obs_ptr(c, found, c.lm_start[found] + k);
-                    for (int d = 0; d < 7; d++) q[d] = p[d];
-                    q[7] = be.td; q[8] = dmm;
-                    c.lm_nobs[found] = k + 1;
-                }
-                tracked++;
-            } else
-                isnew = 1;
-        }
-        flag[j] = isnew;
-    }
-    __syncthreads();
-    PH(106);
-    {
-        double tr = block_sum((double)tracked, sred);
-        if (t == 0) be.last_track_num = (int)tr;
-    }
-    int nnew = block_scan_flags(flag, nobs, offs, scratch);
-    {
-        int nfree = be.n_free;
-        int can = min(nnew, nfree);
-        for (int j = t; j < nobs; j += nt) {
-            if (!flag[j] || offs[j] >= can) continue;
-            int slot = c.lm_free[nfree - 1 - offs[j]];
-            const double *p = o + (size_t)j * 7;
-            unsigned short mm = depth[(size_t)min(max((int)p[4], 0), cfg.height - 1) * cfg.width + min(max((int)p[3], 0), cfg.width - 1)];
-            c.lm_id[slot] = o_id[j]; c.lm_start[slot] = fc; c.lm_nobs[slot] = 1; c.lm_est[slot] = 0; c.lm_solve[slot] = 0;
-            c.lm_dyn[slot] = 0; c.lm_depth[slot] = -1.0;
-            double *q = obs_ptr(c, slot, fc);
-            for (int d = 0; d < 7; d++) q[d] = p[d];
-            q[7] = be.td; q[8] = mm / 1000.0;
-            c.lm_order[nlm + offs[j]] = slot;
-        }
-        __syncthreads();
-        if (t == 0) {
-            be.n_lm = nlm + can; be.n_free = nfree - can;
-            if (can < nnew) be.overflow |= 1;
-        }
-        __syncthreads();
-        nlm = be.n_lm;
-    }
-    PH(107);
-    // parallax (:100-122, :732-768)
-    {
-        double psum = 0, pnum = 0;
-        if (!(fc < 2 || be.last_track_num < 20)) {
-            for (int k = t; k < nlm; k += nt) {
-                int slot = c.lm_order[k];
-                int st = c.lm_start[slot], no = c.lm_nobs[slot];
-                if (st <= fc - 2 && st + no - 1 >= fc - 1) {
-                    const double *fi = obs_ptr(c, slot, fc - 2), *fj = obs_ptr(c, slot, fc - 1);
-                    double dep_i = fi[2], u_i = fi[0] / dep_i, v_i = fi[1] / dep_i;
-                    double du = u_i - fj[0], dv = v_i - fj[1];
-                    psum += fmax(0.0, sqrt(fmin(du * du + dv * dv, du * du + dv * dv)));
-                    pnum += 1.0;
-                }
-            }
-        }
-        psum = block_sum(psum, sred);
-        pnum = block_sum(pnum, sred);
-        if (t == 0) {
-            bool kf;
-            if (fc < 2 || be.last_track_num < 20) kf = true;
-            else if (pnum == 0) kf = true;
-            else kf = psum / pnum >= cfg.min_parallax_px / cfg.focal_length;
-            be.marginalization_flag = kf ? 0 : 1;
-            be.Headers[fc] = stamp;
-        }
-        __syncthreads();
-    }
-    PH(108);
-    // ---- getIMUInterval + processIMU (estimator.cpp:185-200, 1910-1942, 118-154); VO mode (USE_IMU == 0) has neither.  A steady-state frame whose
-    // interval be_preint_ahead_kernel has integrated already, from exactly these inputs, only files that result.
-    bool imu_here = cfg.use_imu;
-    if (ahead && imu_here) {
-        if (fc == W && fc != 0 && preint_ahead_take(c, *ahead, stamp, curTime, &sh_i[5])) imu_here = false;
-        else if (t == 0) ahead->declined++;
-    }
-    if (imu_here && t < 64) {
-        int head, k;
-        imu_interval_search(it, C.NIMU, be.imu_count, be.prevTime, curTime, be.imu_head, head, k);
-        sh_i[6] = head; sh_i[7] = k;
-    }
-    if (imu_here && t == 0) {
-        const int head = sh_i[6], k = sh_i[7];
-        sh_i[0] = head;          // first sample of the interval
-        sh_i[1] = k - head + 1;  // number of samples incl. the first one with t >= curTime
-        be.imu_head = k;         // that last sample is not popped
-        be.n_imu_frame = sh_i[1];
-        be.imu_frame_head = head;
-        if (!be.initFirstPoseFlag) {  // initFirstIMUPose :1890-1909
-            v3 aver = mk(0, 0, 0);
-            for (int q = 0; q < sh_i[1]; q++) aver = add(aver, ld3(ia + (size_t)((head + q) % C.NIMU) * 3));
-            aver = scl(1.0 / (double)sh_i[1], aver);
-            m3 R0 = g2R(aver);
-            double yaw = R2ypr(R0).x;
-            R0 = mul(ypr2R(mk(-yaw, 0, 0)), R0);
-            stm(be.Rs[0], R0);
-            be.initFirstPoseFlag = 1;
-        }
-    }
-    __syncthreads();
-    if (imu_here) {
-        int head = sh_i[0], n = sh_i[1];
-        PreInt &P = c.pre[be.pre_idx[fc]];
-        if (t == 0) {
-            v3 a0 = ld3(ia + (size_t)(head % C.NIMU) * 3), g0 = ld3(ig + (size_t)(head % C.NIMU) * 3);
-            if (!be.first_imu) { be.first_imu = 1; st3(be.acc_0, a0); st3(be.gyr_0, g0); }
-            if (!P.valid) bf::preint_init(P, ld3(be.acc_0), ld3(be.gyr_0), ld3(be.Bas[fc]), ld3(be.Bgs[fc]));
-        }
-        __syncthreads();
-        if (fc != 0) {
-            // IntegrationBase::push_back + Estimator::processIMU for the n samples of the frame: the pipelined propagation on the ring's
-            // interval, with the world-state recursion of Ps / Rs / Vs[fc] as its side job
-            preint_load(P, pw);
-            __shared__ double pi_fv[PREINT_MANY_LDS_DOUBLES];
-            const PreintRing ring = {it, ia, ig, head, C.NIMU, be.prevTime, curTime, n};
-            WorldStep ws = {ld3(be.acc_0), ld3(be.gyr_0), ld3(be.Ps[fc]), ld3(be.Vs[fc]), ldm(be.Rs[fc]), ld3(be.Bas[fc]), ld3(be.Bgs[fc]), ld3(be.g)};
-            const int nb0 = P.n_buf;
-            PH(111);
-            preint_propagate_many<true>(P, pw, K, n, ring, ws, true, pi_fv);
-            PH(112);
-            if (t == 0 && nb0 + n > VIO_IMU_SLOT_CAP) be.overflow |= 2;
-            if (t == 64) {
-                stm(be.Rs[fc], ws.R); st3(be.Ps[fc], ws.P); st3(be.Vs[fc], ws.V);
-                st3(be.acc_0, ws.a0); st3(be.gyr_0, ws.g0);
-            }
-            __syncthreads();
-        } else if (t == 0) {   // frame 0: no pre-integration yet, acc_0 / gyr_0 follow the samples
-            const int idx = (head + n - 1) % C.NIMU;
-            st3(be.acc_0, ld3(ia + (size_t)idx * 3)); st3(be.gyr_0, ld3(ig + (size_t)idx * 3));
-        }
-        if (fc != 0) preint_store(P, pw);
-        if (t == 0) be.prevTime = curTime;
-        __syncthreads();
-    }
-    PH(109);
-    if constexpr (EXCALIB) {
-        // ---- InitialEXRotation::CalibrationExRotation (estimator.cpp:208-226): before triangulateWithDepth, which already uses a rotation
-        // calibrated in this frame
-        __shared__ ExShared exs;
-        if (be.ex_pending && fc != 0)
-            ex_calibrate(B, c, s, fc, nlm, (double *)(((uintptr_t)htab + 15) & ~(uintptr_t)15), scratch, sred, exs);
-    }
-    // ---- triangulateWithDepth (feature_manager.cpp:386-543); the dynamic initialisation triangulates after its SfM instead (estimator.cpp:921-933)
-    if (!cfg.use_imu && be.solver_flag == 1) init_frame_pose_by_pnp(c, fc, c.res, sred);   // estimator.cpp:321-322 (VO mode, NON_LINEAR only)
-    if (!(cfg.dynamic_init && be.solver_flag == 0)) triangulate_with_depth(c, nlm);
-    __syncthreads();
-    PH(110);
-    if (t == 0) {
-        be.processed = 1;
-        be.frames_processed++;
-        if (be.solver_flag == 0) {
-            // static initialisation solves once the window is full; the dynamic one is decided by the host (vio_abi.hip run_dynamic_init)
-            if (fc == W && !cfg.dynamic_init) { be.do_solve = 1; be.do_marg = 1; }
-        } else { be.do_solve = 1; be.do_marg = 1; }
-        // both initialisations are held while the sequence calibrates (estimator.cpp:236, :275); be_finish slides its window
-        if constexpr (EXCALIB) { if (be.ex_pending) { be.do_solve = 0; be.do_marg = 0; } }
-    }
-}
-template __global__ void be_ingest_kernel<false>(Batch, const uint16_t *, size_t, IngestSrc);
-template __global__ void be_ingest_kernel<true>(Batch, const uint16_t *, size_t, IngestSrc);
+// This unit: be_solve (the phased solver, be_phased.h, and the persistent one below), be_marg and be_finish; be_ingest is be_ingest.hip.  What
+// they share is in be_ctx.h, be_preint.h and be_solve_common.h.  The solvers and the marginalisation stay one unit because apart they compile
+// to other code than together, and so do the factor stage kernels at the end.
+#include "be_solve_common.h"
+#include "be_phased.h"
 
 // ====================================================================================================== be_solve
 namespace {
-
-
-// prior residual row i at parameters X: r0 + J dx; dx assembled in LDS sdx (n)
-__device__ __forceinline__ void prior_dx(const Ctx &c, const Params &X, double *sdx, bool sync = true) {
-    const int t = threadIdx.x, W = c.W;
-    const BeSeq &be = *c.be;
-    if (t <= W + 2) {
-        if (t < W) {
-            double d[6];
-            bf::pose_dx(&X.pose[t * 7], &c.prior_x0[t * 7], d);
-            for (int k = 0; k < 6; k++) sdx[6 * t + k] = be.prior_present[t] ? d[k] : 0.0;
-        } else if (t == W) {
-            for (int k = 0; k < 9; k++) sdx[6 * W + k] = be.prior_present[W] ? X.sb[k] - c.prior_x0[W * 7 + k] : 0.0;
-        } else if (t == W + 1) {
-            double d[6];
-            bf::pose_dx(X.ex, &c.prior_x0[W * 7 + 9], d);
-            for (int k = 0; k < 6; k++) sdx[6 * W + 9 + k] = be.prior_present[W + 1] ? d[k] : 0.0;
-        } else
-            sdx[6 * W + 15] = be.prior_present[W + 2] ? X.td - c.prior_x0[W * 7 + 16] : 0.0;
-    }
-    if (sync) __syncthreads();
-}
-// tangent index of prior slot a
-__device__ __forceinline__ int prior_map(int a, int W) {
-    if (a < 6 * W) return a;                                  // pose k at 6k
-    if (a < 6 * W + 9) return 6 * (W + 1) + (a - 6 * W);     // speed-bias 0
-    if (a < 6 * W + 15) return 15 * (W + 1) + (a - 6 * W - 9);
-    return 15 * (W + 1) + 6;
-}
-
-// Frame-pair geometry of the evaluation point X: a table of 32-double records (be_factors.h PairGeo: A1, A2, M, t) and, as record nrec, ric.
-// The one place that fills such a table; the callers differ in how a record is indexed only: pair(p, i, j) names the frames of record p and
-// says whether the record is wanted (a pair without residuals is left as it is).  Called by every thread of the workgroup (nt of them); ends
-// with the barrier behind which the table may be read.
-template <class Pair>
-__device__ __forceinline__ void stage_pair_geo(const Params &X, double *geo, const int nrec, const int nt, Pair pair) {
-    for (int p = threadIdx.x; p <= nrec; p += nt) {
-        if (p == nrec) { stm(geo + (size_t)p * 32, q2R(mkq(X.ex[6], X.ex[3], X.ex[4], X.ex[5]))); continue; }
-        int i, j;
-        if (!pair(p, i, j)) continue;
-        bf::PairGeo g;
-        bf::pair_geo(&X.pose[i * 7], &X.pose[j * 7], X.ex, g);
-        double *o = geo + (size_t)p * 32;
-        for (int q = 0; q < 9; q++) { o[q] = g.A1[q]; o[9 + q] = g.A2[q]; o[18 + q] = g.M[q]; }
-        o[27] = g.t[0]; o[28] = g.t[1]; o[29] = g.t[2];
-    }
-    __syncthreads();
-}
-// record p = i W1 + j of the square table (be_solve's evaluate, ps_eval): the pairs i < j that have residuals
-__device__ __forceinline__ bool pair_of_square(const Ctx &c, const int W1, const int p, int &i, int &j) {
-    i = p / W1; j = p - i * W1;
-    return i < j && c.pair_start[p + 1] != c.pair_start[p];
-}
-// where a projection record keeps its weighted residual: behind the two Jacobian rows of the 42-double layout (vext, relocalisation), in
-// the last column of each row of the compact 28-double one
-__device__ __forceinline__ void rec_put_wr(double *out, const bool compact, const double wgt, const double *rr) {
-    out[compact ? 13 : 40] = wgt * rr[0];
-    out[compact ? 27 : 41] = wgt * rr[1];
-}
 
 // evaluate every residual at X. withJ: store weighted Jacobians/residuals for assembly. Returns total cost.
 // vext: the extrinsic and / or td block is a variable of this solve.  Otherwise the residual records are written in the compact
@@ -1148,146 +102,6 @@ __device__ __forceinline__ double evaluate(const Ctx &c, const Params &X, const 
     cost = block_sum(cost, sred);
     PH(45);
     return cost;
-}
-
-// pair-block entry index of the packed symmetric 20x20
-__device__ __forceinline__ int sym_idx(int a, int b) {
-    if (a > b) { int x = a; a = b; b = x; }
-    return a * 20 - a * (a - 1) / 2 + (b - a);
-}
-__device__ __forceinline__ int local_of(int a, int i, int j, int W) {
-    // tangent index a within the vision set -> local column of pair (i,j) or -1
-    int np = 6 * (W + 1);
-    if (a < np) {
-        int f = a / 6, d = a - f * 6;
-        if (f == i) return d;
-        if (f == j) return 6 + d;
-        return -1;
-    }
-    int e = a - 15 * (W + 1);
-    return 12 + e;  // ex 0..5 -> 12..17, td (6) -> 18
-}
-
-#define PB_U 8  // k groups (of 4 Jacobian rows) loaded per batch in the frame-pair block phase of assemble
-// compact index of the frame pair (i < j)
-__device__ __forceinline__ int pair_slot(int i, int j, int W1) { return i * W1 - i * (i + 1) / 2 + (j - i - 1); }
-
-// One half of a landmark's coupling row (see assemble): `res` = the landmark's residual Jacobians (42 doubles each, observation k
-// at res + 42 (k - 1)), `row` = its Hpl row.  The arrays never overlap; the restrict qualifiers let the loads of the next
-// residual be issued ahead of the row stores of the current one (the loop is bound by the latency of those loads).
-__device__ __forceinline__ void lm_row(const double *__restrict__ res, double *__restrict__ row, double *__restrict__ Hll,
-                                       double *__restrict__ gl, int half, int st, int kend, int ext_off, int krelo = -1) {
-    // krelo: index of the landmark's relocalisation record (rides behind the regular ones, be_phased.h) or -1.  Its pose_j group is
-    // zero by construction and it has no frame st + k of its own: no pose_j store for it (which would land on whatever columns follow)
-    // residual records are 336 bytes apart and 16-byte aligned: 16-byte loads halve the number of cache-line lookups of this gather
-    if (half == 0) {
-        double si[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll 2
-        for (int k = 1; k < kend; k++) {
-            const double *Jr = res + (size_t)(k - 1) * 42;
-            const double2 *J2 = (const double2 *)Jr;
-            const double l0 = Jr[19], l1 = Jr[39];
-            double a[6], b[6], e[6], f[6];
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                double2 va = J2[q], vb = J2[3 + q], ve = J2[10 + q], vf = J2[13 + q];
-                a[2 * q] = va.x; a[2 * q + 1] = va.y; b[2 * q] = vb.x; b[2 * q + 1] = vb.y;
-                e[2 * q] = ve.x; e[2 * q + 1] = ve.y; f[2 * q] = vf.x; f[2 * q + 1] = vf.y;
-            }
-#pragma unroll
-            for (int d = 0; d < 6; d++) {
-                si[d] += a[d] * l0 + e[d] * l1;
-                if (k != krelo) row[6 * (st + k) + d] = b[d] * l0 + f[d] * l1;
-            }
-        }
-#pragma unroll
-        for (int d = 0; d < 6; d++) row[6 * st + d] = si[d];
-    } else {
-        double se[7] = {0, 0, 0, 0, 0, 0, 0}, hll = 0, gg = 0;
-#pragma unroll 2
-        for (int k = 1; k < kend; k++) {
-            const double *Jr = res + (size_t)(k - 1) * 42;
-            const double2 *J2 = (const double2 *)Jr;
-            double a[8], e[8];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                double2 va = J2[6 + q], ve = J2[16 + q];   // Jr[12..19], Jr[32..39]
-                a[2 * q] = va.x; a[2 * q + 1] = va.y; e[2 * q] = ve.x; e[2 * q + 1] = ve.y;
-            }
-            const double2 rr = J2[20];                      // weighted residual (Jr[40], Jr[41])
-            const double l0 = a[7], l1 = e[7];
-#pragma unroll
-            for (int d = 0; d < 7; d++) se[d] += a[d] * l0 + e[d] * l1;
-            hll += l0 * l0 + l1 * l1;
-            gg += l0 * rr.x + l1 * rr.y;
-        }
-#pragma unroll
-        for (int d = 0; d < 7; d++) row[ext_off + d] = se[d];
-        *Hll = hll;
-        *gl = gg;
-    }
-}
-
-// IMU factor block on the FP64 matrix cores (one wavefront): raw_l = [J_raw | r_whitened] (15 x 31, LDS), M_l = chol(cov)^-1 (15 x 15
-// lower triangular, LDS).  The rows of J are whitened on the fly (x = M J_raw, one output row per lane group) and the 31 x 31 Gram
-// matrix [Jw r]^T [Jw r] is accumulated with K = 16 (row 15 is padding): a00 = rows / cols 0-15, a10 = rows 16-31 x cols 0-15,
-// a11 = rows / cols 16-31, in the C/D layout of v_mfma_f64_16x16x4_f64 (element r of lane (lk, li) = row lk + 4 r, column li).
-__device__ __forceinline__ void imu_block_mfma(const double *raw_l, const double *M_l, int li, int lk, v4f64 &a00, v4f64 &a10, v4f64 &a11) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-        const int kk = 4 * ks + lk;
-        double x0 = 0, x1 = 0;
-        if (kk < 15) {
-            const int c1 = 16 + li;
-            for (int k = 0; k <= kk; k++) {
-                double m = M_l[kk * 15 + k];
-                x0 += m * raw_l[k * 31 + li];
-                if (c1 < 30) x1 += m * raw_l[k * 31 + c1];
-            }
-            if (c1 == 30) x1 = raw_l[kk * 31 + 30];
-        }
-        a00 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, x0, a00, 0, 0, 0);
-        a10 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, x0, a10, 0, 0, 0);
-        a11 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, x1, a11, 0, 0, 0);
-    }
-}
-
-// The same for the compact residual records (28 doubles, no extrinsic / td columns): half 0 = pose columns, half 1 = Hll and gl.
-__device__ __forceinline__ void lm_row_compact(const double *__restrict__ res, double *__restrict__ row, double *__restrict__ Hll,
-                                               double *__restrict__ gl, int half, int st, int kend) {
-    if (half == 0) {
-        double si[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll 2
-        for (int k = 1; k < kend; k++) {
-            const double2 *J2 = (const double2 *)(res + (size_t)(k - 1) * 28);
-            double a[6], b[6], e[6], f[6];
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                double2 va = J2[q], vb = J2[3 + q], ve = J2[7 + q], vf = J2[10 + q];
-                a[2 * q] = va.x; a[2 * q + 1] = va.y; b[2 * q] = vb.x; b[2 * q + 1] = vb.y;
-                e[2 * q] = ve.x; e[2 * q + 1] = ve.y; f[2 * q] = vf.x; f[2 * q + 1] = vf.y;
-            }
-            const double l0 = J2[6].x, l1 = J2[13].x;
-#pragma unroll
-            for (int d = 0; d < 6; d++) {
-                si[d] += a[d] * l0 + e[d] * l1;
-                row[6 * (st + k) + d] = b[d] * l0 + f[d] * l1;
-            }
-        }
-#pragma unroll
-        for (int d = 0; d < 6; d++) row[6 * st + d] = si[d];
-    } else {
-        double hll = 0, gg = 0;
-#pragma unroll 2
-        for (int k = 1; k < kend; k++) {
-            const double2 *J2 = (const double2 *)(res + (size_t)(k - 1) * 28);
-            const double2 p0 = J2[6], p1 = J2[13];   // (inv_depth column, weighted residual) of the two rows
-            hll += p0.x * p0.x + p1.x * p1.x;
-            gg += p0.x * p0.y + p1.x * p1.y;
-        }
-        *Hll = hll;
-        *gl = gg;
-    }
 }
 
 // assemble H (P x P, ld LW), g (vec slot 0), Hpl / Hll / gl from the stored residual Jacobians.
@@ -1519,493 +333,8 @@ __device__ __forceinline__ void assemble(const Batch &B, const Ctx &c, const Par
 
 }  // namespace
 
-namespace {
-// Everything optimization() does before the first evaluation (estimator.cpp:1161-1212, 936-981): static-initialisation extras,
-// vector2double into X, landmark / residual / frame-pair indexing, constness decisions (sh_i[0] = extrinsic variable, sh_i[1] = td
-// variable).  Shared by the persistent solve kernel and the phased solver (ps_setup_kernel).
-// allow_relo: the caller can carry relocalisation factors (phased solver): sh_i[4] returns whether this solve has them
-__device__ __forceinline__ void solve_prologue(const Batch &B, Ctx &c, Params &X, int *scratch, PreWork &pw, int *sh_i, int &F, int &Fa, int &nres,
-                                               const bool allow_relo = false, unsigned *lmkey = nullptr, const int lmkey_cap = 0) {
-    const int t = threadIdx.x, nt = blockDim.x;
-    const vio_config &cfg = c.C->c;
-    BeSeq &be = *c.be;
-    const int W = c.W, W1 = W + 1;
-    const int s = c.s;
-    PH_INIT;
-    // ---- static initialisation extras (estimator.cpp:266-283): solveGyroscopeBias + repropagate (IMU mode only, :264)
-    if (be.solver_flag == 0 && cfg.use_imu) {
-        if (t == 0) {
-            double A[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
-            for (int i = 0; i < W; i++) {
-                int j = i + 1;
-                const PreInt &p = c.pre[be.pre_idx[j]];
-                quat q_ij = R2q(mul(tr(ldm(be.Rs[i])), ldm(be.Rs[j])));
-                m3 tA = bf::get33(p.jac, 15, bf::O_R, bf::O_BG);
-                v3 tb = scl(2.0, qvec(qmul(qinv(mkq(p.dq[0], p.dq[1], p.dq[2], p.dq[3])), q_ij)));
-                m3 AtA = mul(tr(tA), tA);
-                v3 Atb = mul(tr(tA), tb);
-                for (int r = 0; r < 9; r++) A[r] += AtA.a[r];
-                b[0] += Atb.x; b[1] += Atb.y; b[2] += Atb.z;
-            }
-            double M[12];
-            for (int r = 0; r < 3; r++) { for (int q = 0; q < 3; q++) M[r * 4 + q] = A[r * 3 + q]; M[r * 4 + 3] = b[r]; }
-            for (int i = 0; i < 3; i++) {
-                int p = i;
-                for (int r = i + 1; r < 3; r++) if (fabs(M[r * 4 + i]) > fabs(M[p * 4 + i])) p = r;
-                for (int q = 0; q < 4; q++) { double tmp = M[i * 4 + q]; M[i * 4 + q] = M[p * 4 + q]; M[p * 4 + q] = tmp; }
-                if (M[i * 4 + i] == 0) continue;
-                for (int r = i + 1; r < 3; r++) {
-                    double f = M[r * 4 + i] / M[i * 4 + i];
-                    for (int q = i; q < 4; q++) M[r * 4 + q] -= f * M[i * 4 + q];
-                }
-            }
-            double x[3] = {0, 0, 0};
-            for (int i = 2; i >= 0; i--) {
-                double sacc = M[i * 4 + 3];
-                for (int q = i + 1; q < 3; q++) sacc -= M[i * 4 + q] * x[q];
-                x[i] = M[i * 4 + i] != 0 ? sacc / M[i * 4 + i] : 0;
-            }
-            for (int i = 0; i <= W; i++) { be.Bgs[i][0] += x[0]; be.Bgs[i][1] += x[1]; be.Bgs[i][2] += x[2]; }
-        }
-        __syncthreads();
-        repropagate_window(c, pw);
-    }
-
-    // ---- vector2double (estimator.cpp:936-981)
-    if (t <= W) {
-        int i = t;
-        X.pose[i * 7 + 0] = be.Ps[i][0]; X.pose[i * 7 + 1] = be.Ps[i][1]; X.pose[i * 7 + 2] = be.Ps[i][2];
-        quat q = R2q(ldm(be.Rs[i]));
-        X.pose[i * 7 + 3] = q.x; X.pose[i * 7 + 4] = q.y; X.pose[i * 7 + 5] = q.z; X.pose[i * 7 + 6] = q.w;
-        for (int k = 0; k < 3; k++) { X.sb[i * 9 + k] = be.Vs[i][k]; X.sb[i * 9 + 3 + k] = be.Bas[i][k]; X.sb[i * 9 + 6 + k] = be.Bgs[i][k]; }
-    }
-    if (t == W + 1) {
-        X.ex[0] = be.tic[0]; X.ex[1] = be.tic[1]; X.ex[2] = be.tic[2];
-        quat q = R2q(ldm(be.ric));
-        X.ex[3] = q.x; X.ex[4] = q.y; X.ex[5] = q.z; X.ex[6] = q.w;
-        X.td = be.td;
-        for (int k = 0; k < 7; k++) X.relo[k] = be.relo_Pose[k];
-    }
-    // constness (estimator.cpp:1187-1212), decided first because the relocalisation factors borrow the columns of a CONSTANT extrinsic
-    if (t == 0) {
-        double v0 = nrm(ld3(be.Vs[0]));
-        int ex_active;
-        if ((cfg.estimate_extrinsic && be.frame_count == W && v0 > 0.2) || be.openExEstimation) { be.openExEstimation = 1; ex_active = 1; }
-        else ex_active = 0;
-        int td_active = cfg.use_imu && cfg.estimate_td && !(v0 < 0.2);   // no td block without the IMU (estimator.cpp:1204)
-        sh_i[0] = ex_active; sh_i[1] = td_active;
-        // (no solver_flag test, like optimization(): the solve that ends the static initialisation runs with solver_flag still 0 here, and
-        // solve_epilogue consumes the request after it)
-        int relo_on = be.relo_info;
-        if (relo_on && (!allow_relo || !cfg.use_imu)) {
-            // relocalisation on the persistent solver (windows beyond the phased solver's range) and in VO mode (solve_epilogue's VO branch
-            // neither moves relo_Pose nor consumes the request) is not supported: the request is dropped and the frame flagged (overflow
-            // bit 64); optimization() without relocalization_info is what runs
-            relo_on = 0; be.relo_info = 0; be.overflow |= 64;
-        } else if (relo_on && ex_active) {
-            // DEVIATION 15: relo_Pose borrows the six tangent columns of the extrinsic in the reduced system, so the extrinsic is held constant
-            // in the (one) solve that carries relocalisation factors even when ESTIMATE_EXTRINSIC has opened it; openExEstimation stays
-            // latched and the next solve refines it again.  The oracle mirrors this under reference_quirks bit 2 (tests).
-            ex_active = 0; sh_i[0] = 0;
-        }
-        sh_i[4] = relo_on; sh_i[3] = 0;
-    }
-    __syncthreads();
-    const int relo_on = sh_i[4];
-    PH(100);
-    // ---- landmark indexing: in-problem (para_Feature index), variable landmarks, residual list
-    const int nlm = be.n_lm;
-    int *tmpA = c.pair_list, *tmpB = c.pair_list + c.NL;       // scan temporaries (pair_list proper is built afterwards)
-    int *alist = c.pair_list + c.nres_cap - c.NL;              // variable-landmark slots, kept for the whole solve
-    int *plist = c.pair_list + c.nres_cap - 2 * c.NL;          // in-problem landmark slots in list order
-    __syncthreads();
-    for (int k = t; k < nlm; k += nt) tmpA[k] = in_problem(c, c.lm_order[k]) ? 1 : 0;
-    __syncthreads();
-    F = block_scan_flags(tmpA, nlm, tmpB, scratch);
-    for (int k = t; k < nlm; k += nt) {
-        int slot = c.lm_order[k];
-        c.lm_pidx[slot] = tmpA[k] ? tmpB[k] : -1;
-        if (tmpA[k]) { c.feat[tmpB[k]] = 1.0 / c.lm_depth[slot]; plist[tmpB[k]] = slot; }
-    }
-    __syncthreads();
-    // variable landmarks (not SetParameterBlockConstant): estimator.cpp:1278-1298
-    for (int k = t; k < nlm; k += nt) {
-        int slot = c.lm_order[k];
-        tmpA[k] = (c.lm_pidx[slot] >= 0 && !(c.lm_est[slot] == 1 && cfg.fix_depth)) ? 1 : 0;
-    }
-    __syncthreads();
-    Fa = block_scan_flags(tmpA, nlm, tmpB, scratch);
-    for (int k = t; k < nlm; k += nt) {
-        int slot = c.lm_order[k];
-        c.lm_aidx[slot] = tmpA[k] ? tmpB[k] : -1;
-        if (tmpA[k]) alist[tmpB[k]] = slot;
-    }
-    __syncthreads();
-    PH(101);
-    // relocalisation factors (estimator.cpp:1307-1346): in-problem landmarks with start_frame <= relo_frame_local_index whose id is among
-    // the match points (upstream walks both ascending lists with one cursor: the same set); their factor rides as one more residual
-    // record behind the landmark's regular ones, marked res_k = 0
-    for (int k = t; k < nlm; k += nt) {
-        const int slot = c.lm_order[k];
-        int hit = 0;
-        if (relo_on && c.lm_pidx[slot] >= 0 && c.lm_start[slot] <= be.relo_local) {
-            const int id = c.lm_id[slot];
-            int lo = 0, hi = be.relo_nmatch - 1;
-            while (lo <= hi) {
-                const int mid = (lo + hi) >> 1, mi = (int)c.relo_mp[3 * mid + 2];
-                if (mi == id) { hit = 1; c.relo_xy[2 * slot] = c.relo_mp[3 * mid]; c.relo_xy[2 * slot + 1] = c.relo_mp[3 * mid + 1]; break; }
-                if (mi < id) lo = mid + 1; else hi = mid - 1;
-            }
-        }
-        c.lm_relo[slot] = hit;
-        if (hit) atomicAdd(&sh_i[3], 1);
-    }
-    // residual list: (nobs-1) residuals per in-problem landmark, list order (estimator.cpp:1243-1302)
-    for (int k = t; k < nlm; k += nt) { int slot = c.lm_order[k]; tmpA[k] = c.lm_pidx[slot] >= 0 ? c.lm_nobs[slot] - 1 + c.lm_relo[slot] : 0; }
-    __syncthreads();
-    nres = block_scan_flags(tmpA, nlm, tmpB, scratch);
-    const int nres_max = c.nres_cap - 2 * c.NL;
-    if (nres > nres_max) { nres = nres_max; if (t == 0) be.overflow |= 8; }
-    for (int k = t; k < nlm; k += nt) {
-        int slot = c.lm_order[k];
-        int r0 = tmpB[k], cnt = tmpA[k];
-        c.lm_tmp[slot] = r0;  // first residual index of this landmark
-        const int nreg = c.lm_nobs[slot] - 1;
-        for (int q = 0; q < cnt; q++)
-            if (r0 + q < nres) { c.res_lm[r0 + q] = slot; c.res_k[r0 + q] = q < nreg ? q + 1 : 0; }
-    }
-    __syncthreads();
-    PH(102);
-    // frame-pair lists in deterministic (landmark list) order: one wavefront per frame pair walks the in-problem landmarks
-    {
-        const int lane = t & 63, wave = t >> 6, nw = nt >> 6;
-        for (int p = t; p <= W1 * W1; p += nt) c.pair_start[p] = 0;
-        // (round 6) what the walks below need of a landmark -- start frame, observation count, relocalisation mark, first residual index -- packed
-        // into one word of LDS per in-problem landmark: every frame pair walks the whole list twice, W1 W / 2 pairs x F / 64 trips x 2, and from HBM
-        // each trip was a chain of two dependent loads (the slot, then its fields): 214 us of ps_setup at W = 20, 55 at W = 10
-        const bool keys = lmkey != nullptr && F <= lmkey_cap && c.nres_cap < (1 << 19);
-        if (keys)
-            for (int k = t; k < F; k += nt) {
-                const int slot = plist[k];
-                lmkey[k] = (unsigned)c.lm_start[slot] | ((unsigned)c.lm_nobs[slot] << 6) | ((unsigned)(c.lm_relo[slot] ? 1 : 0) << 12) | ((unsigned)c.lm_tmp[slot] << 13);
-            }
-        __syncthreads();
-        auto lm_fields = [&](int k, int &st_, int &no_, int &rl_, int &r0_) {
-            if (keys) { const unsigned key = lmkey[k]; st_ = key & 63u; no_ = (key >> 6) & 63u; rl_ = (key >> 12) & 1u; r0_ = (int)(key >> 13); }
-            else { const int slot = plist[k]; st_ = c.lm_start[slot]; no_ = c.lm_nobs[slot]; rl_ = c.lm_relo[slot]; r0_ = c.lm_tmp[slot]; }
-        };
-        for (int p = wave; p < W1 * W1; p += nw) {
-            int i = p / W1, j = p - i * W1;
-            if (!(i < j)) continue;
-            int cnt = 0;
-            for (int k0 = 0; k0 < F; k0 += 64) {
-                int k = k0 + lane;
-                bool hit = false;
-                bool hit2 = false;   // relocalisation record: listed with the pair (start, start + 1), its pose_j columns are zero
-                if (k < F) {
-                    int st_, no_, rl_, r0_;
-                    lm_fields(k, st_, no_, rl_, r0_);
-                    hit = st_ == i && no_ > j - i && r0_ + (j - i - 1) < nres;
-                    hit2 = relo_on && j == i + 1 && st_ == i && rl_ && r0_ + no_ - 1 < nres;
-                }
-                cnt += __popcll(__ballot(hit)) + __popcll(__ballot(hit2));
-            }
-            if (lane == 0) c.pair_start[p] = cnt;
-        }
-        __syncthreads();
-        PH(103);
-        {
-            // exclusive prefix sum of the W1^2 counts (one thread walking them was 441 dependent loads at W = 20): chunks per thread, Hillis-Steele
-            // over the chunk sums in `scratch` (2 nt ints), as block_scan_flags does
-            const int np = W1 * W1, chunk = (np + nt - 1) / nt, b0 = min(np, t * chunk), e0 = min(np, b0 + chunk);
-            int vals[4], sum = 0;   // chunk <= 4: np <= 441 at W = 20 needs nt >= 111
-            if (chunk <= 4) {
-#pragma unroll
-                for (int q = 0; q < 4; q++) { vals[q] = b0 + q < e0 ? c.pair_start[b0 + q] : 0; sum += vals[q]; }
-                int *cur = scratch, *nxt = scratch + nt;
-                __syncthreads();
-                cur[t] = sum;
-                __syncthreads();
-                for (int off = 1; off < nt; off <<= 1) {
-                    int v = cur[t];
-                    if (t >= off) v += cur[t - off];
-                    nxt[t] = v;
-                    __syncthreads();
-                    int *tmp = cur; cur = nxt; nxt = tmp;
-                }
-                int o = cur[t] - sum;
-#pragma unroll
-                for (int q = 0; q < 4; q++) if (b0 + q < e0) { c.pair_start[b0 + q] = o; o += vals[q]; }
-                if (t == nt - 1) c.pair_start[np] = cur[nt - 1];
-            } else if (t == 0) {
-                int acc = 0;
-                for (int p = 0; p < np; p++) { int v = c.pair_start[p]; c.pair_start[p] = acc; acc += v; }
-                c.pair_start[np] = acc;
-            }
-        }
-        __syncthreads();
-        for (int p = wave; p < W1 * W1; p += nw) {
-            int i = p / W1, j = p - i * W1;
-            if (!(i < j)) continue;
-            int o = c.pair_start[p];
-            for (int k0 = 0; k0 < F; k0 += 64) {
-                int k = k0 + lane;
-                bool hit = false;
-                int r = 0;
-                if (k < F) { int st_, no_, rl_, r0_; lm_fields(k, st_, no_, rl_, r0_); r = r0_ + (j - i - 1); hit = st_ == i && no_ > j - i && r < nres; }
-                unsigned long long m = __ballot(hit);
-                if (hit) c.pair_list[o + __popcll(m & ((1ULL << lane) - 1ULL))] = r;
-                o += __popcll(m);
-            }
-            if (relo_on && j == i + 1)
-                for (int k0 = 0; k0 < F; k0 += 64) {
-                    int k = k0 + lane;
-                    bool hit = false;
-                    int r = 0;
-                    if (k < F) { int st_, no_, rl_, r0_; lm_fields(k, st_, no_, rl_, r0_); r = r0_ + no_ - 1; hit = st_ == i && rl_ && r < nres; }
-                    unsigned long long m = __ballot(hit);
-                    if (hit) c.pair_list[o + __popcll(m & ((1ULL << lane) - 1ULL))] = r;
-                    o += __popcll(m);
-                }
-        }
-        __syncthreads();
-    }
-    PH(104);
-    if (t == 0) {
-        be.n_in_problem = F; be.n_var_landmarks = Fa; be.n_residuals = nres - sh_i[3];   // (f_m_cnt counts the regular factors)
-        be.relo_factors = sh_i[3];
-        be.iterations = 0; be.successful = 0;
-    }
-    __syncthreads();
-}
-
-// double2vector + setDepth + failureDetection after the solve (estimator.cpp:985-1111, feature_manager.cpp:197-223, estimator.cpp:345-353).
-// sdx: >= 12 doubles of LDS scratch.  Shared by the persistent solve kernel and the phased solver (ps_final_kernel).
-__device__ __forceinline__ void solve_epilogue(Ctx &c, const Params &X, double cost, int iters_done, int succ, long long ts0, double *sdx, double *sh_d, int *sh_i) {
-    const int t = threadIdx.x, nt = blockDim.x;
-    const vio_config &cfg = c.C->c;
-    BeSeq &be = *c.be;
-    const int W = c.W, nlm = be.n_lm;
-    // ---- write back flat parameters + double2vector (estimator.cpp:985-1111)
-    if (!cfg.use_imu) {
-        // VO mode (estimator.cpp:1060-1067, 1093, 1109): poses straight from the parameters, no gauge fix, nothing else handed back
-        if (t == 0) {
-            be.final_cost = cost; be.iterations = iters_done; be.successful = succ;
-            be.iter_total += iters_done; be.solve_total++;
-            be.dbg[4] = (int)(VIO_CLOCK() - ts0);
-        }
-        if (t <= W) {
-            const int i = t;
-            for (int k = 0; k < 7; k++) be.para_Pose[i][k] = X.pose[i * 7 + k];
-            stm(be.Rs[i], q2R(qnormalized(mkq(X.pose[i * 7 + 6], X.pose[i * 7 + 3], X.pose[i * 7 + 4], X.pose[i * 7 + 5]))));
-            be.Ps[i][0] = X.pose[i * 7]; be.Ps[i][1] = X.pose[i * 7 + 1]; be.Ps[i][2] = X.pose[i * 7 + 2];
-        }
-    } else {
-    if (t == 0) {
-        be.final_cost = cost; be.iterations = iters_done; be.successful = succ;
-        be.iter_total += iters_done; be.solve_total++;
-        be.dbg[4] = (int)(VIO_CLOCK() - ts0);
-        v3 origin_R0 = R2ypr(ldm(be.Rs[0]));
-        v3 origin_P0 = ld3(be.Ps[0]);
-        quat q0 = mkq(X.pose[6], X.pose[3], X.pose[4], X.pose[5]);
-        v3 origin_R00 = R2ypr(q2R(q0));
-        double y_diff = origin_R0.x - origin_R00.x;
-        m3 rot_diff = ypr2R(mk(y_diff, 0, 0));
-        if (fabs(fabs(origin_R0.y) - 90) < 1.0 || fabs(fabs(origin_R00.y) - 90) < 1.0) rot_diff = mul(ldm(be.Rs[0]), tr(q2R(q0)));
-        sh_d[0] = 0;
-        for (int q = 0; q < 9; q++) sdx[q] = rot_diff.a[q];
-        sdx[9] = origin_P0.x; sdx[10] = origin_P0.y; sdx[11] = origin_P0.z;
-    }
-    __syncthreads();
-    // para_Pose as the solve leaves it (estimator.h:139): what Estimator::setReloFrame copies into relo_Pose when no marginalisation
-    // re-runs vector2double afterwards (marg_body overwrites it in that case, like optimization() does)
-    if (t <= W) for (int k = 0; k < 7; k++) be.para_Pose[t][k] = X.pose[t * 7 + k];
-    if (t <= W) {
-        int i = t;
-        m3 rot_diff = ldm(sdx);
-        v3 origin_P0 = mk(sdx[9], sdx[10], sdx[11]);
-        quat qi = qnormalized(mkq(X.pose[i * 7 + 6], X.pose[i * 7 + 3], X.pose[i * 7 + 4], X.pose[i * 7 + 5]));
-        stm(be.Rs[i], mul(rot_diff, q2R(qi)));
-        st3(be.Ps[i], add(mul(rot_diff, mk(X.pose[i * 7] - X.pose[0], X.pose[i * 7 + 1] - X.pose[1], X.pose[i * 7 + 2] - X.pose[2])), origin_P0));
-        st3(be.Vs[i], mul(rot_diff, mk(X.sb[i * 9], X.sb[i * 9 + 1], X.sb[i * 9 + 2])));
-        for (int k = 0; k < 3; k++) { be.Bas[i][k] = X.sb[i * 9 + 3 + k]; be.Bgs[i][k] = X.sb[i * 9 + 6 + k]; }
-        // updateLatestStates (estimator.cpp:1768-1776): latest_Bg feeds predictMotion of the next frame, whose front-end may
-        // start as soon as this kernel is done (overlapping the marginalisation)
-        // (the frame that completes the DYNAMIC initialisation returns without updateLatestStates, estimator.cpp:241-252)
-        if (i == W && !be.init_frame) for (int k = 0; k < 3; k++) be.latest_Bg[k] = X.sb[i * 9 + 6 + k];
-    }
-    if (t == W + 1) {
-        be.tic[0] = X.ex[0]; be.tic[1] = X.ex[1]; be.tic[2] = X.ex[2];
-        stm(be.ric, q2R(qnormalized(mkq(X.ex[6], X.ex[3], X.ex[4], X.ex[5]))));
-        if (cfg.estimate_td) be.td = X.td;
-    }
-    __syncthreads();
-    if (t == 0 && be.relo_info) {
-        // "relative info between two loop frame" (estimator.cpp:1034-1056): the relocalisation pose through the same gauge fix, the drift
-        // between this odometry frame and the old keyframe's world (yaw + translation), the relative pose the pose graph stores
-        const m3 rot_diff = ldm(sdx);
-        const v3 origin_P0 = mk(sdx[9], sdx[10], sdx[11]);
-        const m3 relo_r = mul(rot_diff, q2R(qnormalized(mkq(X.relo[6], X.relo[3], X.relo[4], X.relo[5]))));
-        const v3 relo_t = add(mul(rot_diff, mk(X.relo[0] - X.pose[0], X.relo[1] - X.pose[1], X.relo[2] - X.pose[2])), origin_P0);
-        const m3 prev_r = ldm(be.prev_relo_r);
-        const double drift_yaw = R2ypr(prev_r).x - R2ypr(relo_r).x;
-        const m3 dr = ypr2R(mk(drift_yaw, 0, 0));
-        stm(be.drift_correct_r, dr);
-        st3(be.drift_correct_t, sub(ld3(be.prev_relo_t), mul(dr, relo_t)));
-        const int li = be.relo_local;
-        const m3 Rl = ldm(be.Rs[li]);
-        st3(be.relo_relative_t, mul(tr(relo_r), sub(ld3(be.Ps[li]), relo_t)));
-        const quat qrel = R2q(mul(tr(relo_r), Rl));
-        be.relo_relative_q[0] = qrel.w; be.relo_relative_q[1] = qrel.x; be.relo_relative_q[2] = qrel.y; be.relo_relative_q[3] = qrel.z;
-        const double a = R2ypr(Rl).x - R2ypr(relo_r).x;   // Utility::normalizeAngle (utility.h:131-139), degrees
-        be.relo_relative_yaw = a > 0 ? a - 360.0 * floor((a + 180.0) / 360.0) : a + 360.0 * floor((-a + 180.0) / 360.0);
-        for (int k = 0; k < 7; k++) be.relo_Pose[k] = X.relo[k];
-        be.relo_info = 0;
-    }
-    }   // IMU mode
-    // setDepth (feature_manager.cpp:197-223)
-    for (int k = t; k < nlm; k += nt) {
-        int slot = c.lm_order[k];
-        int pi = c.lm_pidx[slot];
-        if (pi < 0) continue;
-        double d = 1.0 / c.feat[pi];
-        c.lm_depth[slot] = d;
-        c.lm_solve[slot] = d < 0 ? 2 : 1;
-    }
-    __syncthreads();
-    // failureDetection + clearState() / setParameter() (estimator.cpp:345-353, 1113-1159, 43-116, 15-41).  The reference runs it
-    // after optimization() (solve + marginalisation) and throws the whole state away when it fires, so nothing the marginalisation
-    // produces survives a reboot: it is decided HERE, before the host records ev_solve, because the reset rewrites imu_head / td /
-    // ric / latest_Bg, which the next frame's front-end (fe_begin) and the IMU scatter kernel read as soon as this kernel is done.
-    if (be.solver_flag == 1 && !be.init_frame) {
-        if (t == 0) {
-            int fail = 0;
-            if (nrm(ld3(be.Bas[W])) > 2.5) fail = 1;
-            if (nrm(ld3(be.Bgs[W])) > 1.0) fail = 1;
-            v3 tmpP = ld3(be.Ps[W]);
-            if (nrm(sub(tmpP, ld3(be.last_P))) > 5) fail = 1;
-            if (fabs(tmpP.z - be.last_P[2]) > 1) fail = 1;
-            sh_i[0] = fail;
-        }
-        __syncthreads();
-        if (sh_i[0]) {
-            for (int k = t; k < c.NL; k += nt) c.lm_free[k] = c.NL - 1 - k;
-            if (t == 0) {
-                for (int i = 0; i <= W + 1; i++) c.pre[i].valid = 0;
-                for (int i = 0; i <= W; i++) {
-                    for (int k = 0; k < 3; k++) { be.Ps[i][k] = 0; be.Vs[i][k] = 0; be.Bas[i][k] = 0; be.Bgs[i][k] = 0; }
-                    stm(be.Rs[i], eye());
-                    be.Headers[i] = 0;
-                    be.pre_idx[i] = i;
-                }
-                // setParameter() restores the sequence's calibration (Batch::cal).  (estimate_extrinsic = 2: RIC[0], the calibrated rotation,
-                // and TIC[0] = 0 -- the table's tic on such a handle)
-                const vio_calibration &K = *c.K;
-                for (int k = 0; k < 9; k++) be.ric[k] = cfg.estimate_extrinsic == 2 ? be.ex_ric[k] : K.ric[k];
-                for (int k = 0; k < 3; k++) { be.tic[k] = K.tic[k]; be.latest_Bg[k] = 0; }
-                be.td = K.td;
-                be.g[0] = 0; be.g[1] = 0; be.g[2] = K.g_norm;   // setParameter(): g = G (estimator.cpp:26)
-                be.first_imu = 0; be.frame_count = 0; be.solver_flag = 0; be.openExEstimation = 0; be.has_prior = 0;
-                be.initFirstPoseFlag = 0; be.prevTime = -1; be.n_lm = 0; be.n_free = c.NL; be.ring_base = 0;
-                be.imu_head = be.imu_count_ingest;  // clearState() empties imu_buf (samples pushed for the next frame while this one was
-                                                     // being optimised - tracker lag 1 - arrived after the reset)
-                be.relo_info = 0;   // relocalization_info = false (estimator.cpp:96)
-                be.reboot_count++;
-                be.status_code = VIO_REBOOTED;
-                be.rebooted = 1;
-                be.do_marg = 0;
-                be.overflow = 0;
-            }
-        }
-    }
-}
-
-}  // namespace
-
-// LDSA: the reduced system A, b, b_r and the frame blocks G_j live in the dynamic LDS (kernels.h marg_resident_lds_bytes) instead of c.margA / margB /
-// margV / vec / pairblk; LT: the window slide works on LDS copies of the landmark tables.  Compile-time, so that every loop addresses one address space.
-// PART (kernels.h MargSnap): 0 = the whole stage, 1 = what must precede the window slide (be_marg_pre_kernel), 2 = the algebra from the hand-over
-// record (be_marg_alg_kernel); msnap / mlist: that record and the list of this sequence (PART != 0)
-template <bool EXACT, bool LDSA, int PART = 0> __device__ void marg_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem_marg,
-                                                                         MargSnap *msnap = nullptr, int *mlist = nullptr);
-template <bool LT> __device__ void finish_body(const Batch &B, int s, int *scratch, PreWork &pw, unsigned char *smem_marg);
-
 // solve -> marginalise -> window slide for one sequence per workgroup (1024 threads); fusing the three stages makes the
 // step time the maximum over sequences of the *sum* of the stage times instead of the sum of per-stage maxima.
-__device__ __forceinline__ void solve_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem, PreWork &pw);
-
-__global__ __launch_bounds__(1024) void be_solve_kernel(Batch B) {
-    const int s = blockIdx.x + B.s0;
-    __shared__ int scratch[2 * 1024 + 8];
-    __shared__ double sred[64];
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    PreWork &pw = *(PreWork *)(smem + 16 * ((B.cfg->LW * 8 + 15) / 16));  // aliases the work region (used before it)
-    solve_body(B, s, scratch, sred, smem, pw);
-}
-// the same body compiled for 512 threads: 256 VGPRs per lane instead of 128 (no scratch spills), half the waves
-__global__ __launch_bounds__(512) void be_solve_kernel_512(Batch B) {
-    const int s = blockIdx.x + B.s0;
-    __shared__ int scratch[2 * 1024 + 8];
-    __shared__ double sred[64];
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    PreWork &pw = *(PreWork *)(smem + 16 * ((B.cfg->LW * 8 + 15) / 16));
-    solve_body(B, s, scratch, sred, smem, pw);
-}
-// marginalisation + window slide: 512 threads (measured: 2.9 ms against 3.5 ms with 256; the QL phase is one wavefront either way)
-__global__ __launch_bounds__(512) void be_marg_kernel(Batch B) {
-    const int s = blockIdx.x + B.s0;
-    __shared__ int scratch[2 * 512 + 8];
-    __shared__ double sred[64];
-    __shared__ PreWork pw;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    marg_body<false, true>(B, s, scratch, sred, smem);
-    __syncthreads();
-    finish_body<true>(B, s, scratch, pw, smem);
-}
-// VIO_MARG_SPLIT (kernels.h): the same stage as two launches.  The first holds whatever touches window state the next frame's be_ingest / ps_setup
-// share -- they follow it on the front-end stream, beside the second, which is the algebra and nothing else.
-__global__ __launch_bounds__(512) void be_marg_pre_kernel(Batch B, MargSnap *snap, int *mlist) {
-    const int s = blockIdx.x + B.s0;
-    __shared__ int scratch[2 * 512 + 8];
-    __shared__ double sred[64];
-    __shared__ PreWork pw;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    marg_body<false, true, 1>(B, s, scratch, sred, smem, snap + s, mlist + (size_t)s * 2 * B.gNL);
-    __syncthreads();
-    finish_body<true>(B, s, scratch, pw, smem);
-}
-__global__ __launch_bounds__(512) void be_marg_alg_kernel(Batch B, MargSnap *snap, const int *mlist) {
-    const int s = blockIdx.x + B.s0;
-    __shared__ int scratch[2 * 512 + 8];
-    __shared__ double sred[64];
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    marg_body<false, true, 2>(B, s, scratch, sred, smem, snap + s, const_cast<int *>(mlist) + (size_t)s * 2 * B.gNL);
-}
-// the same stage with the reduced system, the frame blocks and the landmark tables in HBM scratch (rounds 1 - 6): windows whose system does not fit
-// the workgroup's LDS (W = 12 and up) and VIO_MARG_LDS = 0
-__global__ __launch_bounds__(512) void be_marg_hbm_kernel(Batch B) {
-    const int s = blockIdx.x + B.s0;
-    __shared__ int scratch[2 * 512 + 8];
-    __shared__ double sred[64];
-    __shared__ PreWork pw;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    marg_body<false, false>(B, s, scratch, sred, smem);
-    __syncthreads();
-    finish_body<false>(B, s, scratch, pw, smem);
-}
-// vio_config.marg_exact: the same stage with the marginalisation of marginalization_factor.cpp:281-315 followed literally (its own kernel so
-// that the hot kernel's registers / LDS are untouched by the parity instrument)
-__global__ __launch_bounds__(512) void be_marg_exact_kernel(Batch B) {
-    const int s = blockIdx.x + B.s0;
-    __shared__ int scratch[2 * 512 + 8];
-    __shared__ double sred[64];
-    __shared__ PreWork pw;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    marg_body<true, false>(B, s, scratch, sred, smem);
-    __syncthreads();
-    finish_body<false>(B, s, scratch, pw, smem);
-}
-
 __device__ __forceinline__ void solve_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem, PreWork &pw) {
     const int t = threadIdx.x, nt = blockDim.x;
     Ctx c = make_ctx(B, s);
@@ -2570,8 +899,12 @@ __device__ __forceinline__ bool marg_certificate(const double *Pinv, int md, int
     return certified;
 }
 
-template <bool EXACT, bool LDSA, int PART> __device__ void marg_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem_marg,
-                                                                     MargSnap *msnap, int *mlist) {
+// LDSA: the reduced system A, b, b_r and the frame blocks G_j live in the dynamic LDS (kernels.h marg_resident_lds_bytes) instead of c.margA / margB /
+// margV / vec / pairblk; LT: the window slide works on LDS copies of the landmark tables.  Compile-time, so that every loop addresses one address space.
+// PART (kernels.h MargSnap): 0 = the whole stage, 1 = what must precede the window slide (be_marg_pre_kernel), 2 = the algebra from the hand-over
+// record (be_marg_alg_kernel); msnap / mlist: that record and the list of this sequence (PART != 0)
+template <bool EXACT, bool LDSA, int PART = 0> __device__ void marg_body(const Batch &B, int s, int *scratch, double *sred, unsigned char *smem_marg,
+                                                                     MargSnap *msnap = nullptr, int *mlist = nullptr) {
     static_assert(!(EXACT && LDSA), "the literal marginalisation keeps its system in HBM");
     static_assert(PART == 0 || !EXACT, "the split runs the default marginalisation only");
     const int t = threadIdx.x, nt = blockDim.x;
@@ -3435,41 +1768,76 @@ template <bool LT> __device__ void finish_body(const Batch &B, int s, int *scrat
     PH(30);
 }
 
-// ====================================================================================================== dynamic init hand-over
-// After a successful host-side initialStructure (dyninit_host.cpp) the host has written Ps / Rs / Vs / Bgs / Bas / g of sequence
-// `seq`: re-propagate the window pre-integrations at the new gyroscope bias (estimator.cpp:829-836) and triangulate with the new
-// poses (solveOdometry -> triangulateWithDepth, :921-933).  The regular be_solve / be_marg launches follow.
-// `samples` = (dt, acc[3], gyr[3]) of every IMU step of window slot j in [offs[j], offs[j + 1]), rebuilt by the host from its mirror of
-// all_image_frame: slots that absorbed dropped frames (MARGIN_SECOND_NEW while INITIAL, estimator.cpp:1651-1687) hold more steps than
-// the per-slot sample buffer on the device keeps (the reference's buffers are unbounded vectors).
-__global__ __launch_bounds__(256) void be_dyn_finalize_kernel(Batch B, int seq, const double *samples, const int *offs) {
+__global__ __launch_bounds__(1024) void be_solve_kernel(Batch B) {
+    const int s = blockIdx.x + B.s0;
+    __shared__ int scratch[2 * 1024 + 8];
+    __shared__ double sred[64];
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PreWork &pw = *(PreWork *)(smem + 16 * ((B.cfg->LW * 8 + 15) / 16));  // aliases the work region (used before it)
+    solve_body(B, s, scratch, sred, smem, pw);
+}
+// the same body compiled for 512 threads: 256 VGPRs per lane instead of 128 (no scratch spills), half the waves
+__global__ __launch_bounds__(512) void be_solve_kernel_512(Batch B) {
+    const int s = blockIdx.x + B.s0;
+    __shared__ int scratch[2 * 1024 + 8];
+    __shared__ double sred[64];
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    PreWork &pw = *(PreWork *)(smem + 16 * ((B.cfg->LW * 8 + 15) / 16));
+    solve_body(B, s, scratch, sred, smem, pw);
+}
+// marginalisation + window slide: 512 threads (measured: 2.9 ms against 3.5 ms with 256; the QL phase is one wavefront either way)
+__global__ __launch_bounds__(512) void be_marg_kernel(Batch B) {
+    const int s = blockIdx.x + B.s0;
+    __shared__ int scratch[2 * 512 + 8];
+    __shared__ double sred[64];
     __shared__ PreWork pw;
-    Ctx c = make_ctx(B, seq);
-    BeSeq &be = *c.be;
-    const vio_config &cfg = c.C->c;
-    const int t = threadIdx.x, nt = blockDim.x, W = c.W;
-    for (int j = 0; j <= W; j++) {
-        PreInt &p = c.pre[be.pre_idx[j]];
-        if (!p.valid) continue;
-        if (t == 0) {
-            v3 la = ld3(p.lin_acc), lg = ld3(p.lin_gyr);
-            p.sum_dt = 0;
-            st3(p.acc0, la); st3(p.gyr0, lg);
-            p.dp[0] = p.dp[1] = p.dp[2] = 0; p.dv[0] = p.dv[1] = p.dv[2] = 0;
-            p.dq[0] = 1; p.dq[1] = p.dq[2] = p.dq[3] = 0;
-            p.lin_ba[0] = p.lin_ba[1] = p.lin_ba[2] = 0;
-            st3(p.lin_bg, ld3(be.Bgs[j]));
-        }
-        for (int i = t; i < 225; i += nt) { pw.J[i] = ((i / 15) == (i % 15)) ? 1.0 : 0.0; pw.Pm[i] = 0; }
-        __syncthreads();
-        for (int q = offs[j]; q < offs[j + 1]; q++) {
-            const double *sm = samples + (size_t)q * 7;
-            preint_propagate(p, pw, *c.K, sm[0], ld3(sm + 1), ld3(sm + 4));
-        }
-        preint_store(p, pw);
-    }
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    marg_body<false, true>(B, s, scratch, sred, smem);
     __syncthreads();
-    triangulate_with_depth(c, be.n_lm);
+    finish_body<true>(B, s, scratch, pw, smem);
+}
+// VIO_MARG_SPLIT (kernels.h): the same stage as two launches.  The first holds whatever touches window state the next frame's be_ingest / ps_setup
+// share -- they follow it on the front-end stream, beside the second, which is the algebra and nothing else.
+__global__ __launch_bounds__(512) void be_marg_pre_kernel(Batch B, MargSnap *snap, int *mlist) {
+    const int s = blockIdx.x + B.s0;
+    __shared__ int scratch[2 * 512 + 8];
+    __shared__ double sred[64];
+    __shared__ PreWork pw;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    marg_body<false, true, 1>(B, s, scratch, sred, smem, snap + s, mlist + (size_t)s * 2 * B.gNL);
+    __syncthreads();
+    finish_body<true>(B, s, scratch, pw, smem);
+}
+__global__ __launch_bounds__(512) void be_marg_alg_kernel(Batch B, MargSnap *snap, const int *mlist) {
+    const int s = blockIdx.x + B.s0;
+    __shared__ int scratch[2 * 512 + 8];
+    __shared__ double sred[64];
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    marg_body<false, true, 2>(B, s, scratch, sred, smem, snap + s, const_cast<int *>(mlist) + (size_t)s * 2 * B.gNL);
+}
+// the same stage with the reduced system, the frame blocks and the landmark tables in HBM scratch (rounds 1 - 6): windows whose system does not fit
+// the workgroup's LDS (W = 12 and up) and VIO_MARG_LDS = 0
+__global__ __launch_bounds__(512) void be_marg_hbm_kernel(Batch B) {
+    const int s = blockIdx.x + B.s0;
+    __shared__ int scratch[2 * 512 + 8];
+    __shared__ double sred[64];
+    __shared__ PreWork pw;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    marg_body<false, false>(B, s, scratch, sred, smem);
+    __syncthreads();
+    finish_body<false>(B, s, scratch, pw, smem);
+}
+// vio_config.marg_exact: the same stage with the marginalisation of marginalization_factor.cpp:281-315 followed literally (its own kernel so
+// that the hot kernel's registers / LDS are untouched by the parity instrument)
+__global__ __launch_bounds__(512) void be_marg_exact_kernel(Batch B) {
+    const int s = blockIdx.x + B.s0;
+    __shared__ int scratch[2 * 512 + 8];
+    __shared__ double sred[64];
+    __shared__ PreWork pw;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    marg_body<true, false>(B, s, scratch, sred, smem);
+    __syncthreads();
+    finish_body<false>(B, s, scratch, pw, smem);
 }
 
 // stage test of the literal marginalisation (kernels.h MargLiteralStage): marg_exact_finish / marg_literal_prior / marg_certificate as be_marg_exact_kernel
@@ -3496,77 +1864,7 @@ __global__ __launch_bounds__(512) void be_stage_marg_literal_kernel(MargLiteralS
     if (t == 0) { a.scal[0] = be.prior_c0; a.info[1] = be.dbg[0]; a.info[2] = be.dbg[2]; a.info[3] = be.dbg[4]; }
 }
 
-// stage test of the device solvePnP: par6 = (rvec, tvec) in / out; trace4 (may be null) = outer iterations, lambda escalations, final
-// lambda_lg10, all six parameters finite
-__global__ __launch_bounds__(256) void be_stage_pnp_kernel(const double *pts, int n, double *par6, int *trace4) {
-    __shared__ double sh_par[6], sh_prev[6], sw[256];
-    if (threadIdx.x < 6) sh_par[threadIdx.x] = par6[threadIdx.x];
-    __syncthreads();
-    pnp_refine_block(pts, n, sh_par, sh_prev, sw, trace4);
-    if (threadIdx.x < 6) par6[threadIdx.x] = sh_par[threadIdx.x];
-    if (trace4 && threadIdx.x == 0) {
-        bool fin = true;
-        for (int i = 0; i < 6; i++) fin = fin && isfinite(sh_par[i]);
-        trace4[3] = fin ? 1 : 0;
-    }
-}
-// cv::Rodrigues as the solve uses it, one thread per item (vio_stage_rodrigues): mode 0 r[3] -> R[9], dR/dr[27]; mode 1 R[9] -> r[3]
-__global__ void be_stage_rodrigues_kernel(int mode, int n, const double *in, double *out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (mode == 0) {
-        const v3 r = ld3(in + 3 * (size_t)i);
-        const m3 Rm = pnp_rodrigues(r);
-        m3 dR[3];
-        pnp_rodrigues_jac(r, Rm, dR);
-        double *o = out + 36 * (size_t)i;
-        stm(o, Rm);
-        for (int k = 0; k < 3; k++) stm(o + 9 + 9 * k, dR[k]);
-    } else
-        st3(out + 3 * (size_t)i, pnp_rodrigues_inv(ldm(in + 9 * (size_t)i)));
-}
-
-#include "be_phased.h"
-
 // ====================================================================================================== stage tests
-// IntegrationBase::push_back x n followed by IMUFactor::Evaluate, through the same device code the pipeline uses.
-__global__ __launch_bounds__(256) void be_stage_imu_kernel(vio_config cfg, PreInt *P, int n, const double *dt, const double *acc,
-                                                            const double *gyr, const double *par /*pi7 sbi9 pj7 sbj9*/, double g_norm,
-                                                            double *preint_out, double *r15, double *J480) {
-    __shared__ PreWork pw;
-    const int t = threadIdx.x;
-    preint_load(*P, pw);
-    for (int q = 0; q < n; q++) preint_propagate(*P, pw, cfg, dt[q], ld3(acc + 3 * q), ld3(gyr + 3 * q));
-    preint_store(*P, pw);
-    if (t == 0) {
-        PreInt &p = *P;
-        preint_out[0] = p.dp[0]; preint_out[1] = p.dp[1]; preint_out[2] = p.dp[2];
-        for (int k = 0; k < 4; k++) preint_out[3 + k] = p.dq[k];
-        preint_out[7] = p.dv[0]; preint_out[8] = p.dv[1]; preint_out[9] = p.dv[2];
-        preint_out[10] = p.sum_dt;
-        for (int k = 0; k < 225; k++) { preint_out[11 + k] = p.jac[k]; preint_out[236 + k] = p.cov[k]; }
-        double raw[15], Jr[450];
-        v3 G = mk(0, 0, g_norm);
-        bf::imu_raw_residual(p, G, par, par + 7, par + 16, par + 23, raw);
-        bf::imu_raw_jacobian(p, G, par, par + 7, par + 16, par + 23, Jr);
-        for (int r = 0; r < 15; r++) {
-            double sacc = 0;
-            for (int k = 0; k <= r; k++) sacc += p.sqrt_info[r * 15 + k] * raw[k];
-            r15[r] = sacc;
-        }
-        // whitened Jacobians in the reference's global layout: 15x7, 15x9, 15x7, 15x9 (7th pose column = 0)
-        for (int r = 0; r < 15; r++)
-            for (int col = 0; col < 30; col++) {
-                double sacc = 0;
-                for (int k = 0; k <= r; k++) sacc += p.sqrt_info[r * 15 + k] * Jr[k * 30 + col];
-                if (col < 6) J480[r * 7 + col] = sacc;
-                else if (col < 15) J480[105 + r * 9 + (col - 6)] = sacc;
-                else if (col < 21) J480[240 + r * 7 + (col - 15)] = sacc;
-                else J480[345 + r * 9 + (col - 21)] = sacc;
-            }
-        for (int r = 0; r < 15; r++) { J480[r * 7 + 6] = 0; J480[240 + r * 7 + 6] = 0; }
-    }
-}
 __global__ void be_stage_projection_kernel(vio_config cfg, const double *in /*pi7 pj7 ex7 inv_dep td oi9 oj9*/, int use_td, int form, double *r2, double *J46) {
     if (threadIdx.x != 0) return;
     // form 0: the frame-pair formulation the solver uses (evaluate()); form 1: bf::eval_projection, the per-residual form used by the
@@ -3590,30 +1888,6 @@ __global__ void be_stage_projection_kernel(vio_config cfg, const double *in /*pi
 // The IMU factor exactly as evaluate() + assemble() process it in the solver: raw residual whitened by thread 0, the four raw
 // Jacobian column groups by imu_raw_jacobian_part, then [Jw r]^T [Jw r] on the matrix cores (imu_block_mfma).  One wavefront.
 // G961: the 31 x 31 Gram matrix, row-major, columns = pose_i(6) speedbias_i(9) pose_j(6) speedbias_j(9) | r.
-// InitialEXRotation::solveRelativeR on one set of correspondences (vio_stage_relative_r): corres6[n][6] = (x, y, z) in frame l, (x, y, z) in
-// frame r; grid 1, 256 threads, dynamic LDS 40 n + 64 bytes.  The same device code as the calibration phase of be_ingest<true>.
-__global__ __launch_bounds__(256) void be_stage_relative_r_kernel(int n, const double *corres6, double *R9, int *detail8) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_rr[];
-    __shared__ ExShared S;
-    double *X1 = (double *)smem_rr, *Y1 = X1 + n, *X2 = Y1 + n, *Y2 = X2 + n;
-    int *st = (int *)(Y2 + n);
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {   // cv::Point2f(corres[i].first(0), corres[i].first(1)) ...
-        X1[i] = (double)(float)corres6[6 * i]; Y1[i] = (double)(float)corres6[6 * i + 1];
-        X2[i] = (double)(float)corres6[6 * i + 3]; Y2[i] = (double)(float)corres6[6 * i + 4];
-    }
-    __syncthreads();
-    ex_relative_r(n, X1, Y1, X2, Y2, st, S);
-    if (threadIdx.x < 9) R9[threadIdx.x] = S.Rout[threadIdx.x];
-    if (detail8 && threadIdx.x == 0) {   // (S.R.maxGood and the votes are defined only when the RANSAC ran / a model was found)
-        const bool ran = n >= 9, ok = ran && S.ok;
-        detail8[0] = ok ? 1 : 0;
-        detail8[1] = ran ? S.R.maxGood : 0;
-        for (int k = 0; k < 4; k++) detail8[2 + k] = ok ? S.cnt[k] : 0;
-        detail8[6] = ok ? S.win : 0;
-        detail8[7] = ok ? S.flip : 0;
-    }
-}
-
 __global__ __launch_bounds__(64) void be_stage_imu_block_kernel(const PreInt *P, const double *par /*pi7 sbi9 pj7 sbj9*/, double g_norm, double *G961) {
     __shared__ double raw_l[472], M_l[232];
     const int lane = threadIdx.x;
@@ -3645,51 +1919,6 @@ __global__ __launch_bounds__(64) void be_stage_imu_block_kernel(const PreInt *P,
     }
 }
 
-// out686 of the pre-integration harnesses = delta_p(3) delta_q(wxyz) delta_v(3) sum_dt jacobian(225) covariance(225) sqrt_info(225)
-__device__ __forceinline__ void stage_preint_out(const PreInt &p, double *out686) {
-    if (threadIdx.x == 0) {
-        out686[0] = p.dp[0]; out686[1] = p.dp[1]; out686[2] = p.dp[2];
-        for (int k = 0; k < 4; k++) out686[3 + k] = p.dq[k];
-        out686[7] = p.dv[0]; out686[8] = p.dv[1]; out686[9] = p.dv[2];
-        out686[10] = p.sum_dt;
-    }
-    for (int k = threadIdx.x; k < 225; k += blockDim.x) { out686[11 + k] = p.jac[k]; out686[236 + k] = p.cov[k]; out686[461 + k] = p.sqrt_info[k]; }
-}
-// The two propagation routines of the pipeline on one sample list, for comparison with each other and with the definition: mode 0 = n calls
-// of preint_propagate (be_dyn_finalize, be_marg's repropagation), 1 = preint_propagate_many(append = false), 2 = the same with append = true
-// (the MARGIN_SECOND_NEW merge: the samples are also filed into P's buffers, n_buf saturating at VIO_IMU_SLOT_CAP).  preint_store refreshes
-// sqrt_info as everywhere.
-__global__ __launch_bounds__(256) void be_stage_preint_kernel(vio_config cfg, PreInt *P, int n, const double *dt, const double *acc,
-                                                               const double *gyr, int mode, double *out686) {
-    __shared__ PreWork pw;
-    __shared__ double lds_fv[PREINT_MANY_LDS_DOUBLES];
-    preint_load(*P, pw);
-    if (mode == 0)
-        for (int q = 0; q < n; q++) preint_propagate(*P, pw, cfg, dt[q], ld3(acc + 3 * q), ld3(gyr + 3 * q));
-    else {
-        PreintNoSide none;
-        preint_propagate_many<false>(*P, pw, cfg, n, PreintArrays{dt, (const double (*)[3])acc, (const double (*)[3])gyr}, none, mode == 2, lds_fv);
-    }
-    preint_store(*P, pw);
-    stage_preint_out(*P, out686);
-}
-// What be_ingest adds to preint_propagate_many: the n samples of a ring's interval as the source (PreintRing) and the world-state step
-// (WorldStep) as the side job, append on.  world31 (in and out) = WorldStep's fields acc_0 gyr_0 P V R(9) Ba Bg g, then the overflow
-// bits by be_ingest's rule.
-__global__ __launch_bounds__(256) void be_stage_preint_ring_kernel(vio_config cfg, PreInt *P, PreintRing ring, double *world31, double *out686) {
-    __shared__ PreWork pw;
-    __shared__ double lds_fv[PREINT_MANY_LDS_DOUBLES];
-    const double *w = world31;
-    const int t = threadIdx.x;
-    preint_load(*P, pw);
-    WorldStep ws = {ld3(w), ld3(w + 3), ld3(w + 6), ld3(w + 9), ldm(w + 12), ld3(w + 21), ld3(w + 24), ld3(w + 27)};
-    const int nb0 = P->n_buf;
-    preint_propagate_many<true>(*P, pw, cfg, ring.n, ring, ws, true, lds_fv);
-    if (t == 0) world31[30] = nb0 + ring.n > VIO_IMU_SLOT_CAP ? 2 : 0;
-    if (t == 64) { st3(world31, ws.a0); st3(world31 + 3, ws.g0); st3(world31 + 6, ws.P); st3(world31 + 9, ws.V); stm(world31 + 12, ws.R); }
-    preint_store(*P, pw);
-    stage_preint_out(*P, out686);
-}
 // IntegrationBase::evaluate and the raw (un-whitened) Jacobian of IMUFactor::Evaluate on a caller-supplied pre-integration (P: delta state,
 // jacobian, linearisation biases).  Lane 0: imu_raw_residual and imu_raw_jacobian (r15, J450 = 15 x 30 row-major, columns pose_i(6)
 // speedbias_i(9) pose_j(6) speedbias_j(9)); lanes 1-4: the four imu_raw_jacobian_part calls into a 15 x 31 buffer as be_stage_imu_block_kernel

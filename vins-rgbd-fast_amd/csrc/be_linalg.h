@@ -1,4 +1,4 @@
-// Block / wavefront primitives and the dense FP64 linear algebra of the back-end kernels (included by be_kernels.hip only):
+// Block / wavefront primitives and the dense FP64 linear algebra of the back-end kernels (be_kernels.hip, be_ingest.hip, stage_linalg.hip):
 //   * DPP + v_readlane wavefront reductions, block sums / scans
 //   * symmetric eigen-solvers (Jacobi for the 15x15 block, Householder tridiagonalisation + implicit QL for the prior)
 //   * landmark Schur complement on v_mfma_f64_16x16x4_f64 (HBM, LDS-tile and LDS-staged variants)

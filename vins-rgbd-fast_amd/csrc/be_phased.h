@@ -1,4 +1,4 @@
-// PHASED solver (included at the end of be_kernels.hip): the trust-region loop of optimization() (estimator.cpp:1161-1368) cut into
+// PHASED solver (included at the top of be_kernels.hip): the trust-region loop of optimization() (estimator.cpp:1161-1368) cut into
 // kernels.  The persistent kernel (be_solve_kernel_512) gives one workgroup = one CU to a sequence for the whole solve: at S = 128 half
 // of the 256 CUs idle and the other half wait on their own dependent phases.  Here every data-parallel phase is a launch that covers
 // all sequences with many workgroups each -- residual evaluation (one thread per residual), frame-pair / IMU Gram blocks on the FP64
@@ -8,6 +8,9 @@
 // synchronisation); sequences that have converged fall through.  State between kernels: SolveSt (vio_state.h) + the vectors that
 // already live in HBM.  Same mathematics and the same iteration / acceptance logic as solve_body; sums are formed in a fixed order,
 // so results are deterministic and independent of the batch a sequence runs in.
+#pragma once
+#include "be_solve_common.h"
+
 #define PS_LDS_TILE_DOUBLES 16896   // 66 tiles (LW = 176, W = 10): the most ps_serial keeps resident in LDS
 
 namespace {

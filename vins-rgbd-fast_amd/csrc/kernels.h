@@ -4,7 +4,7 @@
 #include "vio_state.h"
 #include "../../include/vio_synth.h"
 
-// pipelined pre-integration (be_kernels.hip preint_propagate_many; be_ingest and be_marg run it): samples per chunk, and the LDS doubles
+// pipelined pre-integration (be_preint.h preint_propagate_many; be_ingest and be_marg run it): samples per chunk, and the LDS doubles
 // it borrows from its caller (F 15x15 and V 15x18 of every sample of a chunk); the host sizes the marginalisation's dynamic LDS with the same
 // macro
 #define PI_CH 8
@@ -184,7 +184,7 @@ __global__ void be_stage_projection_kernel(vio_config cfg, const double *in, int
 __global__ void be_stage_imu_block_kernel(const PreInt *P, const double *par, double g_norm, double *G961);
 __global__ void be_stage_preint_kernel(vio_config cfg, PreInt *P, int n, const double *dt, const double *acc, const double *gyr, int mode,
                                        double *out686);
-// Sample source of preint_propagate_many (be_kernels.hip) in be_ingest and in its stage harness: the frame's interval of a sequence's IMU
+// Sample source of preint_propagate_many (be_preint.h) in be_ingest and in its stage harness: the frame's interval of a sequence's IMU
 // ring (getIMUInterval + the dt of processMeasurements, estimator.cpp:185-200): n samples from `head`, the last one being the first at or
 // after curTime.  dt runs from prevTime to the first stamp, between stamps, and up to curTime.
 struct PreintRing {

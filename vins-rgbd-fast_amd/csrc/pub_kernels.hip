@@ -73,7 +73,7 @@ __device__ void publish_seq(const PubIn &in, const PubOut &out) {
         }
         __syncthreads();
         if (want[0] || want[1] || want[2]) {
-            // feature_per_frame[0]: the row of window frame `start`, addressed as obs_ptr (be_kernels.hip): physical = (frame + ring_base) % (W + 1)
+            // feature_per_frame[0]: the row of window frame `start`, addressed as obs_ptr (be_ctx.h): physical = (frame + ring_base) % (W + 1)
             const double *obs0 = in.lm_obs + ((size_t)slot * W1 + (start + ring) % W1) * VIO_OBS_D;
             const dm::v3 pw = world_point(in, start, obs0, in.lm_depth[slot]);
             if (want[0] && out.cloud && row[0] < out.cap) dm::st3(out.cloud + (size_t)row[0] * 3, pw);
